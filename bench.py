@@ -2,6 +2,12 @@
 
     python bench.py --gpus N --steps K --warmup W [--config {0,1,3,4}]       (N > 1: re-executes itself under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                  (also the extra legs: sustained, bf16 mode, h2d, B = 1 latency, gather, host processes,
+                                                 other configs, strong scaling, dominant-kernel roofline probes, CPU baseline)
+    python bench.py ... --dump-outputs DIR      (writes what the last timed step returned as DIR/<name>.npy, float32)
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the result line; the extra legs run only under --full (or when
+an option asks for one explicitly).
 
 Default workload (BASELINE.json configs[1]/[2], the configuration the metric is quoted on): per GPU 64 environments, 256x256
 RGB-D frames, 80-token instruction, full HCM model (2x ResNet-50 RGB, 2x GN-ResNet-50 depth, BERT-base, cross-modal block,
@@ -337,6 +343,13 @@ def _act_stepper(args, cfg, eng, B, rank, local_rank, hi_only, dev, stager_ok):
                                               reuse_instruction=args.reuse_instruction and mask is None and state["tick"] > 3,
                                               host_frames=host_frames, gather=gather)
         return r
+
+    def outputs(r):
+        """What the caller of the step receives (--dump-outputs): the step's result and the recurrent state it handed back."""
+        if hi_only:
+            return {"logits": r, "hidden_hi": state["hh"]}
+        return {"records": r, "hidden_hi": state["hh"], "hidden_lo": state["lh"]}
+    step.outputs = outputs
     return step
 
 
@@ -365,10 +378,33 @@ def build_probe_workload(args):
         d, i = sets[state["tick"] & 1]
         state["tick"] += 1
         return probe.forward(d, i)
+    step.outputs = lambda r: {"output": r}
     esz = 2 if prec == "fp16" else 4
     # depth f32 in + instruction tensor in + (B,L,256) out, weights once per batch
     alg_bytes = B * (256 * 256 * 4 + L * 768 * esz + L * 256 * esz) + (3.26e6 + 1.02e6) * esz
     return cfg, B, probe, step, alg_bytes, prec
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(raw_step, r):
+    """Host float32 copies of what the last step returned (r: its result; N > 1: the gathered records of every rank)."""
+    return {k: v.detach().float().cpu().numpy() for k, v in raw_step.outputs(r).items()}
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: one DIR/<name>.npy per output, float32.  Should the whole exceed DUMP_LIMIT_BYTES (a large --batch), every array
+    over its even share of the budget is replaced by a fixed sample of its flattened elements (seed 0, indices in order), the same on every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(outputs))
+    total = sum(a.nbytes for a in outputs.values())
+    for name, a in outputs.items():
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _respawn(args):
@@ -394,47 +430,58 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=1, choices=[0, 1, 3, 4], help="BASELINE.json configs index (1 = the headline workload)")
-    ap.add_argument("--no-kernel-probe", action="store_true", help="skip the dominant-kernel timing (profiler runs: keeps the trace to the step's own launches)")
+    ap.add_argument("--full", action="store_true", help="also run every extra leg, probe and baseline (the defaults marked `--full` below); "
+                    "without it the run only times the K steps of the headline workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "(action records, recurrent states; configs[3]: the cross-modal output) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-kernel-probe", action="store_true", help="skip the dominant-kernel timing of --full (profiler runs: keeps the trace to the step's own launches)")
     ap.add_argument("--prewarm", type=int, default=40, help="untimed clock-ramp steps before the W warm-up steps (0 for profiler runs)")
-    ap.add_argument("--sustain", type=float, default=5.0, help="seconds of the additional sustained measurement reported as `sustained` (0 = skip)")
+    ap.add_argument("--sustain", type=float, default=None, help="seconds of the additional sustained measurement reported as `sustained` (default 5 with --full, else 0 = skip)")
     ap.add_argument("--batch", type=int, default=0, help="environments per GPU (default: the BASELINE size of the config)")
     ap.add_argument("--total-batch", type=int, default=0, help="strong scaling as the PRIMARY value: total environments, split evenly over the ranks; "
                                                                "default 0 = weak scaling at --batch per GPU (N > 1 then adds a `strong` leg at --strong-total)")
-    ap.add_argument("--strong-total", type=int, default=512, help="N > 1: total environments of the additional strong-scaling leg reported as `strong` "
-                                                                  "(BASELINE configs[2]: 512; 0 = skip)")
+    ap.add_argument("--strong-total", type=int, default=None, help="N > 1: total environments of the additional strong-scaling leg reported as `strong` "
+                                                                   "(BASELINE configs[2]: 512, the default with --full; else 0 = skip)")
     ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16", "fp32"],
                     help="fp16 = the measured 16-bit mode (range-calibrated fp16 tiles); bf16 = bf16 tiles in BERT / RGB trunks / cross-modal block")
-    ap.add_argument("--latency-leg", type=int, default=1, help="N = 1, configs[1]: also report the synchronous latency of a single-environment (B = 1) step, "
-                    "the reference's own evaluation loop, for both graph replay forms (0 = skip)")
+    ap.add_argument("--latency-leg", type=int, default=None, help="N = 1, configs[1]: also report the synchronous latency of a single-environment (B = 1) step, "
+                    "the reference's own evaluation loop, for both graph replay forms (default 1 with --full, else 0 = skip)")
     ap.add_argument("--chain-graphs", choices=("auto", "0", "1"), default=None, help="engine option chain_graphs for the timed legs: one linear hipGraph per chain "
                     "(lower host cost and B = 1 latency, 2-4 %% less pipelined throughput); default 0 = the single forked graph, the measured configuration -- "
                     "except with --h2d, where the default is the engine's own choice (auto: the frame copies overlap BERT in that form)")
-    ap.add_argument("--bf16-leg", type=float, default=2.0, help="N = 1, configs[1], --precision fp16: seconds of an additional run of the SAME workload on a "
-                                                                 "`precision=\"bf16\"` engine, reported as `bf16_mode` (0 = skip)")
-    ap.add_argument("--h2d-leg", type=float, default=2.0, help="N = 1, configs[1]: seconds of an additional PCIe-inclusive run of the SAME workload (pinned host "
-                    "frames copied inside every step) reported as `h2d` (0 = skip)")
+    ap.add_argument("--bf16-leg", type=float, default=None, help="N = 1, configs[1], --precision fp16: seconds of an additional run of the SAME workload on a "
+                                                                  "`precision=\"bf16\"` engine, reported as `bf16_mode` (default 2 with --full, else 0 = skip)")
+    ap.add_argument("--h2d-leg", type=float, default=None, help="N = 1, configs[1]: seconds of an additional PCIe-inclusive run of the SAME workload (pinned host "
+                    "frames copied inside every step) reported as `h2d` (default 2 with --full, else 0 = skip)")
     ap.add_argument("--torch-gather", action="store_true", help="N > 1: the per-step all-gather through torch.distributed instead of the library's own "
                                                                 "RCCL call behind the step (A/B of rounds 1-2 vs round 3)")
     ap.add_argument("--reuse-instruction", action="store_true",
                     help="NOT the headline configuration: steps after the first skip BERT (instructions unchanged; hcm_act_ex flag)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU-oracle baseline of --full")
     ap.add_argument("--cpu-batches", action="store_true", help="additionally time the CPU oracle at batch 4, 16 and 64, best of 5 steps each "
-                                                               "(BASELINE.md section 3's protocol; minutes of CPU work, not in the default run)")
+                                                               "(BASELINE.md section 3's protocol; minutes of CPU work, not in the --full run by default)")
     ap.add_argument("--h2d", action="store_true", help="include the per-step host->device staging of uint8 RGB + f32 depth "
                     "(pinned buffers) in the timed region: the PCIe-inclusive rate quoted in DESIGN.md, never the headline value")
     ap.add_argument("--h2d-prestage", action="store_true", help="with --h2d: copy the frames in front of the step on the caller's stream instead of "
                     "handing the pinned host frames to the library (HCM_ACT_HOST_FRAMES: one copy per encoder chain inside the step)")
     ap.add_argument("--no-graph", action="store_true", help="enqueue the kernels of a step eagerly instead of replaying the captured hipGraph")
     ap.add_argument("--probe-lds-ring", action="store_true", help="configs[3] A/B aid: the cross-modal layer with its weights through the LDS ring (hcm_op_vla_layer) instead of fragment-order weights read into registers")
-    ap.add_argument("--configs-leg", type=float, default=1.5, help="N = 1 default run: seconds per configuration of the bounded `configs` block (BASELINE configs[0], [3], [4] "
-                    "at their own batch sizes: value, ms_per_step, roofline.frac); 0 = skip")
-    ap.add_argument("--host-procs-leg", type=int, default=8, help="N = 1 default run: processes of the `host_8proc` leg (tools/host_procs.py: N processes pinned to 2 cores each, "
-                    "every one driving its own engine through the real graph-replay call on the shared GPU: host time inside act()); 0 = skip")
-    ap.add_argument("--gather-leg", type=float, default=1.0, help="N = 1 default run: seconds per side of `gather_world1` -- the same step with the library's collective "
-                    "(hcm_act_gather through real librccl on a one-rank communicator) against the plain step; 0 = skip")
+    ap.add_argument("--configs-leg", type=float, default=None, help="N = 1 default-workload run: seconds per configuration of the bounded `configs` block (BASELINE configs[0], [3], [4] "
+                    "at their own batch sizes: value, ms_per_step, roofline.frac); default 1.5 with --full, else 0 = skip")
+    ap.add_argument("--host-procs-leg", type=int, default=None, help="N = 1 default-workload run: processes of the `host_8proc` leg (tools/host_procs.py: N processes pinned to 2 cores each, "
+                    "every one driving its own engine through the real graph-replay call on the shared GPU: host time inside act()); default 8 with --full, else 0 = skip")
+    ap.add_argument("--gather-leg", type=float, default=None, help="N = 1 default-workload run: seconds per side of `gather_world1` -- the same step with the library's collective "
+                    "(hcm_act_gather through real librccl on a one-rank communicator) against the plain step; default 1 with --full, else 0 = skip")
     args = ap.parse_args()
     if args.chain_graphs is None:
         args.chain_graphs = "auto" if args.h2d else "0"
+    # the extra legs: on by default under --full, off in a plain run unless asked for by their own option
+    for name, full_default in (("sustain", 5.0), ("strong_total", 512), ("latency_leg", 1), ("bf16_leg", 2.0), ("h2d_leg", 2.0),
+                               ("configs_leg", 1.5), ("host_procs_leg", 8), ("gather_leg", 1.0)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    kernel_probe = args.full and not args.no_kernel_probe
+    with_cpu_baseline = (args.full or args.cpu_batches) and not args.no_cpu_baseline
     if args.gpus > 1 and "RANK" not in os.environ:
         if args.config != 1:
             raise SystemExit("--config 0/3/4 are single-GPU roofline lines; the multi-GPU workload is configs[1]/[2]")
@@ -512,9 +559,10 @@ def main():
             if rank == 0:
                 print("bench.py: " + gather_note, file=sys.stderr)
 
-    def run_leg(B, raw_step, steps, sustain=0.0, with_overlap=False):
+    def run_leg(B, raw_step, steps, sustain=0.0, with_overlap=False, keep_outputs=False):
         """One measured leg at B environments per rank: rank-tagged gather check, untimed warm-up, K timed steps between barriers (MAX over ranks),
-        validation of what the step returned.  -> dict(dt, host_us, ranks_seen, sustained, overlapped)"""
+        validation of what the step returned.  -> dict(dt, host_us, ranks_seen, sustained, overlapped, outputs)
+        keep_outputs: `outputs` = host float32 copies of what the LAST timed step returned, taken before anything else runs."""
         global_B = B * world
         lo_e, hi_e = shard_range(global_B, world, rank)     # this rank's contiguous block of environments e -> rank e // B
         all_rec = torch.empty(global_B, 7, device=dev) if use_dist else None
@@ -587,7 +635,9 @@ def main():
             step()
         dt = timed(steps)
         res = {"B": B, "global_B": global_B, "dt": dt, "steps": steps, "host_us": last["host_s"] * 1e6, "ranks_seen": ranks_seen,
-               "sustained": None, "overlapped": None}
+               "sustained": None, "overlapped": None, "outputs": None}
+        if keep_outputs:
+            res["outputs"] = step_outputs(raw_step, last["full"] if use_dist else last["r"])
         # what the step returned is checked, not only timed: finite, and (N>1) this rank's rows of the gathered records are its own
         r = last["r"]
         assert torch.isfinite(r.float()).all(), "non-finite outputs"
@@ -616,7 +666,9 @@ def main():
                                  "note": "all-gather of step i on a communication stream, overlapping the compute of step i+1 (needs a pipelined simulator)"}
         return res
 
-    leg = run_leg(B, raw_step, args.steps, sustain=args.sustain, with_overlap=use_dist)
+    leg = run_leg(B, raw_step, args.steps, sustain=args.sustain, with_overlap=use_dist and args.full, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg["outputs"])
     global_B, dt, host_us = leg["global_B"], leg["dt"], leg["host_us"]
     sustained, overlapped = leg["sustained"], leg["overlapped"]
     strong = None
@@ -643,7 +695,7 @@ def main():
             bf16_mode = {"value": round(l2["global_B"] * n2 / l2["dt"], 2), "ms_per_step": round(l2["dt"] / n2 * 1e3, 3), "steps": n2,
                          "dtype": dtype_string(a2, eng2), "note": "same workload, same timed-region protocol, on an engine built with precision=\"bf16\""}
             eng2.close()
-            if not args.no_kernel_probe:
+            if kernel_probe:
                 # the mode's own roofline block: the same dominant launch (BERT FFN1 on gemm256f_kernel) on bf16 tiles, timed live like the fp16 one
                 dk2 = dominant_kernel_probe(B2, cfg.instr_len, dtype="bf16")
                 v2 = bf16_mode["value"] * GFLOP[1] / 1e3
@@ -875,7 +927,7 @@ def main():
                 whole["basis"] = "cached-instruction variant: 36.9 - 13.83 (BERT) GFLOP per env-step x env-steps/s"
             roof = dict(whole)
             roof["scope"] = "whole step"
-            if args.precision != "fp32" and not args.no_kernel_probe and args.config in (1, 4) and not STUB:
+            if args.precision != "fp32" and kernel_probe and args.config in (1, 4) and not STUB:
                 try:
                     L = cfg.instr_len
                     dk = dominant_kernel_probe(B, L)
@@ -896,7 +948,7 @@ def main():
             out["config"]["hipgraph"] = {"enabled": not args.no_graph, "inputs": "read in place from two alternating device buffer sets"}
         if hasattr(eng, "query"):
             out["config"]["hipgraph"] = {"enabled": not args.no_graph and args.config in (0, 1), "chain_graphs": args.chain_graphs, "graph_steps": eng.query(7), "eager_steps": eng.query(8)}
-        if not args.no_cpu_baseline and world == 1 and args.config == 1 and not STUB:          # reported on rank 0 at N=1 only
+        if with_cpu_baseline and world == 1 and args.config == 1 and not STUB:          # reported on rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(cfg, *weights)
             out["cpu_baseline"]["batches"] = cpu_baseline_protocol(cfg, *weights, budget_s=None if args.cpu_batches else 30.0)
         sys.stdout.flush()

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -21,7 +23,7 @@ def _run(extra, env_extra=None, timeout=600):
 
 
 def test_gpus_2_spawns_its_own_ranks_and_prints_one_line():
-    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm", "1"])
+    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm", "1", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout
@@ -41,6 +43,25 @@ def test_gpus_1_stays_in_process():
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.strip()][0])
     assert out["n_gpus"] == 1 and "strong" not in out and "ranks_seen" not in out
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full only the K timed steps run (no extra legs, probes or baselines in the line); --dump-outputs writes what the last
+    timed step returned as float32 .npy files, the same on every run with the same arguments."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm", "1", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.strip()][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert not {"sustained", "strong", "cpu_baseline", "bf16_mode", "h2d", "single_env_latency", "gather_world1", "host_8proc", "configs"} & set(out)
+        assert sorted(os.listdir(d)) == ["hidden_hi.npy", "hidden_lo.npy", "records.npy"]
+        dumps.append({f: np.load(d / f) for f in os.listdir(d)})
+    B = 2
+    assert dumps[0]["records.npy"].shape == (B, 7) and dumps[0]["hidden_hi.npy"].shape[1:] == (B, 512)
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][f]), f
 
 
 def test_world_size_mismatch_is_refused():

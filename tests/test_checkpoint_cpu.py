@@ -101,24 +101,41 @@ def test_reference_written_checkpoint_structure():
     _strict_load(cfg, hi, lo)
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/robo_vln_baselines"), reason="needs the reference checkout (build container only)")
+ROUNDTRIP_CFG = dict(rgb_hw=128, depth_hw=128, instr_len=20, bert_layers=1)
+
+
+def pattern_weights(cfg):
+    """(hi, lo) state_dicts in spec order, every tensor with its own value pattern (tensor i holds 64 * i + (0..60 repeating), exact in fp32,
+    compressible a few thousand to one): the weights of tests/golden/ref_checkpoint_roundtrip.pth.xz (oracle/gen_checkpoint_roundtrip_fixture.py)."""
+    out = []
+    for spec in (synth.high_level_spec(cfg), synth.low_level_spec(cfg)):
+        sd = {}
+        for i, (key, shape, kind, _) in enumerate(spec):
+            if kind == "nbt":
+                sd[key] = np.asarray(i, dtype=np.int64)
+            else:
+                n = int(np.prod(shape)) if len(shape) else 1
+                sd[key] = (np.arange(n, dtype=np.int64) % 61 + 64 * i).astype(np.float32).reshape(shape)
+        out.append(sd)
+    return out
+
+
 def test_checkpoint_saved_from_reference_modules_roundtrips_exactly():
-    """Container-only: the imported reference models (synthetic weights loaded with strict=True) are saved exactly as
-    RoboDaggerTrainer.save_checkpoint does (hierarchical_trainer.py:349-363) and read back: every value identical, strict load ok."""
-    from oracle import ref_shims
-    cfg = HCMConfig(rgb_hw=128, depth_hw=128, instr_len=20, bert_layers=1).validate()
-    hi_sd, lo_sd = synth.make_weights(cfg, seed=2)
-    hi, lo = ref_shims.build_models(cfg, hi_sd, lo_sd)
-    buf = io.BytesIO()
-    torch.save({"high_level_state_dict": hi.state_dict(), "low_level_state_dict": lo.state_dict(), "config": ref_shims.model_config(cfg)}, buf)
-    buf.seek(0)
-    hi2, lo2, conf = checkpoint.load_checkpoint(buf)
-    for got, ref in ((hi2, hi.state_dict()), (lo2, lo.state_dict())):
-        keys = [k for k in ref if not k.endswith(checkpoint.IGNORED_SUFFIXES)]
-        assert list(got) == keys
-        for k in keys:
-            assert torch.equal(got[k], ref[k]), k
+    """tests/golden/ref_checkpoint_roundtrip.pth.xz: the imported reference models (pattern_weights loaded with strict=True) saved exactly
+    as RoboDaggerTrainer.save_checkpoint does (hierarchical_trainer.py:349-363), xz-compressed.  Read back: the keys in the order the
+    reference modules wrote them (that of the synth.py specs), every value identical, strict load ok."""
+    import lzma
+    import os
+    cfg = HCMConfig(**ROUNDTRIP_CFG).validate()
+    hi_sd, lo_sd = pattern_weights(cfg)
+    with lzma.open(os.path.join(GOLD, "ref_checkpoint_roundtrip.pth.xz"), "rb") as f:
+        hi2, lo2, conf = checkpoint.load_checkpoint(io.BytesIO(f.read()))
+    for got, want in ((hi2, hi_sd), (lo2, lo_sd)):
+        assert list(got) == list(want)
+        for k in want:
+            assert torch.equal(got[k], torch.from_numpy(np.asarray(want[k]))), k
     assert torch.equal(hi2["linear.weight"], torch.from_numpy(hi_sd["linear.weight"]))
+    assert type(conf).__module__ != "builtins" and conf["STATE_ENCODER"]["rnn_type"] == cfg.rnn_type
     _strict_load(cfg, hi2, lo2)
 
 

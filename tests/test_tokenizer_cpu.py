@@ -1,6 +1,7 @@
 """The WordPiece tokenizer of the input pipeline (robo-vln_amd/tokenizer.py) against `tokenizers.BertWordPieceTokenizer` -- the
-library the reference calls in transform_obs (common/utils.py:87-107) -- on a synthetic vocabulary everywhere, and in the
-build container also on the reference's own `vocab_files/bert-base-uncased-vocab.txt`.  The library is the test oracle only."""
+library the reference calls in transform_obs (common/utils.py:87-107) -- on a synthetic vocabulary and on the
+reference's own `vocab_files/bert-base-uncased-vocab.txt` (a fixture under tests/golden/).  The library is the test oracle only."""
+import lzma
 import os
 import tempfile
 
@@ -73,14 +74,16 @@ def test_padding_truncation_and_cache():
         WordPieceTokenizer({"a": 0})
 
 
-REAL_VOCAB = "/root/reference/vocab_files/bert-base-uncased-vocab.txt"
+REAL_VOCAB_XZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bert-base-uncased-vocab.txt.xz")
 
 
-@pytest.mark.skipif(not os.path.exists(REAL_VOCAB), reason="needs the reference checkout (build container only)")
-def test_matches_the_reference_library_on_the_real_vocabulary():
-    """The vocabulary file the reference loads (common/utils.py:105), read in place: token-for-token equality with the
-    `tokenizers` library on navigation instructions, unicode / punctuation edge cases and random strings."""
+def test_matches_the_reference_library_on_the_real_vocabulary(tmp_path):
+    """The vocabulary file the reference loads (common/utils.py:105; kept xz-compressed under tests/golden/): token-for-token equality
+    with the `tokenizers` library on navigation instructions, unicode / punctuation edge cases and random strings."""
     tk = pytest.importorskip("tokenizers")
+    REAL_VOCAB = str(tmp_path / "bert-base-uncased-vocab.txt")
+    with lzma.open(REAL_VOCAB_XZ) as src, open(REAL_VOCAB, "wb") as dst:
+        dst.write(src.read())
     ref = tk.BertWordPieceTokenizer(REAL_VOCAB, lowercase=True)
     mine = WordPieceTokenizer(REAL_VOCAB, lowercase=True)
     assert (mine.cls, mine.sep, mine.pad, mine.unk) == (101, 102, 0, 100)
