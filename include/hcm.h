@@ -35,7 +35,8 @@ enum hcm_status {
 };
 
 enum hcm_dtype { HCM_F32 = 0, HCM_BF16 = 1, HCM_I32 = 2, HCM_I64 = 3, HCM_U8 = 4, HCM_F16 = 5 };
-enum hcm_model { HCM_HIGH = 0, HCM_LOW = 1, HCM_CMA = 2 /* CMANet flat baseline: hcm_cma_create handles only */ };
+enum hcm_model { HCM_HIGH = 0, HCM_LOW = 1, HCM_CMA = 2 /* CMANet flat baseline: hcm_cma_create handles only */,
+                 HCM_S2S = 3 /* Seq2SeqNet flat baseline: hcm_s2s_create handles only */ };
 enum hcm_encoder { HCM_ENC_RESNET = 0, HCM_ENC_SIMPLECNN = 1 };
 enum hcm_rnn { HCM_LSTM = 0, HCM_GRU = 1 };
 
@@ -302,6 +303,58 @@ int hcm_cma_create(const hcm_cma_config* cfg, hcm_handle* out);
  *   the tensor it was given and returns it; here h_out may alias h_in to get the same effect. */
 int hcm_cma_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int L,
                     const float* h_in, const float* mask, float* out, float* stop, float* h_out, void* stream);
+
+/* ---- Seq2SeqNet flat baseline (paper_configs/seq2seq_robo.yaml, seq2seq_robo_pm.yaml) ----
+ * `Seq2SeqNet` (models/seq2seq.py:21-189; constructed at robo_vln_trainer.py:333-339 whenever MODEL.CMA.use is false) behind the same
+ * handle type: hcm_s2s_create -> hcm_load_tensor(h, HCM_S2S, key, ...) for every entry of the module's state_dict (strict; `sub_goal_linear.*`
+ * and `progress_monitor.*` are always part of it, seq2seq.py:104-109, and `sub_goal_linear` is never read by forward) -> hcm_finalize ->
+ * hcm_s2s_forward ...; hcm_query / hcm_last_error / hcm_destroy and the tap hooks work as for the other handles (taps: `s2s.instruction`,
+ * `s2s.depth_flat`, `s2s.rgb_flat`, `s2s.rnn_in`).  hcm_query(HCM_NUM_RECURRENT_LAYERS) = 2 for LSTM, 1 for GRU (seq2seq.py:132-134). */
+typedef struct hcm_s2s_config {
+    int32_t struct_size;
+    int32_t precision;            /* as hcm_cma_config: 16-bit trunks behind the range calibration, fp32 text / recurrent side */
+    int32_t max_batch;
+    int32_t rgb_h, rgb_w, depth_h, depth_w;   /* frame sizes: the limits of hcm_config for the chosen encoder kinds */
+    int32_t instr_len;            /* MAXIMUM padded token count per instruction (<= 256); every forward passes its own L <= instr_len */
+    int32_t vocab_size, embedding_size, instr_hidden;    /* MODEL.INSTRUCTION_ENCODER.* (default.py:97-115); instr_hidden: a multiple of 64, <= 512 */
+    int32_t instr_rnn;            /* INSTRUCTION_ENCODER.rnn_type: HCM_LSTM or HCM_GRU (instruction_encoder.py:42) */
+    int32_t bidirectional;        /* must be 0: with final_state_only the encoder returns (2,B,H) (instruction_encoder.py:90) and seq2seq.py:163 raises */
+    int32_t rgb_encoder, depth_encoder;       /* hcm_encoder: TorchVisionResNet50 / VlnResnetDepthEncoder in flat mode, or SimpleRGBCNN / SimpleDepthCNN (seq2seq.py:50-82) */
+    int32_t rgb_out, depth_out, depth_baseplanes;
+    int32_t hidden, rnn_type;     /* MODEL.STATE_ENCODER.* */
+    int32_t num_actions;          /* 2 */
+    int32_t num_sub_tasks;        /* rows of sub_goal_linear (seq2seq.py:108): part of the state_dict only */
+    int32_t use_prev_action;      /* must be 0: SEQ2SEQ.use_prev_action (default.py:202 default False; seq2seq.py:167-171 raises at the cat) */
+    int32_t is_bert;              /* must be 0: INSTRUCTION_ENCODER.is_bert selects LanguageEncoder (seq2seq.py:45-46), not built */
+    int32_t progress_monitor;     /* PROGRESS_MONITOR.use (seq2seq_robo_pm.yaml): tanh(progress_monitor(x)) (seq2seq.py:177) becomes an extra OUTPUT */
+    int32_t ablate_instruction;   /* seq2seq.py:156-161: `embedding * 0` behind an encoder -- the encoder is then not run, zeros go in */
+    int32_t ablate_depth;
+    int32_t ablate_rgb;
+    int32_t reserved[6];
+} hcm_s2s_config;
+
+int hcm_s2s_create(const hcm_s2s_config* cfg, hcm_handle* out);
+
+/* Replaces `output, stop_out, rnn_hidden_states = actor_critic((observations, rnn_hidden_states, prev_actions, masks))`
+ * (robo_vln_trainer.py:1096 -> models/seq2seq.py:140-189).
+ *   rgb (B,H,W,3) HCM_F32 / HCM_U8; depth (B,H,W,1) f32
+ *   ids (B_instr,L) HCM_I32 / HCM_I64 / HCM_F32, 0 = padding; B_instr = B, or 1: ONE instruction for all B frames (the `.expand` of
+ *       seq2seq.py:163) -- the encoder then runs for one sample.  The instruction vector is the encoder's hidden state at each sample's own
+ *       last non-padding token (final_state_only, instruction_encoder.py:86-90).  A row that is all padding makes the reference raise
+ *       (pack_padded_sequence); here it yields the zero vector, as such a row does on the CMANet path.
+ *   h_in (R,B,hidden) f32, R = 2 (LSTM) / 1 (GRU);  mask (B,) f32 (column 0 of the reference's masks, seq2seq.py:172)
+ *   out (B,num_actions), stop (B,1), h_out (R,B,hidden): f32 outputs; h_out may alias h_in
+ *   progress (B,1) f32 out = tanh(progress_monitor(x)) when the config's progress_monitor is set; must be NULL when it is clear.  (The
+ *       reference computes the value only while AuxLosses is active and keeps it inside the loss, seq2seq.py:176-185; the loss itself needs
+ *       observations["progress"] and stays with the caller.)
+ * Repeated calls with the same pointers on a non-default stream are captured into a hipGraph and replayed, as for the other handle kinds. */
+int hcm_s2s_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int B_instr, int L,
+                    const float* h_in, const float* mask, float* out, float* stop, float* progress, float* h_out, void* stream);
+/* Training / validation path: T*N rows at once, time-major, then the masked T-step scan (RNNStateEncoder.seq_forward, state_encoder.py:83-133),
+ * as hcm_low_forward_seq.  ids (B_instr,L) with B_instr = T*N or 1; masks (T*N,); h_in / h_out (R,N,hidden); out (T*N,num_actions), stop (T*N,1),
+ * progress (T*N,1) or NULL.  T*N must not exceed max_batch. */
+int hcm_s2s_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int B_instr,
+                        int L, const float* h_in, const float* masks, float* out, float* stop, float* progress, float* h_out, void* stream);
 
 /* ---- test / profiling hooks (not part of the drop-in surface) ---- */
 

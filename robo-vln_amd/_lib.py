@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhcm_dev.so" if os.environ.get("HCM_DEV_LIB", "0") not in ("", "0") else "libhcm.so")
 
 HCM_F32, HCM_BF16, HCM_I32, HCM_I64, HCM_U8, HCM_F16 = 0, 1, 2, 3, 4, 5
-HCM_HIGH, HCM_LOW, HCM_CMA = 0, 1, 2
+HCM_HIGH, HCM_LOW, HCM_CMA, HCM_S2S = 0, 1, 2, 3
 HCM_ENC_RESNET, HCM_ENC_SIMPLECNN = 0, 1
 HCM_LSTM, HCM_GRU = 0, 1
 (HCM_NUM_RECURRENT_LAYERS, HCM_HIDDEN_SIZE, HCM_NUM_ACTIONS, HCM_RECORD_WIDTH, HCM_WORKSPACE_BYTES,
@@ -43,7 +43,20 @@ class HcmCmaConfigStruct(C.Structure):
         "instr_rnn", "ablate_instruction", "ablate_depth", "ablate_rgb")] + [("reserved", C.c_int32 * 4)]
 
 
+class HcmS2sConfigStruct(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "struct_size", "precision", "max_batch", "rgb_h", "rgb_w", "depth_h", "depth_w", "instr_len",
+        "vocab_size", "embedding_size", "instr_hidden", "instr_rnn", "bidirectional", "rgb_encoder", "depth_encoder",
+        "rgb_out", "depth_out", "depth_baseplanes", "hidden", "rnn_type", "num_actions", "num_sub_tasks",
+        "use_prev_action", "is_bert", "progress_monitor", "ablate_instruction", "ablate_depth", "ablate_rgb")] + [("reserved", C.c_int32 * 6)]
+
+
 EXPORTS = {
+    "hcm_s2s_create": (C.c_int, [C.POINTER(HcmS2sConfigStruct), C.POINTER(C.c_void_p)]),
+    "hcm_s2s_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hcm_s2s_forward_seq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hcm_cma_create": (C.c_int, [C.POINTER(HcmCmaConfigStruct), C.POINTER(C.c_void_p)]),
     "hcm_cma_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

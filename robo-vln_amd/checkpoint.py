@@ -82,6 +82,24 @@ def load_checkpoint(path_or_file, map_location="cpu"):
     return clean[0], clean[1], ckpt.get("config")
 
 
+def load_flat_checkpoint(path_or_file, map_location="cpu"):
+    """-> (state_dict, config) from a checkpoint of the flat trainer, `torch.save({"state_dict": actor_critic.state_dict(), "config": ...})`
+    (robo_vln_baselines/robo_vln_trainer.py:367-372; loaded back at :355): the file that holds a `CMANet` or a `Seq2SeqNet`.  Read through
+    the same restricted un-pickler as the hierarchical trainer's checkpoints."""
+    ckpt = torch.load(path_or_file, map_location=map_location, pickle_module=_TolerantPickle, weights_only=False)
+    if "state_dict" not in ckpt:
+        raise KeyError(f"checkpoint has no 'state_dict' (keys: {list(ckpt)})")
+    return dict(ckpt["state_dict"]), ckpt.get("config")
+
+
+def s2s_engine_from_checkpoint(path, cfg, **engine_kwargs):
+    """Build an S2SEngine from a flat-trainer checkpoint of a `Seq2SeqNet` (strict key / shape check inside libhcm: `sub_goal_linear.*` and
+    `progress_monitor.*` are part of every such state_dict, seq2seq.py:104-109)."""
+    from .seq2seq import S2SEngine
+    sd, _ = load_flat_checkpoint(path)
+    return S2SEngine(cfg, sd, **engine_kwargs)
+
+
 def load_ddppo_depth_weights(path_or_file, map_location="cpu"):
     """The remap `VlnResnetDepthEncoder.__init__` applies to a DDPPO point-nav checkpoint (models/encoders/resnet_encoders.py:38-52):
     for every key of `ckpt["state_dict"]`, drop the first two dotted components (`actor_critic.net.`), keep only what then starts with

@@ -183,3 +183,93 @@ class CMAConfig:
 
     def to_dict(self):
         return asdict(self)
+
+
+@dataclass
+class S2SConfig:
+    """`Seq2SeqNet` flat baseline (models/seq2seq.py:21-189) with the values of paper_configs/seq2seq_robo.yaml and
+    seq2seq_robo_pm.yaml over config/default.py:97-115,:180-216: a unidirectional instruction encoder that returns its final state
+    only, both encoders in flat mode, one recurrent state encoder over [instruction | depth | rgb]."""
+    rgb_hw: int = 256              # RGB frame height (and width when rgb_w == 0)
+    rgb_w: int = 0
+    depth_hw: int = 256            # depth frame height (and width when depth_w == 0; the ResNet depth encoder needs square frames)
+    depth_w: int = 0
+    instr_len: int = 80            # longest padded instruction handed to the model (INSTRUCTION_ENCODER.max_length = 200)
+    vocab_size: int = 2504         # INSTRUCTION_ENCODER.vocab_size
+    embedding_size: int = 50
+    instr_hidden: int = 256        # INSTRUCTION_ENCODER.hidden_size (config/default.py:110)
+    instr_rnn: str = "LSTM"        # INSTRUCTION_ENCODER.rnn_type
+    bidirectional: bool = False
+    final_state_only: bool = True  # both Seq2Seq paper configs; the model cannot run without it (seq2seq.py:163 needs a (B, H) tensor)
+    is_bert: bool = False          # INSTRUCTION_ENCODER.is_bert (LanguageEncoder): not built
+    depth_encoder: str = "VlnResnetDepthEncoder"
+    rgb_encoder: str = "TorchVisionResNet50"
+    rgb_out: int = 256
+    depth_out: int = 128
+    depth_baseplanes: int = 32
+    hidden: int = 512
+    rnn_type: str = "LSTM"
+    num_actions: int = 2           # robo_vln_trainer.py:333-339
+    num_sub_tasks: int = 4         # rows of sub_goal_linear (seq2seq.py:108): state_dict only
+    use_prev_action: bool = False  # SEQ2SEQ.use_prev_action
+    progress_monitor: bool = False  # PROGRESS_MONITOR.use (seq2seq_robo_pm.yaml): tanh(progress_monitor(x)) becomes an extra output
+    ablate_instruction: bool = False
+    ablate_depth: bool = False
+    ablate_rgb: bool = False
+
+    def validate(self):
+        if self.bidirectional:
+            raise ValueError("Seq2SeqNet cannot run a bidirectional instruction encoder: with final_state_only it returns (2,B,H) "
+                             "(instruction_encoder.py:90) and seq2seq.py:163 raises")
+        if not self.final_state_only:
+            raise ValueError("Seq2SeqNet needs INSTRUCTION_ENCODER.final_state_only (seq2seq.py:163 expands a (B, H) tensor)")
+        if self.use_prev_action:
+            raise ValueError("SEQ2SEQ.use_prev_action is not built (config/default.py:202 default False; seq2seq.py:167-171 raises at the cat)")
+        if self.is_bert:
+            raise ValueError("INSTRUCTION_ENCODER.is_bert (LanguageEncoder, seq2seq.py:45-46) is not built")
+        if self.instr_rnn not in ("LSTM", "GRU"):
+            raise ValueError("INSTRUCTION_ENCODER.rnn_type must be LSTM or GRU (instruction_encoder.py:42)")
+        if self.rnn_type not in ("LSTM", "GRU"):
+            raise ValueError("STATE_ENCODER.rnn_type must be LSTM or GRU")
+        if self.instr_hidden % 64 or not 64 <= self.instr_hidden <= 512:
+            raise ValueError("INSTRUCTION_ENCODER.hidden_size must be a multiple of 64 up to 512")
+        if self.depth_encoder not in ("VlnResnetDepthEncoder", "SimpleDepthCNN"):
+            raise ValueError("DEPTH_ENCODER.cnn_type must be SimpleDepthCNN or VlnResnetDepthEncoder (seq2seq.py:50-53)")
+        if self.rgb_encoder not in ("TorchVisionResNet50", "SimpleRGBCNN"):
+            raise ValueError("RGB_ENCODER.cnn_type must be SimpleRGBCNN or TorchVisionResNet50 (seq2seq.py:67-70)")
+        if self.depth_encoder == "VlnResnetDepthEncoder":
+            if self.depth_w not in (0, self.depth_hw):
+                raise ValueError("depth frames must be square with the ResNet depth encoder")
+            if self.depth_hw < 64 or self.depth_hw % 64 or self.depth_hw > 1024:
+                raise ValueError("depth frame size must be a multiple of 64 (habitat's ResNetEncoder, resnet_encoders.py:37-62)")
+        return self
+
+    @property
+    def rgb_shape(self):
+        return self.rgb_hw, (self.rgb_w or self.rgb_hw)
+
+    @property
+    def depth_shape(self):
+        return self.depth_hw, (self.depth_w or self.depth_hw)
+
+    @property
+    def instr_out(self):           # InstructionEncoder.output_size (instruction_encoder.py:49-51)
+        return self.instr_hidden
+
+    @property
+    def rnn_input_size(self):      # seq2seq.py:88-92
+        return self.instr_hidden + self.depth_out + self.rgb_out
+
+    @property
+    def num_recurrent_layers(self):   # seq2seq.py:132-134
+        return 2 if self.rnn_type == "LSTM" else 1
+
+    def depth_final_spatial(self):
+        return int((self.depth_hw // 2) / 32)
+
+    def depth_compress_channels(self):
+        fs = self.depth_final_spatial()
+        return int(round(2048 / (fs * fs)))
+
+    def to_dict(self):
+        return asdict(self)

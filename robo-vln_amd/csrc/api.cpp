@@ -18,6 +18,10 @@ void prepare_cma(hcm_ctx* ctx);
 void run_refresh_instruction(hcm_ctx* ctx, const void* ids, int ids_dt, int B, const int32_t* idx, int n);   // L = ctx->cur_L
 void run_cma(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, const float* h_in,
              const float* mask, float* out, float* stop, float* h_out);
+void build_spec_s2s(hcm_ctx* ctx);
+void prepare_s2s(hcm_ctx* ctx);
+void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,
+             const float* mask, float* out, float* stop, float* progress, float* h_out, int T = 1);
 void comm_destroy(hcm_ctx* ctx);
 void run_step(hcm_ctx* ctx, bool do_hi, bool do_lo, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt,
               int B, const float* hi_h_in, const float* lo_h_in, const float* mask, const int64_t* subtask, float* logits,
@@ -335,10 +339,67 @@ int hcm_cma_create(const hcm_cma_config* cfg, hcm_handle* out) {
     return HCM_OK;
 }
 
+int hcm_s2s_create(const hcm_s2s_config* cfg, hcm_handle* out) {
+    hcm_ctx* h = nullptr;
+    REQUIRE(cfg && out, HCM_ERR_ARG, "hcm_s2s_create: null argument");
+    REQUIRE(cfg->struct_size == (int32_t)sizeof(hcm_s2s_config), HCM_ERR_ARG, "hcm_s2s_create: struct_size mismatch");
+    REQUIRE(cfg->precision == HCM_F32 || cfg->precision == HCM_BF16 || cfg->precision == HCM_F16, HCM_ERR_ARG, "precision must be HCM_F32, HCM_F16 or HCM_BF16");
+    REQUIRE(cfg->max_batch >= 1, HCM_ERR_ARG, "max_batch must be >= 1");
+    // settings the reference's Seq2SeqNet cannot run, or that select a module that is not built
+    REQUIRE(!cfg->bidirectional, HCM_ERR_UNSUPPORTED,
+            "INSTRUCTION_ENCODER.bidirectional with final_state_only returns a (2,B,H) state (instruction_encoder.py:90) and Seq2SeqNet raises at seq2seq.py:163");
+    REQUIRE(!cfg->use_prev_action, HCM_ERR_UNSUPPORTED,
+            "SEQ2SEQ.use_prev_action (config/default.py:202 default False) is not built: the reference raises at the cat of seq2seq.py:167-171");
+    REQUIRE(!cfg->is_bert, HCM_ERR_UNSUPPORTED, "INSTRUCTION_ENCODER.is_bert selects LanguageEncoder (seq2seq.py:45-46), which is not built");
+    REQUIRE(cfg->rnn_type == HCM_LSTM || cfg->rnn_type == HCM_GRU, HCM_ERR_ARG, "STATE_ENCODER.rnn_type must be LSTM or GRU");
+    REQUIRE(cfg->instr_rnn == HCM_LSTM || cfg->instr_rnn == HCM_GRU, HCM_ERR_ARG, "INSTRUCTION_ENCODER.rnn_type must be LSTM or GRU (instruction_encoder.py:42)");
+    REQUIRE(cfg->rgb_encoder == HCM_ENC_RESNET || cfg->rgb_encoder == HCM_ENC_SIMPLECNN, HCM_ERR_ARG, "RGB_ENCODER.cnn_type must be SimpleRGBCNN or TorchVisionResNet50 (seq2seq.py:67-70)");
+    REQUIRE(cfg->depth_encoder == HCM_ENC_RESNET || cfg->depth_encoder == HCM_ENC_SIMPLECNN, HCM_ERR_ARG, "DEPTH_ENCODER.cnn_type must be SimpleDepthCNN or VlnResnetDepthEncoder (seq2seq.py:50-53)");
+    REQUIRE(cfg->hidden >= 64 && cfg->hidden % 64 == 0, HCM_ERR_UNSUPPORTED, "hidden size must be a multiple of 64");
+    REQUIRE(cfg->instr_hidden >= 64 && cfg->instr_hidden % 64 == 0 && cfg->instr_hidden <= 512, HCM_ERR_UNSUPPORTED,
+            "INSTRUCTION_ENCODER.hidden_size must be a multiple of 64 up to 512");
+    REQUIRE(cfg->embedding_size >= 1 && cfg->vocab_size >= 2 && cfg->num_sub_tasks >= 1 && cfg->num_actions >= 1, HCM_ERR_ARG, "bad INSTRUCTION_ENCODER / head sizes");
+    REQUIRE(cfg->instr_len >= 1 && cfg->instr_len <= 256, HCM_ERR_UNSUPPORTED, "1 <= instr_len <= 256");
+    REQUIRE(cfg->depth_h == cfg->depth_w || cfg->depth_encoder == HCM_ENC_SIMPLECNN, HCM_ERR_UNSUPPORTED, "depth frames must be square with the ResNet depth encoder");
+    if (cfg->rgb_encoder == HCM_ENC_SIMPLECNN) REQUIRE(cfg->rgb_h >= 36 && cfg->rgb_w >= 36, HCM_ERR_UNSUPPORTED, "SimpleRGBCNN: rgb frame too small");
+    else REQUIRE(cfg->rgb_h >= 32 && cfg->rgb_w >= 32, HCM_ERR_UNSUPPORTED, "rgb frame too small");
+    if (cfg->depth_encoder == HCM_ENC_SIMPLECNN) REQUIRE(cfg->depth_h >= 36 && cfg->depth_w >= 36, HCM_ERR_UNSUPPORTED, "SimpleDepthCNN: depth frame too small");
+    else REQUIRE(cfg->depth_h >= 64 && cfg->depth_h % 64 == 0 && cfg->depth_h <= 1024, HCM_ERR_UNSUPPORTED,
+                 "depth frame size must be a multiple of 64 (habitat's ResNetEncoder: final map (H/2)/32, resnet_encoders.py:37-62)");
+    REQUIRE(cfg->depth_baseplanes == 32, HCM_ERR_UNSUPPORTED, "resnet_baseplanes is 32 in the reference (resnet_encoders.py:19)");
+    REQUIRE(cfg->rgb_out % 4 == 0 && cfg->depth_out % 4 == 0 && cfg->rgb_out >= 4 && cfg->depth_out >= 4, HCM_ERR_UNSUPPORTED, "encoder output sizes must be multiples of 4");
+    h = new hcm_ctx();
+    (void)hipGetDevice(&h->device);
+    h->kind = 2;
+    h->s2s_cfg = *cfg;
+    std::memset(&h->cfg, 0, sizeof(h->cfg));
+    hcm_config& c = h->cfg;                      // the fields the shared trunk / recurrent code reads
+    c.struct_size = (int32_t)sizeof(hcm_config);
+    c.precision = cfg->precision; c.max_batch = cfg->max_batch;
+    c.rgb_h = cfg->rgb_h; c.rgb_w = cfg->rgb_w; c.depth_h = cfg->depth_h; c.depth_w = cfg->depth_w; c.instr_len = cfg->instr_len;
+    c.rgb_encoder = cfg->rgb_encoder; c.depth_encoder = cfg->depth_encoder;
+    c.rgb_out = cfg->rgb_out; c.depth_out = cfg->depth_out; c.depth_baseplanes = cfg->depth_baseplanes;
+    c.hidden = cfg->hidden; c.rnn_type = cfg->rnn_type; c.num_actions = cfg->num_actions; c.lo_actions = cfg->num_actions; c.num_sub_tasks = cfg->num_sub_tasks;
+    h->dt = cfg->precision == HCM_BF16 ? DT_BF16 : cfg->precision == HCM_F16 ? DT_F16 : DT_F32;
+    h->dt_rgb = h->dt_bert = h->dt_vla = h->dt_depth = h->dt;
+    if (h->dt == DT_BF16) h->dt_depth = h->dt_rgb = DT_F16;          // both trunk kinds on range-folded fp16 tiles, as in the HCM handle's bf16 mode
+    try {
+        build_spec_s2s(h);
+    } catch (const std::exception& e) {
+        std::string m = e.what();
+        delete h;
+        h = nullptr;
+        return fail(nullptr, HCM_ERR_ARG, m);
+    }
+    *out = h;
+    return HCM_OK;
+}
+
 int hcm_load_tensor(hcm_handle h, int model, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(!h->finalized, HCM_ERR_STATE, "hcm_load_tensor after hcm_finalize");
     if (h->kind == 1) REQUIRE(model == HCM_CMA, HCM_ERR_ARG, "a CMANet handle takes model = HCM_CMA");
+    else if (h->kind == 2) REQUIRE(model == HCM_S2S, HCM_ERR_ARG, "a Seq2SeqNet handle takes model = HCM_S2S");
     else REQUIRE(model == HCM_HIGH || model == HCM_LOW, HCM_ERR_ARG, "model must be HCM_HIGH or HCM_LOW");
     REQUIRE(key && data && (shape || ndim == 0), HCM_ERR_ARG, "null argument");
     auto& sd = h->sd[model];
@@ -377,6 +438,11 @@ static void dry_run(hcm_ctx* h, int B) {
         run_cma(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B, nullptr, nullptr, nullptr, nullptr, nullptr);
         return;
     }
+    if (h->kind == 2) {                                // the step with one instruction per row, and the sequence path at T = 2, 3 (as below)
+        for (int T = 1; T <= 3 && T <= B; ++T)
+            run_s2s(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B / T * T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, T);
+        return;
+    }
     const bool hi = h->cfg.build_high != 0, lo = h->cfg.build_low != 0;
     for (int T = 1; T <= 3 && T <= B; ++T) {
         const int rows = B / T * T;
@@ -408,6 +474,7 @@ static void free_device_weights(hcm_ctx* h) {
     h->weight_bytes = 0;
     h->hi = hcm::HighW();
     h->lo = hcm::LowW();
+    h->s2s = hcm::S2sW();
 }
 static int calibrate_run(hcm_ctx* h, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int L, hipStream_t stream,
                          int pass = 0) {
@@ -435,6 +502,8 @@ static int calibrate_run(hcm_ctx* h, const void* rgb, int rgb_dt, const float* d
     try {
         if (h->kind == 1)
             run_cma(h, rgb, rgb_dt, depth, ids, ids_dt, B, hh, mask, rec, rec + 8 * (size_t)B, hh2);
+        else if (h->kind == 2)
+            run_s2s(h, rgb, rgb_dt, depth, ids, ids_dt, B, B, hh, mask, rec, rec + 8 * (size_t)B, nullptr, hh2);
         else if (c.build_high && c.build_low)
             run_step(h, true, true, rgb, rgb_dt, depth, ids, ids_dt, B, hh, lh, mask, nullptr, rec, 7, rec + 4, 7, rec + 6, 7, hh2, lh2);
         else if (c.build_high)
@@ -537,6 +606,7 @@ static int calibrate_run(hcm_ctx* h, const void* rgb, int rgb_dt, const float* d
     try {
         free_device_weights(h);
         if (h->kind == 1) prepare_cma(h);
+        else if (h->kind == 2) prepare_s2s(h);
         else {
             if (c.build_high) prepare_high(h);
             if (c.build_low) prepare_low(h);
@@ -579,8 +649,9 @@ static int calibrate_synthetic(hcm_ctx* h) {
     auto next = [&]() { s ^= s << 13; s ^= s >> 17; s ^= s << 5; return s; };
     for (auto& v : rgb) v = (unsigned char)(next() >> 24);
     for (auto& v : dep) v = (float)(next() >> 8) * (1.0f / 16777216.0f);
-    if (h->kind == 1) {
-        for (auto& v : ids) v = 1 + (int64_t)(next() % (uint32_t)(h->cma_cfg.vocab_size > 2 ? h->cma_cfg.vocab_size - 1 : 1));      // CMANet's own vocabulary, no padding
+    if (h->kind == 1 || h->kind == 2) {
+        const int vocab = h->kind == 1 ? h->cma_cfg.vocab_size : h->s2s_cfg.vocab_size;
+        for (auto& v : ids) v = 1 + (int64_t)(next() % (uint32_t)(vocab > 2 ? vocab - 1 : 1));      // the model's own vocabulary, no padding
     } else {
         for (auto& v : ids) v = 1000 + (int64_t)(next() % (uint32_t)(c.bert_vocab > 1001 ? c.bert_vocab - 1000 : 1));
         for (int b = 0; b < B; ++b) { ids[(size_t)b * L] = 101; ids[(size_t)b * L + L - 1] = 102; }
@@ -601,12 +672,16 @@ static int calibrate_synthetic(hcm_ctx* h) {
 int hcm_finalize(hcm_handle h) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(!h->finalized, HCM_ERR_STATE, "hcm_finalize called twice");
-    for (int m = 0; m < 3; ++m)
+    for (int m = 0; m < hcm_ctx::kModels; ++m)
         for (auto& kv : h->sd[m])
             if (!kv.second.loaded) return fail(h, HCM_ERR_KEY, std::string("Missing key in state_dict: ") + kv.first);
     try {
         if (h->kind == 1) {
             prepare_cma(h);
+            if (hipMalloc((void**)&h->len_buf, (size_t)h->cfg.max_batch * sizeof(int)) != hipSuccess) return fail(h, HCM_ERR_NOMEM, "hipMalloc failed");
+        }
+        if (h->kind == 2) {
+            prepare_s2s(h);
             if (hipMalloc((void**)&h->len_buf, (size_t)h->cfg.max_batch * sizeof(int)) != hipSuccess) return fail(h, HCM_ERR_NOMEM, "hipMalloc failed");
         }
         if (h->cfg.build_high) prepare_high(h);
@@ -688,7 +763,7 @@ int hcm_finalize(hcm_handle h) {
     }
     // host copies are no longer needed -- unless the caller wants to calibrate on its own observations (hcm_config.reserved[4])
     if (!h->cfg.reserved[4]) {
-        for (int m = 0; m < 3; ++m)
+        for (int m = 0; m < hcm_ctx::kModels; ++m)
             for (auto& kv : h->sd[m]) { std::vector<float>().swap(kv.second.f); }
         h->host_weights = false;
     }
@@ -699,7 +774,7 @@ int hcm_finalize(hcm_handle h) {
 int hcm_calibrate(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int L, void* stream) {
     int rc = check_fwd(h, B);
     if (rc) return rc;
-    const bool needs_ids = h->kind == 1 || h->cfg.build_high;
+    const bool needs_ids = h->kind == 1 || h->kind == 2 || h->cfg.build_high;
     REQUIRE(rgb && depth && (ids || !needs_ids), HCM_ERR_ARG, "null pointer");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     if (needs_ids && (rc = check_len(h, L))) return rc;
@@ -719,7 +794,7 @@ int hcm_calibrate(hcm_handle h, const void* rgb, int rgb_dtype, const float* dep
 
 int hcm_release_host_weights(hcm_handle h) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
-    for (int m = 0; m < 3; ++m)
+    for (int m = 0; m < hcm_ctx::kModels; ++m)
         for (auto& kv : h->sd[m]) { std::vector<float>().swap(kv.second.f); }
     h->host_weights = false;
     return HCM_OK;
@@ -794,6 +869,51 @@ int hcm_cma_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* d
     const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)rgb_dtype, (uint64_t)ids_dtype, (uint64_t)rgb, (uint64_t)depth, (uint64_t)ids,
                                        (uint64_t)h_in, (uint64_t)mask, (uint64_t)out, (uint64_t)stop, (uint64_t)h_out, (uint64_t)stream};
     return run_graphed(h, key, stream, [&]() { run_cma(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, h_in, mask, out, stop, h_out); });
+}
+
+// argument checks of the two Seq2SeqNet entry points that do not need a finalized handle come first, so that a caller's mistake is reported as
+// such whatever state the handle is in
+static int s2s_check_args(hcm_ctx* h, int rows, int B_instr, const float* progress) {
+    REQUIRE(h, HCM_ERR_ARG, "null handle");
+    REQUIRE(h->kind == 2, HCM_ERR_STATE, "not a Seq2SeqNet handle (hcm_s2s_create)");
+    REQUIRE(B_instr == 1 || B_instr == rows, HCM_ERR_ARG, "B_instr must be 1 (one instruction for every frame, seq2seq.py:163) or the number of frames");
+    REQUIRE(h->s2s_cfg.progress_monitor || !progress, HCM_ERR_ARG,
+            "progress must be NULL: the handle was created without PROGRESS_MONITOR.use (hcm_s2s_config.progress_monitor)");
+    return HCM_OK;
+}
+
+int hcm_s2s_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int B_instr, int L,
+                    const float* h_in, const float* mask, float* out, float* stop, float* progress, float* h_out, void* stream) {
+    int rc = s2s_check_args(h, B, B_instr, progress);
+    if (rc) return rc;
+    if ((rc = check_fwd(h, B))) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    h->stream = (hipStream_t)stream;
+    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)B_instr, (uint64_t)L, (uint64_t)rgb_dtype, (uint64_t)ids_dtype, (uint64_t)rgb, (uint64_t)depth,
+                                       (uint64_t)ids, (uint64_t)h_in, (uint64_t)mask, (uint64_t)out, (uint64_t)stop, (uint64_t)progress, (uint64_t)h_out,
+                                       (uint64_t)stream, 1u};
+    return run_graphed(h, key, stream, [&]() { run_s2s(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, B_instr, h_in, mask, out, stop, progress, h_out); });
+}
+
+int hcm_s2s_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int B_instr,
+                        int L, const float* h_in, const float* masks, float* out, float* stop, float* progress, float* h_out, void* stream) {
+    REQUIRE(h, HCM_ERR_ARG, "null handle");
+    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
+    int rc = s2s_check_args(h, T * N, B_instr, progress);
+    if (rc) return rc;
+    if ((rc = check_fwd(h, T * N))) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(rgb && depth && ids && h_in && masks && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    h->stream = (hipStream_t)stream;
+    try {
+        run_s2s(h, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, B_instr, h_in, masks, out, stop, progress, h_out, T);
+    } catch (const std::exception& e) {
+        return fail(h, HCM_ERR_HIP, e.what());
+    }
+    return HCM_OK;
 }
 
 int hcm_high_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,

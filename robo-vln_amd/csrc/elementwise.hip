@@ -1071,15 +1071,16 @@ __device__ __forceinline__ void heads_eval(const float* hs, int Hd, const Heads&
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     __shared__ float lg[64];
     __shared__ int best_s;
-    for (int r = wave; r < hd.r0 + hd.r1; r += nw) {
-        const bool first = r < hd.r0;
-        const int rr = first ? r : r - hd.r0;
-        const float* w = (first ? hd.w0 : hd.w1) + (size_t)rr * Hd;
+    for (int r = wave; r < hd.r0 + hd.r1 + hd.r2; r += nw) {
+        const bool first = r < hd.r0, third = r >= hd.r0 + hd.r1;
+        const int rr = first ? r : third ? r - hd.r0 - hd.r1 : r - hd.r0;
+        const float* w = (first ? hd.w0 : third ? hd.w2 : hd.w1) + (size_t)rr * Hd;
         float acc = 0.f;
         for (int j = lane; j < Hd; j += 64) acc += w[j] * hs[j];
         acc = wave_sum(acc);
         if (lane == 0) {
             if (first) { const float v = acc + hd.b0[rr]; hd.out0[(size_t)b * hd.ld0 + rr] = v; if (rr < 64) lg[rr] = v; }
+            else if (third) hd.out2[(size_t)b * hd.ld2 + rr] = tanhf(acc + hd.b2[rr]);      // tanh(progress_monitor(x)), seq2seq.py:177
             else hd.out1[(size_t)b * hd.ld1 + rr] = acc + hd.b1[rr];
         }
     }
@@ -1397,6 +1398,149 @@ hipError_t launch_instr_lstm_scan(const float* pre0, const float* pre1, const fl
     if (e != hipSuccess) return e;
     void* args[] = {&a, &lengths, &out, &B, &L, &H, &ld_out};
     return hipLaunchKernel(fn, dim3((B + SB - 1) / SB, dirs), dim3(1024), args, lds, s);
+}
+
+// Seq2SeqNet's instruction encoder: InstructionEncoder with final_state_only (instruction_encoder.py:86-90; both Seq2Seq paper configs) returns ONE
+// vector per sample, the hidden state at the sample's own last token.  Same layout as instr_lstm_scan_kernel (W_hh transposed and gate-interleaved,
+// one 16-byte load per (k, unit); h double-buffered in LDS; c in registers; 256 units x 4 k-quarters), for nn.LSTM (i,f,g,o) and nn.GRU (r,z,n: the
+// fourth weight slot is zero and not accumulated; b_hn stays inside the r * (.) product as in torch), with three differences:
+//   - no per-token output: the only global store is the final h, straight into the state encoder's input row (out, ld_out);
+//   - a workgroup runs max(length) over the SB samples it owns, not L steps (the lengths are read on the device: nothing for the host to wait
+//     for, the launch is graph-capturable); a sample's state is frozen once t >= length[b];
+//   - Bi == 1 with rows > 1: one instruction for `rows` frames (seq2seq.py:163 `.expand`) -- one sample is scanned, its result written to every row.
+// pre = x_t W_ih^T + bias [Bi*L][NG*H]: LSTM bias b_ih + b_hh; GRU bias b_ih + (b_hr, b_hz, 0).  No atomics, fixed summation order: bitwise
+// reproducible (the k-quarter partials are added as ((q0 + q1) + (q2 + q3)), as in instr_lstm_scan_kernel).
+template <int SB, bool GRU>
+__global__ __launch_bounds__(1024) void instr_final_scan_kernel(const float* __restrict__ pre, const float* __restrict__ wt, const float* __restrict__ bhn,
+                                                                 const int* __restrict__ lengths, float* __restrict__ out, int Bi, int rows, int L, int H,
+                                                                 int ld_out) {
+    constexpr int NG = GRU ? 3 : 4;
+    extern __shared__ float sm[];          // h [2][SB][H], partials [3][NG][SB][H]
+    __shared__ int len_s[SB];
+    float* hs = sm;
+    float* ps = sm + 2 * SB * H;
+    const int b0 = blockIdx.x * SB;
+    const int j = threadIdx.x & 255, kq = threadIdx.x >> 8;
+    const int KQ = H / 4;
+    const float* __restrict__ wq = wt + ((size_t)kq * KQ * H + j) * 4;
+    if (threadIdx.x < SB) {
+        const int b = b0 + threadIdx.x;
+        int l = b < Bi ? lengths[b] : 0;               // samples past the batch never become active
+        len_s[threadIdx.x] = l < 0 ? 0 : l > L ? L : l;
+    }
+    for (int i = threadIdx.x; i < 2 * SB * H; i += 1024) hs[i] = 0.f;
+    __syncthreads();
+    int tmax = 0;                                      // workgroup-uniform: every thread reads the same SB words
+#pragma unroll
+    for (int s_ = 0; s_ < SB; ++s_) tmax = len_s[s_] > tmax ? len_s[s_] : tmax;
+    float c[SB];
+#pragma unroll
+    for (int s_ = 0; s_ < SB; ++s_) c[s_] = 0.f;
+    const float bn = GRU ? bhn[j] : 0.f;
+    int cur = 0;
+    for (int t = 0; t < tmax; ++t) {
+        float acc[NG][SB];
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int s_ = 0; s_ < SB; ++s_) acc[g][s_] = 0.f;
+        const float* hc = hs + cur * SB * H + kq * KQ;
+#pragma unroll 8
+        for (int k = 0; k < KQ; ++k) {
+            const float4 w4 = *reinterpret_cast<const float4*>(wq + (size_t)k * 4 * H);
+            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int s_ = 0; s_ < SB; ++s_) {
+                const float hk = hc[s_ * H + k];
+#pragma unroll
+                for (int g = 0; g < NG; ++g) acc[g][s_] += wv[g] * hk;
+            }
+        }
+        if (kq > 0) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+#pragma unroll
+                for (int s_ = 0; s_ < SB; ++s_) ps[(((kq - 1) * NG + g) * SB + s_) * H + j] = acc[g][s_];
+        }
+        __syncthreads();
+        float* hn = hs + (cur ^ 1) * SB * H;
+        if (kq == 0) {
+#pragma unroll
+            for (int s_ = 0; s_ < SB; ++s_) {
+                float hv = hs[cur * SB * H + s_ * H + j];
+                if (t < len_s[s_]) {                   // (len_s > 0 only for b0 + s_ < Bi: the read of `pre` is in bounds)
+                    const float* p = pre + ((size_t)(b0 + s_) * L + t) * NG * H + j;
+                    float rs[NG];
+#pragma unroll
+                    for (int g = 0; g < NG; ++g)
+                        rs[g] = (acc[g][s_] + ps[((0 * NG + g) * SB + s_) * H + j]) + (ps[((1 * NG + g) * SB + s_) * H + j] + ps[((2 * NG + g) * SB + s_) * H + j]);
+                    if (GRU) {
+                        const float r = sigmoidf_(p[0] + rs[0]), z = sigmoidf_(p[H] + rs[1]);
+                        const float n = tanhf(p[2 * H] + r * (rs[2] + bn));
+                        hv = (1.0f - z) * n + z * hv;
+                    } else {
+                        const float gi = sigmoidf_(p[0] + rs[0]), gf = sigmoidf_(p[H] + rs[1]), gg = tanhf(p[2 * H] + rs[2]), go = sigmoidf_(p[(NG - 1) * H] + rs[NG - 1]);
+                        c[s_] = gf * c[s_] + gi * gg;
+                        hv = go * tanhf(c[s_]);
+                    }
+                }
+                hn[s_ * H + j] = hv;
+            }
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const float* hf = hs + cur * SB * H;               // (tmax == 0: the zero state)
+    if (Bi == 1 && rows > 1) {
+        if (blockIdx.x == 0)
+            for (int r = kq; r < rows; r += 4) out[(size_t)r * ld_out + j] = hf[j];
+    } else if (kq == 0) {
+#pragma unroll
+        for (int s_ = 0; s_ < SB; ++s_)
+            if (b0 + s_ < Bi) out[(size_t)(b0 + s_) * ld_out + j] = hf[s_ * H + j];
+    }
+}
+template <int SB>
+static const void* instr_final_scan_fn(int gru) {
+    return gru ? reinterpret_cast<const void*>(instr_final_scan_kernel<SB, true>) : reinterpret_cast<const void*>(instr_final_scan_kernel<SB, false>);
+}
+hipError_t launch_instr_final_scan(const float* pre, const float* wt, const float* bhn, const int* lengths, float* out, int Bi, int rows, int L, int H,
+                                   int gru, int ld_out, hipStream_t s) {
+    if (H != 256 || Bi < 1 || rows < Bi || L < 1 || ld_out < H || (gru && !bhn)) return hipErrorInvalidValue;     // 256 hidden units x 4 k-quarters = 1024 threads
+    // samples per workgroup as for instr_lstm_scan_kernel: the fewest (from 2 up) that keep the launch within 128 workgroups, so that the scan does not
+    // take the CUs from the trunks running beside it (B = 64: 32 workgroups).  SB = 1 is not instantiated (see launch_instr_lstm_scan).
+    int SB = 2;
+    while (SB < 8 && (Bi + SB - 1) / SB > 128) SB *= 2;
+    const int NG = gru ? 3 : 4;
+    const size_t lds = (size_t)(2 * SB * H + 3 * NG * SB * H) * sizeof(float);
+    const void* fn = SB == 2 ? instr_final_scan_fn<2>(gru) : SB == 4 ? instr_final_scan_fn<4>(gru) : instr_final_scan_fn<8>(gru);
+    // (28 KB at SB = 2, 112 KB at SB = 8; the kernel also holds a few static words, so the limit asked for is what the launch needs, not the CU's 160 KB)
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    void* args[] = {&pre, &wt, &bhn, &lengths, &out, &Bi, &rows, &L, &H, &ld_out};
+    return hipLaunchKernel(fn, dim3((Bi + SB - 1) / SB), dim3(1024), args, lds, s);
+}
+
+__global__ void gather_last_kernel(const float* __restrict__ all, const int* __restrict__ lengths, float* __restrict__ out, int Bi, int L, int H, int ld_out) {
+    const int r = blockIdx.x, b = Bi == 1 ? 0 : r;
+    int l = lengths[b];
+    l = l > L ? L : l;
+    for (int j = threadIdx.x; j < H; j += blockDim.x) out[(size_t)r * ld_out + j] = l > 0 ? all[((size_t)b * L + l - 1) * H + j] : 0.f;
+}
+hipError_t launch_gather_last(const float* all, const int* lengths, float* out, int Bi, int rows, int L, int H, int ld_out, hipStream_t s) {
+    if (rows < 1 || (Bi != 1 && Bi < rows)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_last_kernel, dim3(rows), dim3(256), 0, s, all, lengths, out, Bi, L, H, ld_out);
+    return hipGetLastError();
+}
+__global__ void copy_rows_kernel(const float* __restrict__ src, int ld_src, int n_src, float* __restrict__ dst, int ld_dst, int cols) {
+    const int r = blockIdx.x;
+    const float* sp = src + (size_t)(n_src == 1 ? 0 : r) * ld_src;
+    for (int j = threadIdx.x; j < cols; j += blockDim.x) dst[(size_t)r * ld_dst + j] = sp[j];
+}
+hipError_t launch_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s) {
+    if (rows < 1 || (n_src != 1 && n_src < rows)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(copy_rows_kernel, dim3(rows), dim3(256), 0, s, src, ld_src, n_src, dst, ld_dst, cols);
+    return hipGetLastError();
 }
 
 // CMANet._attn (models/cma.py:201-209): ONE query per sample over S positions:

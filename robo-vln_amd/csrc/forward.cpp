@@ -885,6 +885,7 @@ struct Fwd {
             Heads hd = heads;
             if (hd.out0) hd.out0 += (size_t)t * N * hd.ld0;
             if (hd.out1) hd.out1 += (size_t)t * N * hd.ld1;
+            if (hd.out2) hd.out2 += (size_t)t * N * hd.ld2;
             // the steps run in order on one stream: every step re-uses the same gate / split-K scratch (bounded by the dry runs at
             // T = 1..3 of hcm_finalize instead of growing with T)
             const size_t m = ar.mark();
@@ -1519,6 +1520,104 @@ struct Fwd {
     }
 
 
+    // ---------------------------------------------------------------- Seq2SeqNet.forward (models/seq2seq.py:140-189)
+    // tap of `cols` columns of a strided f32 row block
+    void tap_cols(const std::string& name, const float* p, int ld, int B, int cols) {
+        if (dry || !ctx->taps_on) return;
+        float* tmp = nullptr;
+        ck(hipMalloc((void**)&tmp, (size_t)B * cols * 4), "tap scratch");
+        ck(hipMemcpy2DAsync(tmp, (size_t)cols * 4, p, (size_t)ld * 4, (size_t)cols * 4, B, hipMemcpyDeviceToDevice, s), "tap gather");
+        tap(name, tmp, false, {B, cols});
+        ck(hipStreamSynchronize(s), "tap sync");
+        (void)hipFree(tmp);
+    }
+    // Three chains as in cma_step: the instruction encoder on aux 0, the depth encoder on aux 1, the RGB encoder on the caller's stream, each writing
+    // its own columns of the state encoder's input row [instruction | depth | rgb | h*mask] (seq2seq.py:164; RnnW layout with no late columns), joined
+    // in front of the cell.  Bi = B, or 1: one instruction for all B frames (seq2seq.py:163).  T > 1: the rows are T*N frames, time-major.
+    void s2s_step(const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,
+                  const float* mask, float* out, float* stop, float* progress, float* h_out) {
+        ar.reset();
+        const hcm_config& c = ctx->cfg;
+        const hcm_s2s_config& m = ctx->s2s_cfg;
+        const S2sW& w = ctx->s2s;
+        const LowW& lw = ctx->lo;
+        const int L = ctx->cur_L, Lm = c.instr_len, Hi = m.instr_hidden, E = m.embedding_size;
+        const bool multi = ctx->concurrent && !ctx->taps_on;
+        hipStream_t main_s = ctx->stream;
+        hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s;
+        const int ldx = lw.rnn.in + c.hidden;
+        float* xh = alloc_f((size_t)B * ldx);
+        LoBufs lb;                                                // the low-level model's encoder paths write [depth | rgb] at its column 0
+        lb.xh = xh + Hi; lb.ldx = ldx;
+        if (multi) fork_join_begin(2);
+
+        // chain A (aux 0): InstructionEncoder with final_state_only (instruction_encoder.py:70-90) -- three launches whatever L is: embedding gather +
+        // lengths, the input projection of every token at once, the final-state scan writing columns [0, Hi) of every row
+        on(a0);
+        if (m.ablate_instruction) {
+            // seq2seq.py:156-157 `instruction_embedding * 0`: the encoder's value cannot reach an output (finite x * 0 = 0) -- not run
+            if (!dry) ck(hipMemset2DAsync(xh, (size_t)ldx * 4, 0, (size_t)Hi * 4, B, s), "ablate: zero instruction");
+        } else {
+            const bool gru = m.instr_rnn == HCM_GRU;
+            const int G = gru ? 3 : 4;
+            const int ldi = w.ih.Kp;
+            float* x = alloc_f((size_t)Bi * Lm * ldi);
+            float* pre = alloc_f((size_t)Bi * Lm * G * Hi);
+            if (!dry) ck(launch_instr_embed(ids, ids_dt, w.emb, x, ctx->len_buf, Bi, L, E, ldi, m.vocab_size, s), "instr embed");
+            linear(w.ih, x, Bi * L, ldi, pre, G * Hi, ACT_NONE, true);
+            // HCM_S2S_SCAN (development build; tools/bench_s2s.py): 0 = the per-token launches (what other instr_hidden sizes take), 2 = LSTM only: the
+            // all-outputs scan of CMANet's encoder over all L steps + a gather at each sample's last token -- what the library could do before this kernel
+            static const int scan_mode = dev_env("HCM_S2S_SCAN") ? atoi(dev_env("HCM_S2S_SCAN")) : 1;
+            if (Hi == 256 && scan_mode == 1) {
+                if (!dry) ck(launch_instr_final_scan(pre, w.hh_t, w.bhn, ctx->len_buf, xh, Bi, B, L, Hi, gru ? 1 : 0, ldx, s), "instr final-state scan");
+            } else if (Hi == 256 && scan_mode == 2 && !gru) {
+                float* all = alloc_f((size_t)Bi * Lm * Hi);
+                if (!dry) {
+                    ck(launch_instr_lstm_scan(pre, nullptr, w.hh_t, nullptr, ctx->len_buf, all, Bi, L, Hi, 1, Hi, s), "instr lstm scan (all outputs)");
+                    ck(launch_gather_last(all, ctx->len_buf, xh, Bi, B, L, Hi, ldx, s), "instr final-state gather");
+                }
+            } else {
+                // other INSTRUCTION_ENCODER.hidden_size values: a launch pair per token (the cells freeze h once t >= length[b]), then the final
+                // states are copied (Bi == 1: broadcast) into the rows
+                float* gh = alloc_f((size_t)Bi * G * Hi);
+                float* hc = alloc_f((size_t)2 * Bi * Hi);
+                float* seq = alloc_f((size_t)Bi * Lm * Hi);       // the cells' per-token output, unused here
+                if (!dry) ck(hipMemsetAsync(hc, 0, (size_t)2 * Bi * Hi * 4, s), "instr state reset");
+                for (int t = 0; t < L; ++t) {
+                    linear(w.hh, hc, Bi, Hi, gh, G * Hi, ACT_NONE, true);
+                    if (dry) continue;
+                    if (gru) ck(launch_instr_gru_cell(pre, gh, hc, ctx->len_buf, seq, t, Bi, L, Hi, Hi, 0, s), "instr gru cell");
+                    else ck(launch_instr_lstm_cell(pre, gh, hc, hc + (size_t)Bi * Hi, ctx->len_buf, seq, t, Bi, L, Hi, Hi, 0, s), "instr lstm cell");
+                }
+                if (!dry) ck(launch_copy_rows(hc, Hi, Bi, xh, ldx, B, Hi, s), "instr final-state rows");
+            }
+        }
+        tap_cols("s2s.instruction", xh, ldx, B, Hi);
+        // chain B (aux 1): depth encoder, flat mode (seq2seq.py:154)
+        on(a1);
+        if (m.ablate_depth) {
+            if (!dry) ck(hipMemset2DAsync(xh + Hi, (size_t)ldx * 4, 0, (size_t)c.depth_out * 4, B, s), "ablate: zero depth features");      // seq2seq.py:158-159
+        } else lo_depth(depth, B, lb);
+        tap_cols("s2s.depth_flat", xh + Hi, ldx, B, c.depth_out);
+        // chain C (caller's stream): RGB encoder, flat mode (seq2seq.py:155)
+        on(main_s);
+        if (m.ablate_rgb) {
+            if (!dry) ck(hipMemset2DAsync(xh + Hi + c.depth_out, (size_t)ldx * 4, 0, (size_t)c.rgb_out * 4, B, s), "ablate: zero rgb features");   // seq2seq.py:160-161
+        } else lo_rgb(rgb, rgb_dt, B, lb);
+        tap_cols("s2s.rgb_flat", xh + Hi + c.depth_out, ldx, B, c.rgb_out);
+        if (multi) fork_join_end(2);
+
+        // state encoder (seq2seq.py:174) with the heads in the cell launch: linear, stop_linear, tanh(progress_monitor(x)) (:177,:187-188)
+        use(ctx->dt_vla);
+        Heads hd;
+        hd.w0 = lw.lin_w; hd.b0 = lw.lin_b; hd.out0 = out; hd.r0 = c.num_actions; hd.ld0 = c.num_actions;
+        hd.w1 = lw.stop_w; hd.b1 = lw.stop_b; hd.out1 = stop; hd.r1 = 1; hd.ld1 = 1;
+        if (progress) { hd.w2 = w.pm_w; hd.b2 = w.pm_b; hd.out2 = progress; hd.r2 = 1; hd.ld2 = 1; }
+        rnn_scan(lw.rnn, xh, ldx, T, B / T, h_in, mask, h_out, hd);
+        tap_rnn_in("s2s.rnn_in", lw.rnn, xh, ldx, B);
+    }
+
+
     // ---------------------------------------------------------------- one step: independent encoder chains run on
     // separate HIP streams (fork/join by events, capturable into a hipGraph): the two RGB ResNet-50s, the two depth
     // trunks and BERT have no data dependence until the cross-modal block / the recurrent cells.  Each chain owns a
@@ -1693,5 +1792,11 @@ void run_cma(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, cons
              const float* mask, float* out, float* stop, float* h_out) {
     Fwd f(ctx);
     f.cma_step(rgb, rgb_dt, depth, ids, ids_dt, B, h_in, mask, out, stop, h_out);
+}
+void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,
+             const float* mask, float* out, float* stop, float* progress, float* h_out, int T) {
+    Fwd f(ctx);
+    f.T = T;
+    f.s2s_step(rgb, rgb_dt, depth, ids, ids_dt, B, Bi, h_in, mask, out, stop, progress, h_out);
 }
 }  // namespace hcm

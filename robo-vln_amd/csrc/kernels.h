@@ -258,6 +258,8 @@ hipError_t launch_rnn_prep(const float* h_in, const float* mask, float* xh, int 
 struct Heads {            // up to two small linear heads on the new hidden state
     const float* w0 = nullptr; const float* b0 = nullptr; float* out0 = nullptr; int r0 = 0; int ld0 = 0;
     const float* w1 = nullptr; const float* b1 = nullptr; float* out1 = nullptr; int r1 = 0; int ld1 = 0;
+    // optional third head behind a tanh: Seq2SeqNet's progress estimate tanh(progress_monitor(x)) (seq2seq.py:177)
+    const float* w2 = nullptr; const float* b2 = nullptr; float* out2 = nullptr; int r2 = 0; int ld2 = 0;
     // optional, fused act() step: pred[b] = argmax(out0 row) (first maximal index, hierarchical_trainer.py:1098) and the low-level model's
     // sub-task embedding row emb[pred] written to emb_out[b*emb_ld ..] -- saves two launches on the step's serial tail
     int64_t* pred = nullptr; const float* emb = nullptr; float* emb_out = nullptr; int emb_dim = 0, emb_ld = 0, emb_rows = 0;    // optional overflow guard: incremented once per sample whose gate pre-activations are not all finite (an fp16 overflow or a NaN
@@ -295,6 +297,16 @@ hipError_t launch_instr_gru_cell(const float* pre, const float* gh, float* h, co
 // all L steps of both directions in one launch (H == 256): wt = W_hh transposed [H][4H]
 hipError_t launch_instr_lstm_scan(const float* pre0, const float* pre1, const float* wt0, const float* wt1, const int* lengths, float* out,
                                   int B, int L, int H, int dirs, int ld_out, hipStream_t s);
+// Seq2SeqNet's instruction encoder (final_state_only, instruction_encoder.py:86-90): the packed scan that keeps ONLY h at t = length[b] - 1.
+// pre [Bi*L][G*H] = x_t W_ih^T + bias (G = 4 LSTM i,f,g,o / 3 GRU r,z,n), wt = W_hh as [H][H][4] (GRU: 4th slot 0), bhn = GRU's b_hn or null.
+// Row b of the result goes to out[b * ld_out .. + H) for b < Bi; with Bi == 1 and rows > 1 the one result is written to `rows` rows.
+// H == 256.  A workgroup runs max(length) of its own samples steps, not L.
+hipError_t launch_instr_final_scan(const float* pre, const float* wt, const float* bhn, const int* lengths, float* out, int Bi, int rows, int L, int H,
+                                   int gru, int ld_out, hipStream_t s);
+// dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
+// out[r][0..H) = all[b][max(len_b, 1) - 1][0..H) with b = (Bi == 1 ? 0 : r): the last active step of an all-outputs scan (len_b == 0: zeros)
+hipError_t launch_gather_last(const float* all, const int* lengths, float* out, int Bi, int rows, int L, int H, int ld_out, hipStream_t s);
+hipError_t launch_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s);
 hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int* lengths, float* out,
                          int ldo, int B, int S, int D, int Dv, float scale, hipStream_t s);
 // pred[b] = argmax_j logits[b*ld + j] (first max), int64

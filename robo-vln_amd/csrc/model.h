@@ -149,6 +149,16 @@ struct CmaW {
     float* lin_w = nullptr; float* lin_b = nullptr; float* stop_w = nullptr; float* stop_b = nullptr;
 };
 
+// Seq2SeqNet (models/seq2seq.py:21-189): the trunks, the state encoder and the two action heads live in LowW (the low-level model's flat-mode
+// paths); what is specific to this model is the final-state instruction encoder and the progress head
+struct S2sW {
+    float* emb = nullptr;          // word embedding table [vocab][E] f32
+    LinW ih, hh;                   // W_ih (LSTM: bias b_ih + b_hh; GRU: b_ih + the r / z parts of b_hh) and W_hh (per-token path only; GRU bias: b_hn in the n rows)
+    float* hh_t = nullptr;         // W_hh as [H (k)][H (unit)][4]: gates i,f,g,o (LSTM) or r,z,n,0 (GRU) -- one 16-byte load per (k, unit)
+    float* bhn = nullptr;          // GRU: b_hh of the n gate [H] (stays inside the r * (.) product); LSTM: null
+    float* pm_w = nullptr; float* pm_b = nullptr;      // progress_monitor (1, hidden)
+};
+
 struct Arena {
     char* base = nullptr;
     size_t cap = 0, off = 0, peak = 0;
@@ -178,11 +188,14 @@ struct hcm_ctx {
     // storage / MFMA input type per sub-network: in bf16 mode the GroupNorm depth trunk runs
     // on fp16 MFMA tiles (same rate, 3 more mantissa bits), everything else on bf16
     int dt_rgb = 0, dt_depth = 0, dt_bert = 0, dt_vla = 0;
-    std::map<std::string, hcm::HostTensor> sd[3];       // HCM_HIGH, HCM_LOW, HCM_CMA
-    int kind = 0;                   // 0: HCM hi/lo handle, 1: CMANet handle (hcm_cma_create)
+    static constexpr int kModels = 4;
+    std::map<std::string, hcm::HostTensor> sd[kModels];       // HCM_HIGH, HCM_LOW, HCM_CMA, HCM_S2S
+    int kind = 0;                   // 0: HCM hi/lo handle, 1: CMANet handle (hcm_cma_create), 2: Seq2SeqNet handle (hcm_s2s_create)
     hcm_cma_config cma_cfg;
     hcm::CmaW cma;
-    int* len_buf = nullptr;         // CMANet: per-sample instruction lengths
+    hcm_s2s_config s2s_cfg;
+    hcm::S2sW s2s;
+    int* len_buf = nullptr;         // CMANet / Seq2SeqNet: per-sample instruction lengths
     bool finalized = false;
     int device = -1;                // the HIP device the handle was created on
     // hcm_guard_poll: the overflow-guard word travels to a pinned host word behind the caller's stream; read back without a synchronisation

@@ -203,6 +203,39 @@ void build_spec_cma(hcm_ctx* ctx) {
     s.linear("stop_linear", 1, c.hidden);
 }
 
+// Seq2SeqNet state_dict (models/seq2seq.py:32-111; InstructionEncoder models/encoders/instruction_encoder.py:9-47): the low-level model's encoder
+// keys without the sub-task embedding, plus the instruction encoder, sub_goal_linear and progress_monitor
+void build_spec_s2s(hcm_ctx* ctx) {
+    const hcm_config& c = ctx->cfg;
+    const hcm_s2s_config& m = ctx->s2s_cfg;
+    SpecB s{ctx->sd[HCM_S2S]};
+    const int G = m.instr_rnn == HCM_GRU ? 3 : 4;
+    const std::string p = "instruction_encoder.encoder_rnn.";
+    s.add("instruction_encoder.embedding_layer.weight", {m.vocab_size, m.embedding_size});
+    s.add(p + "weight_ih_l0", {G * m.instr_hidden, m.embedding_size});
+    s.add(p + "weight_hh_l0", {G * m.instr_hidden, m.instr_hidden});
+    s.add(p + "bias_ih_l0", {G * m.instr_hidden});
+    s.add(p + "bias_hh_l0", {G * m.instr_hidden});
+    if (c.depth_encoder == HCM_ENC_RESNET) {
+        const int fs = depth_final_spatial(c), cc = depth_compress_channels(c);
+        spec_gn_resnet50(s, "depth_encoder.visual_encoder.", 1, c.depth_baseplanes, cc);
+        s.linear("depth_encoder.visual_fc.1", c.depth_out, cc * fs * fs);
+    } else {
+        spec_simple_cnn(s, "depth_encoder.", 1, c.depth_h, c.depth_w, c.depth_out);
+    }
+    if (c.rgb_encoder == HCM_ENC_RESNET) {
+        spec_tv_resnet50(s, "rgb_encoder.cnn.", true);
+        s.linear("rgb_encoder.fc", c.rgb_out, 2048);
+    } else {
+        spec_simple_cnn(s, "rgb_encoder.", 3, c.rgb_h, c.rgb_w, c.rgb_out);
+    }
+    spec_rnn(s, "state_encoder.rnn.", c, m.instr_hidden + c.depth_out + c.rgb_out);      // seq2seq.py:88-92
+    s.linear("progress_monitor", 1, c.hidden);
+    s.linear("linear", c.num_actions, c.hidden);
+    s.linear("sub_goal_linear", m.num_sub_tasks, c.hidden);                              // seq2seq.py:108: in the state_dict, never used by forward
+    s.linear("stop_linear", 1, c.hidden);
+}
+
 // ------------------------------------------------------------------------------------------------ upload helpers
 static uint16_t f2bf_host(float f) {
     uint32_t u;
@@ -915,10 +948,22 @@ void prepare_high(hcm_ctx* ctx) {
     h.head_b = up.f32(T_(ctx, M, "linear.bias").f);
 }
 
+static void prepare_flat_encoders(hcm_ctx* ctx, Uploader& up, int M);
 void prepare_low(hcm_ctx* ctx) {
-    const hcm_config& c = ctx->cfg;
     const int M = HCM_LOW;
     Uploader up{ctx};
+    LowW& l = ctx->lo;
+    prepare_flat_encoders(ctx, up, M);
+    l.subtask_emb = up.f32(T_(ctx, M, "sub_task_embedding.weight").f);
+    l.rnn = make_rnn(ctx, up, M, "state_encoder.rnn.", ctx->cfg.depth_out + ctx->cfg.rgb_out);   // early: depth | rgb; late: sub-task embedding
+    l.lin_w = up.f32(T_(ctx, M, "linear.weight").f);
+    l.lin_b = up.f32(T_(ctx, M, "linear.bias").f);
+    l.stop_w = up.f32(T_(ctx, M, "stop_linear.weight").f);
+    l.stop_b = up.f32(T_(ctx, M, "stop_linear.bias").f);
+}
+// the flat-mode encoders of Seq2Seq_LowLevel and Seq2SeqNet (same modules, same keys): trunk + fc, or a SimpleCNN
+static void prepare_flat_encoders(hcm_ctx* ctx, Uploader& up, int M) {
+    const hcm_config& c = ctx->cfg;
     LowW& l = ctx->lo;
     l.depth_simple = c.depth_encoder == HCM_ENC_SIMPLECNN;
     l.rgb_simple = c.rgb_encoder == HCM_ENC_SIMPLECNN;
@@ -940,12 +985,48 @@ void prepare_low(hcm_ctx* ctx) {
     } else {
         l.rgb_s = make_simple_cnn(ctx, ctx->dt_rgb, up, M, "rgb_encoder.", 3, c.rgb_h, c.rgb_w);
     }
-    l.subtask_emb = up.f32(T_(ctx, M, "sub_task_embedding.weight").f);
-    l.rnn = make_rnn(ctx, up, M, "state_encoder.rnn.", ctx->cfg.depth_out + ctx->cfg.rgb_out);   // early: depth | rgb; late: sub-task embedding
+}
+
+// Seq2SeqNet: encoders / state encoder / heads into LowW (the step reuses the low-level model's flat-mode paths), the instruction encoder into S2sW
+void prepare_s2s(hcm_ctx* ctx) {
+    const hcm_s2s_config& m = ctx->s2s_cfg;
+    const int M = HCM_S2S;
+    Uploader up{ctx};
+    LowW& l = ctx->lo;
+    S2sW& w = ctx->s2s;
+    prepare_flat_encoders(ctx, up, M);
+    l.rnn = make_rnn(ctx, up, M, "state_encoder.rnn.");                  // input row [instruction | depth | rgb | h*mask]: no late columns
     l.lin_w = up.f32(T_(ctx, M, "linear.weight").f);
     l.lin_b = up.f32(T_(ctx, M, "linear.bias").f);
     l.stop_w = up.f32(T_(ctx, M, "stop_linear.weight").f);
     l.stop_b = up.f32(T_(ctx, M, "stop_linear.bias").f);
+    w.pm_w = up.f32(T_(ctx, M, "progress_monitor.weight").f);
+    w.pm_b = up.f32(T_(ctx, M, "progress_monitor.bias").f);
+    const std::string p = "instruction_encoder.encoder_rnn.";
+    w.emb = up.f32(T_(ctx, M, "instruction_encoder.embedding_layer.weight").f);
+    const HostTensor& whh = T_(ctx, M, p + "weight_hh_l0");              // (G*H, H)
+    const HostTensor& bih = T_(ctx, M, p + "bias_ih_l0");
+    const HostTensor& bhh = T_(ctx, M, p + "bias_hh_l0");
+    const int H = m.instr_hidden, G = m.instr_rnn == HCM_GRU ? 3 : 4;
+    HostTensor b, b2;
+    b.shape = bih.shape; b.f = bih.f;
+    b2.shape = bhh.shape; b2.f.assign(bhh.f.size(), 0.f);
+    // LSTM: b_ih + b_hh go with the input projection.  GRU: n = tanh(W_in x + b_in + r * (W_hn h + b_hn)) -- the r / z parts of b_hh go with the input
+    // projection, b_hn stays with the recurrent product
+    for (int n = 0; n < G * H; ++n) {
+        if (G == 4 || n < 2 * H) b.f[n] += bhh.f[n];
+        else b2.f[n] = bhh.f[n];
+    }
+    w.ih = make_linear(up, {&T_(ctx, M, p + "weight_ih_l0")}, {&b}, DT_F32);
+    w.ih.K = w.ih.Kp;              // the embedded tokens are stored zero-padded to Kp columns (launch_instr_embed)
+    if (G == 3) w.hh = make_linear(up, {&whh}, {&b2}, DT_F32);
+    else w.hh = make_linear(up, {&whh}, {}, DT_F32);
+    w.bhn = G == 3 ? up.f32(std::vector<float>(bhh.f.begin() + 2 * H, bhh.f.end())) : nullptr;
+    std::vector<float> t((size_t)H * H * 4, 0.f);
+    // [k][unit j][gate g]: the gate weights of (input k, unit j) are one 16-byte load of the scan kernel (GRU: the fourth slot stays zero)
+    for (int n = 0; n < G * H; ++n)
+        for (int k = 0; k < H; ++k) t[((size_t)k * H + (n % H)) * 4 + n / H] = whh.f[(size_t)n * H + k];
+    w.hh_t = up.f32(t);
 }
 
 }  // namespace hcm

@@ -380,3 +380,57 @@ def make_cma_observations(cfg, batch: int, step: int = 0, seed: int = 0, rgb_uin
     for b in range(B):
         ids[b, lens[b]:] = 0
     return {"rgb": rgb, "depth": depth.astype(np.float32), "instruction": ids}
+
+
+def seq2seq_spec(cfg):
+    """Seq2SeqNet state_dict (models/seq2seq.py:32-111; InstructionEncoder instruction_encoder.py:9-47): a unidirectional instruction
+    encoder, the flat-mode encoders of the low-level model, one state encoder over [instruction | depth | rgb], and the four heads --
+    `progress_monitor` and `sub_goal_linear` exist in every configuration (seq2seq.py:104-109)."""
+    cfg.validate()
+    g = 4 if cfg.rnn_type == "LSTM" else 3
+    gi = 4 if cfg.instr_rnn == "LSTM" else 3
+    s = [("instruction_encoder.embedding_layer.weight", (cfg.vocab_size, cfg.embedding_size), "emb", 1.0)]
+    s += _rnn_generic("instruction_encoder.encoder_rnn.", gi, cfg.instr_hidden, cfg.embedding_size)
+    if cfg.depth_encoder == "VlnResnetDepthEncoder":
+        fs = cfg.depth_final_spatial()
+        cc = cfg.depth_compress_channels()
+        s += habitat_gn_resnet50_spec("depth_encoder.visual_encoder.", 1, cfg.depth_baseplanes, cc)
+        s += _linear("depth_encoder.visual_fc.1", cfg.depth_out, cc * fs * fs, gain=RELU_GAIN)
+    else:
+        s += simple_cnn_spec("depth_encoder.", 1, cfg.depth_shape, cfg.depth_out)
+    if cfg.rgb_encoder == "TorchVisionResNet50":
+        s += torchvision_resnet50_spec("rgb_encoder.cnn.", with_fc=True)
+        s += _linear("rgb_encoder.fc", cfg.rgb_out, 2048, gain=RELU_GAIN)
+    else:
+        s += simple_cnn_spec("rgb_encoder.", 3, cfg.rgb_shape, cfg.rgb_out)
+    s += _rnn_generic("state_encoder.rnn.", g, cfg.hidden, cfg.rnn_input_size)
+    s += _linear("progress_monitor", 1, cfg.hidden)
+    s += _linear("linear", cfg.num_actions, cfg.hidden)
+    s += _linear("sub_goal_linear", cfg.num_sub_tasks, cfg.hidden)
+    s += _linear("stop_linear", 1, cfg.hidden)
+    return s
+
+
+def make_s2s_weights(cfg, seed: int = 0):
+    """Seq2SeqNet state_dict as a numpy fp32 dict (row 0 of the word embedding is the padding row: zeros)."""
+    sd = materialize(seq2seq_spec(cfg), "s2s", seed)
+    sd["instruction_encoder.embedding_layer.weight"][0] = 0.0
+    return sd
+
+
+def make_s2s_observations(cfg, batch: int, step: int = 0, seed: int = 0, rgb_uint8: bool = False, n_instr=None):
+    """As make_cma_observations (ids 1..vocab-1, 0-padded, ragged: per-row length in [L/2, L]); n_instr = 1 gives ONE (1, L)
+    instruction for all `batch` frames (seq2seq.py:163)."""
+    B, L = batch, cfg.instr_len
+    n = B if n_instr is None else n_instr
+    tag = f"obs/{step}"
+    rh, rw = cfg.rgb_shape
+    rgb = np.floor(uniform01(tag + "/rgb", B * rh * rw * 3, seed) * 256.0)
+    rgb = rgb.reshape(B, rh, rw, 3).astype(np.uint8 if rgb_uint8 else np.float32)
+    dh, dw = cfg.depth_shape
+    depth = uniform01(tag + "/depth", B * dh * dw, seed).reshape(B, dh, dw, 1)
+    ids = randint("obs/s2s_instr", n * L, 1, cfg.vocab_size, seed).reshape(n, L)
+    lens = randint("obs/s2s_instr_len", n, max(2, L // 2), L + 1, seed)
+    for b in range(n):
+        ids[b, lens[b]:] = 0
+    return {"rgb": rgb, "depth": depth.astype(np.float32), "instruction": ids}

@@ -1,0 +1,84 @@
+"""Seq2SeqNet step time at the BASELINE frame size (B = 64, 256 x 256 RGB-D uint8 / f32, L = 80 with lengths drawn over 20..80, "fp16"), beside
+hcm_low_forward on the same frames in the same process, and the instruction chain on its own (an engine with both visual encoders ablated minus
+an engine with all three ablated: what is left is embed + projection + scan).  One JSON line.
+
+    python tools/bench_s2s.py [--instr-rnn GRU] [--reps 5] [--steps 40]
+    HCM_DEV_LIB=1 HCM_S2S_SCAN=2 python tools/bench_s2s.py --chain-only     # development build: the pre-existing all-outputs scan + gather (LSTM)
+    HCM_DEV_LIB=1 HCM_S2S_SCAN=0 python tools/bench_s2s.py --chain-only     # ... the per-token launch pairs
+"""
+import json, os, statistics, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np, torch
+import hcm_pkg; hcm_pkg.load()
+from robo_vln_amd.config import S2SConfig, HCMConfig
+from robo_vln_amd import synth
+from robo_vln_amd.seq2seq import S2SEngine
+from robo_vln_amd.policy import HCMEngine
+
+
+def arg(name, default):
+    return type(default)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+B, L = 64, 80
+REPS, STEPS, RNN = arg("--reps", 5), arg("--steps", 40), arg("--instr-rnn", "LSTM")
+
+
+def timed(fn):
+    """median / min / max over REPS runs of STEPS calls each, after a warm-up of STEPS calls (ms per call)."""
+    for _ in range(STEPS):
+        fn()
+    ms = []
+    for _ in range(REPS):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(STEPS):
+            fn()
+        torch.cuda.synchronize(); ms.append((time.perf_counter() - t0) / STEPS * 1e3)
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def s2s(graph, **kw):
+    cfg = S2SConfig(instr_len=L, instr_rnn=RNN, **kw).validate()
+    eng = S2SEngine(cfg, synth.make_s2s_weights(cfg, 0), max_batch=B, precision="fp16", graph=graph)
+    obs = {k: torch.from_numpy(np.asarray(v)).cuda() for k, v in synth.make_s2s_observations(cfg, B, rgb_uint8=True).items()}
+    lens = synth.randint("bench/s2s_len", B, 20, L + 1)
+    ids = synth.randint("bench/s2s_ids", B * L, 1, cfg.vocab_size).reshape(B, L)
+    for b in range(B):
+        ids[b, lens[b]:] = 0
+    obs["instruction"] = torch.from_numpy(ids).cuda()
+    st = {"h": torch.zeros(cfg.num_recurrent_layers, B, cfg.hidden, device="cuda")}
+    m = torch.ones(B, device="cuda")
+
+    def step():
+        st["h"] = eng.forward(obs, st["h"], m)[3]
+    r = timed(step)
+    r["graph_launches"] = eng.query(7)
+    eng.close()
+    return r, obs
+
+
+res = {"bench": "s2s_step", "B": B, "L": L, "lengths": "20..80", "frames": 256, "precision": "fp16", "instr_rnn": RNN,
+       "scan_mode": os.environ.get("HCM_S2S_SCAN", "1"), "dev_lib": os.environ.get("HCM_DEV_LIB", "0"), "reps": REPS, "steps": STEPS}
+for graph in (True, False):
+    tag = "graph" if graph else "eager"
+    res[f"chain_plus_cell_{tag}"], _ = s2s(graph, ablate_depth=True, ablate_rgb=True)
+    res[f"cell_only_{tag}"], _ = s2s(graph, ablate_depth=True, ablate_rgb=True, ablate_instruction=True)
+    res[f"instr_chain_{tag}_ms"] = round(res[f"chain_plus_cell_{tag}"]["median_ms"] - res[f"cell_only_{tag}"]["median_ms"], 4)
+res["instr_chain_launches"] = {"1": 3, "2": 4, "0": 2 * L + 4}[res["scan_mode"]]      # by construction: embed, projection, (scan | scan + gather | reset + L pairs + copy)
+if "--chain-only" not in sys.argv:
+    for graph in (True, False):
+        tag = "graph" if graph else "eager"
+        res[f"s2s_step_{tag}"], obs = s2s(graph)
+        res[f"s2s_env_steps_per_s_{tag}"] = round(B / res[f"s2s_step_{tag}"]["median_ms"] * 1e3, 1)
+        res[f"s2s_no_instr_{tag}"], _ = s2s(graph, ablate_instruction=True)
+    hc = HCMConfig(instr_len=L)
+    lo = HCMEngine(hc, None, synth.materialize(synth.low_level_spec(hc), "lo", 0), max_batch=B, precision="fp16")
+    st = {"h": torch.zeros(hc.num_recurrent_layers, B, hc.hidden, device="cuda")}
+    m, sub = torch.ones(B, device="cuda"), torch.zeros(B, dtype=torch.int64, device="cuda")
+
+    def lo_step():
+        st["h"] = lo.low_forward(obs, st["h"], m, sub)[2]
+    res["hcm_low_forward_eager"] = timed(lo_step)
+    res["s2s_minus_low_eager_ms"] = round(res["s2s_step_eager"]["median_ms"] - res["hcm_low_forward_eager"]["median_ms"], 4)
+    lo.close()
+print(json.dumps(res))
