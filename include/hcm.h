@@ -163,6 +163,46 @@ int hcm_low_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const floa
                         const float* h_in, const float* masks, const int64_t* subtask,
                         float* vel, float* stop, float* h_out, void* stream);
 
+/* The teacher-forced validation step, HierarchicalTrainer._update_agent_val (hierarchical_trainer.py:562-631, driven by val_epoch :747-831): both
+ * models on the same T*N frames and the three criteria + the sub-task accuracy counts, in one call.  HCM handles that hold both models only
+ * (a CMANet / Seq2SeqNet handle: HCM_ERR_STATE).  Rows, lengths, masks, hidden states and the T*N <= max_batch rule are those of
+ * hcm_high_forward_seq / hcm_low_forward_seq.
+ *   oracle_subtask    (T*N,)   int64  observations['vln_oracle_action_sensor'] (:578-580): 0 = padded row, k = sub-task k - 1
+ *   corrected_actions (T*N,2)  f32    (:615-620)
+ *   oracle_stop       (T*N,1)  f32    -1 = padded row (:623)
+ * The high-level model gives logits (T*N, num_actions) (:575-576); the low-level model is TEACHER-FORCED with sub-task oracle_subtask - 1, and
+ * num_sub_tasks (the embedding's extra row) where oracle_subtask == 0 (:597-599, :613), and gives vel (T*N,2), stop (T*N,1).  The two models have
+ * no data dependence: five encoder chains are in flight together (the high-level RGB trunk on the caller's stream; the low-level RGB trunk, BERT, and
+ * the two depth trunks one behind the other, on three side streams of the handle), then the low-level tail (sub-task embedding, masked T-step scan, heads) runs on a side
+ * stream beside the cross-modal block and the high-level scan, and one criterion launch on the caller's stream follows the join.  Each model's trunks run with the launches of its own
+ * sequence call (no shared or hi|lo-paired trunks: those agree with the single-model calls to round-off only) and no instruction stream is cached.
+ *   result (8,) f32 device out:
+ *     [0] high-level loss: CrossEntropyLoss(ignore_index=-1, reduction="mean") against oracle_subtask - 1 (:567, :581) = the mean over the rows
+ *         with oracle_subtask != 0 of logsumexp(logits[r]) - logits[r, target]  (the masked_fill_ of the padded rows, :579, cannot reach the value)
+ *     [1] low-level action loss: vel set to 0 wherever corrected_actions == 0, element by element, then MSELoss(): the mean over ALL 2*T*N
+ *         elements (:617-621)
+ *     [2] stop loss: BCEWithLogitsLoss() over the rows with oracle_stop != -1 (:623-626), as max(x,0) - x*y + log1p(exp(-|x|))
+ *     [3] correct: rows with oracle_subtask != 0 whose argmax(logits[r]) (first maximal index; a NaN counts as the maximum, as in torch.argmax)
+ *         is the target (:583-587);  [4] total (:588)
+ *     [5] rows that entered the stop loss
+ *     [6] rows whose oracle_subtask lies outside [0, num_sub_tasks]: such a row counts as padded for [0], [3], [4] and the low-level model gets
+ *         the padded sub-task for it, so the call never reads outside the embedding; a caller should treat a non-zero count as an error
+ *     [7] 0
+ *   With no valid row the call gives what torch gives: 0/0 = NaN in [0] (respectively [2]) and counts of 0.  That NaN is a result, not a fault:
+ *   it does not touch the overflow guard (HCM_STEP_NONFINITE).  NaN / inf in a valid row's model outputs propagate into the loss as in torch.
+ *   hi_h_out / lo_h_out (R,N,hidden) out (may alias the inputs)
+ *   logits / vel / stop: optional outputs (NULL = not wanted): the models' outputs BEFORE any masking, bit-identical -- as are both hidden
+ *   states -- to what hcm_high_forward_seq and hcm_low_forward_seq (given the remapped sub-task) write for the same inputs.
+ * All f32 arithmetic of the criteria is done in a fixed order by one workgroup: two calls on the same inputs give the same eight words.
+ * No host synchronisation, no allocation, nothing read back: the call may be enqueued inside a stream capture (after one eager call at the
+ * same shape, which performs the one-time kernel attribute setup).  The call itself is never replayed from a graph of the library's own. */
+int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth,
+                 const void* ids, int ids_dtype, const int32_t* lengths, int T, int N, int L,
+                 const int64_t* oracle_subtask, const float* corrected_actions, const float* oracle_stop,
+                 const float* hi_h_in, const float* lo_h_in, const float* masks,
+                 float* result, float* hi_h_out, float* lo_h_out,
+                 float* logits, float* vel, float* stop, void* stream);
+
 /* The caller-side step of the eval loop, hierarchical_trainer.py:1095-1101: high -> argmax(dim=1) -> low.
  *   record (B,7) f32 out: [4 sub-task logits, lin_vel, ang_vel, stop logit].
  * When called repeatedly with the same pointers on a non-default stream, the step (all forked encoder streams
@@ -502,6 +542,10 @@ int hcm_op_conv2d_gn_res2(const void* x, const void* w_ohwi, const float* gamma,
                           const float* beta2, void* y, int dtype, int B, int H, int W, int Cin, int Cin2, int stride2, int Cout, int groups, float eps,
                           int relu, void* stream);
 int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, int C, void* stream);
+/* The criterion launch of hcm_val_step on its own (csrc/elementwise.hip, val_loss_kernel): logits (rows, A), vel (rows, 2), stop (rows, 1), the three
+ * label tensors as hcm_val_step takes them, result (8,) as it writes them; any rows >= 1 (one workgroup, rows strided over its 256 threads). */
+int hcm_op_val_loss(const float* logits, const float* vel, const float* stop, const int64_t* oracle_subtask, const float* corrected_actions,
+                    const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,9 @@ void comm_destroy(hcm_ctx* ctx);
 void run_step(hcm_ctx* ctx, bool do_hi, bool do_lo, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt,
               int B, const float* hi_h_in, const float* lo_h_in, const float* mask, const int64_t* subtask, float* logits,
               int ld_logits, float* vel, int ld_vel, float* stop, int ld_stop, float* hi_h_out, float* lo_h_out, int T = 1);
+void run_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, const int64_t* oracle,
+                  const float* corrected, const float* oracle_stop, const float* hi_h_in, const float* lo_h_in, const float* mask, float* result,
+                  float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop);
 }  // namespace hcm
 
 using namespace hcm;
@@ -449,7 +452,14 @@ static void dry_run(hcm_ctx* h, int B) {
         for (int which = 0; which < 3; ++which) {          // both (the fused step) / high alone / low alone
             const bool dh = hi && which != 2, dl = lo && which != 1;
             if ((which == 0 && !(hi && lo)) || (which == 1 && !hi) || (which == 2 && !lo)) continue;
-            if (which == 0 && T > 1) continue;             // the fused step has no sequence form
+            if (which == 0 && T > 1) {                     // the fused step has no sequence form; hcm_val_step runs both models on T*N rows
+                run_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, T, rows / T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, nullptr);
+                continue;
+            }
+            if (which == 0)                                // ... and at T = 1 (its trunks are never shared, and it keeps its own label / output rows)
+                run_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, 1, rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, nullptr);
             run_step(h, dh, dl, nullptr, DT_F32, nullptr, nullptr, DT_I64, rows, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0,
                      nullptr, 0, nullptr, nullptr, T);
         }
@@ -952,6 +962,34 @@ int hcm_low_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const floa
     try {
         run_step(h, false, true, rgb, rgb_dtype, depth, nullptr, DT_I64, T * N, nullptr, h_in, masks, subtask, nullptr, 0, vel,
                  h->cfg.lo_actions, stop, 1, nullptr, h_out, T);
+    } catch (const std::exception& e) {
+        return fail(h, HCM_ERR_HIP, e.what());
+    }
+    return HCM_OK;
+}
+
+int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, const int32_t* lengths, int T, int N,
+                 int L, const int64_t* oracle_subtask, const float* corrected_actions, const float* oracle_stop, const float* hi_h_in,
+                 const float* lo_h_in, const float* masks, float* result, float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop,
+                 void* stream) {
+    REQUIRE(h, HCM_ERR_ARG, "null handle");
+    REQUIRE(h->kind == 0, HCM_ERR_STATE, "hcm_val_step needs an HCM handle (hcm_create): the flat baselines have no high-level / low-level pair");
+    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
+    REQUIRE(result, HCM_ERR_ARG, "null result");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
+    int rc = check_fwd(h, T * N);
+    if (rc) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_val_step needs both models in the handle");
+    REQUIRE(rgb && depth && ids && oracle_subtask && corrected_actions && oracle_stop && hi_h_in && lo_h_in && masks && hi_h_out && lo_h_out,
+            HCM_ERR_ARG, "null pointer");
+    h->cur_lens = lengths;
+    drop_instruction_cache(h);
+    h->stream = (hipStream_t)stream;
+    try {
+        run_val_step(h, rgb, rgb_dtype, depth, ids, ids_dtype, T, N, oracle_subtask, corrected_actions, oracle_stop, hi_h_in, lo_h_in, masks, result,
+                     hi_h_out, lo_h_out, logits, vel, stop);
     } catch (const std::exception& e) {
         return fail(h, HCM_ERR_HIP, e.what());
     }
@@ -1496,6 +1534,14 @@ int hcm_op_conv2d_gn_res2(const void* x, const void* w_ohwi, const float* gamma,
     }
     return op_rc(launch_groupnorm_apply2(y, raw2, gamma, beta, st1, gamma2, beta2, st2, hw / 64, dt, B, hw, Cout, groups, eps, eps, relu, (hipStream_t)stream));
 }
+int hcm_op_val_loss(const float* logits, const float* vel, const float* stop, const int64_t* oracle_subtask, const float* corrected_actions,
+                    const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, void* stream) {
+    if (!logits || !vel || !stop || !oracle_subtask || !corrected_actions || !oracle_stop || !result || rows < 1 || A < 1 || num_sub_tasks < 0)
+        return HCM_ERR_ARG;
+    return op_rc(launch_val_loss(logits, A, vel, 2, stop, 1, oracle_subtask, corrected_actions, oracle_stop, result, rows, A, num_sub_tasks, 2,
+                                 (hipStream_t)stream));
+}
+
 int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, int C, void* stream) {
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     return op_rc(launch_maxpool3x3s2(x, y, op_dt(dtype), B, H, W, C, Ho, Wo, (hipStream_t)stream));

@@ -1619,6 +1619,105 @@ hipError_t launch_embed_rows(const float* emb, const int64_t* idx, float* y, int
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ teacher-forced validation step (hcm_val_step)
+// discrete_actions = (oracle - 1).masked_fill_(oracle == 0, num_sub_tasks)  (hierarchical_trainer.py:597-599), on the device.  A label outside
+// [0, num_sub_tasks] is given the padded sub-task as well, so that the embedding lookup stays inside its table; val_loss_kernel counts such rows.
+__global__ void val_subtask_kernel(const int64_t* __restrict__ oracle, int64_t* __restrict__ subtask, int rows, int num_sub_tasks) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const int64_t o = oracle[r];
+    subtask[r] = (o >= 1 && o <= num_sub_tasks) ? o - 1 : num_sub_tasks;
+}
+hipError_t launch_val_subtask(const int64_t* oracle, int64_t* subtask, int rows, int num_sub_tasks, hipStream_t s) {
+    hipLaunchKernelGGL(val_subtask_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, oracle, subtask, rows, num_sub_tasks);
+    return hipGetLastError();
+}
+
+// The criteria of HierarchicalTrainer._update_agent_val (hierarchical_trainer.py:578-588, :617-626) over the rows of one call, f32:
+//   result[0] CrossEntropyLoss(ignore_index = -1, mean) of logits against oracle - 1 over the rows with oracle != 0
+//   result[1] MSELoss of vel.masked_fill(corrected == 0, 0) against corrected, mean over all 2 * rows elements
+//   result[2] BCEWithLogitsLoss of stop against oracle_stop over the rows with oracle_stop != -1 (max(x,0) - x*y + log1p(exp(-|x|)))
+//   result[3] rows with oracle != 0 whose argmax (first maximal index) is the target;  result[4] rows with oracle != 0
+//   result[5] rows that entered the stop loss;  result[6] rows with oracle outside [0, num_sub_tasks] (treated as padded);  result[7] 0
+// No valid row: 0 / 0 = NaN in result[0] / result[2], as torch gives.
+// ONE workgroup of kValLossThreads threads -- the launch shape is PINNED, so the order of summation is fixed: thread t adds its rows t, t + 256, ...
+// in row order, a wave adds its lanes by a xor butterfly, lane 0 of wave 0 adds the four waves' sums in wave order.  No atomics; counts are
+// integers until the final store.
+constexpr int kValLossThreads = 256;
+__global__ __launch_bounds__(kValLossThreads) void val_loss_kernel(const float* __restrict__ logits, int ld_logits, const float* __restrict__ vel, int ld_vel,
+                                                                   const float* __restrict__ stop, int ld_stop, const int64_t* __restrict__ oracle,
+                                                                   const float* __restrict__ corrected, const float* __restrict__ oracle_stop,
+                                                                   float* __restrict__ result, int rows, int A, int num_sub_tasks, int n_vel) {
+    float ce = 0.f, mse = 0.f, bce = 0.f;
+    int correct = 0, total = 0, n_stop = 0, n_bad = 0;
+    for (int r = threadIdx.x; r < rows; r += kValLossThreads) {
+        const int64_t o = oracle[r];
+        if (o < 0 || o > num_sub_tasks) ++n_bad;
+        else if (o != 0) {
+            const float* p = logits + (size_t)r * ld_logits;
+            const int target = (int)o - 1;
+            int best = 0;
+            float mx = p[0];
+            for (int j = 1; j < A; ++j)                         // torch.argmax: a NaN counts as the maximum, the first one wins
+                if (p[j] > mx || (p[j] != p[j] && mx == mx)) { mx = p[j]; best = j; }
+            // log-sum-exp around the row maximum; a NaN or an infinite maximum turns into NaN through the subtraction, as in torch's log_softmax
+            float se = 0.f;
+            for (int j = 0; j < A; ++j) se += expf(p[j] - mx);
+            // a target outside the A logits cannot be picked (num_sub_tasks > A is a configuration the models do not have): NaN, never a wild read
+            ce += target < A ? (mx + logf(se)) - p[target] : __builtin_nanf("");
+            correct += best == target ? 1 : 0;
+            ++total;
+        }
+        for (int j = 0; j < n_vel; ++j) {
+            const float c = corrected[(size_t)r * n_vel + j];
+            const float v = c == 0.f ? 0.f : vel[(size_t)r * ld_vel + j];
+            const float d = v - c;
+            mse += d * d;
+        }
+        const float y = oracle_stop[r];
+        if (y != -1.f) {
+            const float x = stop[(size_t)r * ld_stop];
+            bce += (fmaxf(x, 0.f) - x * y) + log1pf(expf(-fabsf(x)));
+            ++n_stop;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        ce += __shfl_xor(ce, o, 64); mse += __shfl_xor(mse, o, 64); bce += __shfl_xor(bce, o, 64);
+        correct += __shfl_xor(correct, o, 64); total += __shfl_xor(total, o, 64); n_stop += __shfl_xor(n_stop, o, 64); n_bad += __shfl_xor(n_bad, o, 64);
+    }
+    constexpr int NW = kValLossThreads / 64;
+    __shared__ float fs[NW][3];
+    __shared__ int is[NW][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        fs[wave][0] = ce; fs[wave][1] = mse; fs[wave][2] = bce;
+        is[wave][0] = correct; is[wave][1] = total; is[wave][2] = n_stop; is[wave][3] = n_bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float f[3] = {0.f, 0.f, 0.f};
+        int n[4] = {0, 0, 0, 0};
+        for (int w = 0; w < NW; ++w) {
+            for (int k = 0; k < 3; ++k) f[k] += fs[w][k];
+            for (int k = 0; k < 4; ++k) n[k] += is[w][k];
+        }
+        result[0] = f[0] / (float)n[1];
+        result[1] = f[1] / (float)(rows * n_vel);
+        result[2] = f[2] / (float)n[2];
+        result[3] = (float)n[0];
+        result[4] = (float)n[1];
+        result[5] = (float)n[2];
+        result[6] = (float)n[3];
+        result[7] = 0.f;
+    }
+}
+hipError_t launch_val_loss(const float* logits, int ld_logits, const float* vel, int ld_vel, const float* stop, int ld_stop, const int64_t* oracle,
+                           const float* corrected, const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, int n_vel, hipStream_t s) {
+    hipLaunchKernelGGL(val_loss_kernel, dim3(1), dim3(kValLossThreads), 0, s, logits, ld_logits, vel, ld_vel, stop, ld_stop, oracle, corrected,
+                       oracle_stop, result, rows, A, num_sub_tasks, n_vel);
+    return hipGetLastError();
+}
+
 template <typename T>
 __global__ void to_f32_kernel(const T* __restrict__ x, float* __restrict__ y, size_t n) {
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) y[e] = Tr<T>::ld(x + e);

@@ -930,6 +930,15 @@ struct Fwd {
     const float* lo_h_in_early = nullptr;
     float* lo_pre = nullptr;
     bool pred_fused = false;          // argmax + sub-task embedding done by the high-level cell kernel (hi_tail)
+    // hcm_val_step (teacher-forced validation, hierarchical_trainer.py:575-631): both models on the same T*N frames, the low-level one fed the
+    // oracle's sub-task instead of the high-level argmax, then the criteria.  val.on with null labels = the sizing pass of hcm_finalize.
+    struct Val {
+        bool on = false;
+        const int64_t* oracle = nullptr;
+        const float* corrected = nullptr;
+        const float* oracle_stop = nullptr;
+        float* result = nullptr;
+    } val;
 
 
     HiBufs hi_alloc(int B) {
@@ -1682,13 +1691,31 @@ struct Fwd {
         if (do_lo) lb = lo_alloc(B);
         const bool multi = ctx->concurrent && !ctx->taps_on;    // taps allocate/synchronise: keep them single-stream
         hipStream_t main_s = ctx->stream;
+        int64_t* val_subtask = nullptr;
+        if (val.on) {
+            // outputs the caller did not ask for still feed the criteria: workspace rows
+            const hcm_config& c = ctx->cfg;
+            if (!logits) { logits = alloc_f((size_t)B * c.num_actions); ld_logits = c.num_actions; }
+            if (!vel) { vel = alloc_f((size_t)B * c.lo_actions); ld_vel = c.lo_actions; }
+            if (!stop) { stop = alloc_f((size_t)B); ld_stop = 1; }
+            val_subtask = (int64_t*)ar.alloc((size_t)B * sizeof(int64_t));
+            // discrete_actions (:597-599), on the device, in front of the fork: the low-level tail reads it behind the join
+            on(main_s);
+            if (!dry) ck(launch_val_subtask(val.oracle, val_subtask, B, c.num_sub_tasks, s), "val subtask");
+        }
         hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s, a2 = multi ? ctx->aux[2] : main_s;
+        // hcm_val_step: five chains in flight on four streams -- the high-level RGB trunk on the caller's stream, the low-level one on aux 0, BERT on
+        // aux 2, and on aux 1 the two depth trunks one behind the other: together they end long before the RGB trunks and BERT do.  (A fifth
+        // stream was tried for the low-level depth trunk: with the runtime's default of four hardware queues it shared BERT's queue, started only
+        // when BERT had ended and sat on the critical path -- profiles/val_step.md.)
+        hipStream_t a3 = a1;
+        const int n_fork = val.on ? 3 : 4;
 #ifdef HCM_DEV_KNOBS
         static const int skip = dev_env("HCM_SKIP") ? atoi(dev_env("HCM_SKIP")) : 0;   // profiling aid (make DEV=1 builds only): drop chains (bitmask)
 #else
         constexpr int skip = 0;
 #endif
-        if (multi) fork_join_begin(4);
+        if (multi) fork_join_begin(n_fork);
         if (ctx->host_frames && !dry) {
             // HCM_ACT_HOST_FRAMES: each chain's frames come up from the pinned host buffers on that chain's own stream, so BERT and the other
             // chain's compute run beside the copies.  The RGB frames go FIRST: the copy engine works in submission order and the RGB trunks are
@@ -1724,8 +1751,10 @@ struct Fwd {
         on(a1);
         chain_begin();
         mark("depth.start");
-        const bool dshare = do_hi && do_lo && ctx->hi.depth_shared && !ctx->lo.depth_simple;
-        const bool pair = do_hi && do_lo && ctx->hi.has_depth_pair && !ctx->lo.depth_simple;
+        const bool dshare = do_hi && do_lo && !val.on && ctx->hi.depth_shared && !ctx->lo.depth_simple;
+        // (hcm_val_step promises the bits of the single-model sequence calls: it runs each model's trunks with those calls' own launches, side by
+        //  side on the chains' streams, not as shared trunks or hi|lo pairs, whose grouped launches agree with them to round-off only)
+        const bool pair = do_hi && do_lo && !val.on && ctx->hi.has_depth_pair && !ctx->lo.depth_simple;
         if (ctx->cfg.ablate_depth) {
             if (!(skip & 4)) ablated_encoder(1, B, do_hi ? &hb : nullptr, do_lo ? &lb : nullptr);
         } else if (dshare) {
@@ -1733,39 +1762,72 @@ struct Fwd {
         } else if (pair) {
             if (!(skip & 4)) depth_pair(depth, B, hb, lb);
         } else if (do_hi && !(skip & 4)) hi_depth(depth, B, hb);
-        on(a1);
+        on(a3);
+        if (val.on) mark("lodepth.start");
         if (do_lo && !pair && !dshare && !ctx->cfg.ablate_depth && !(skip & 4)) lo_depth(depth, B, lb);
+        if (val.on) mark("lodepth.end");
+        on(a1);
         mark("depth.end");
         chain_end();
         // chain 0 (caller's stream): the high-level RGB trunk (or the low-level one when it is the only model)
         on(main_s);
         chain_begin();
         mark("rgb.start");
-        const bool rshare = do_hi && do_lo && ctx->hi.rgb_shared && !ctx->lo.rgb_simple;
-        const bool rpair = do_hi && do_lo && ctx->hi.has_rgb_pair && !ctx->lo.rgb_simple;
+        const bool rshare = do_hi && do_lo && !val.on && ctx->hi.rgb_shared && !ctx->lo.rgb_simple;
+        const bool rpair = do_hi && do_lo && !val.on && ctx->hi.has_rgb_pair && !ctx->lo.rgb_simple;
         if (ctx->cfg.ablate_rgb) { if (!(skip & 1)) ablated_encoder(0, B, do_hi ? &hb : nullptr, do_lo ? &lb : nullptr); }
         else if (rshare) { if (!(skip & 1)) rgb_shared(rgb, rgb_dt, B, hb, lb); }
         else if (rpair) { if (!(skip & 1)) rgb_pair(rgb, rgb_dt, B, hb, lb); }
         else if (!(skip & 1)) { if (do_hi) hi_rgb(rgb, rgb_dt, B, hb); else lo_rgb(rgb, rgb_dt, B, lb); }
         // chain 1: the low-level RGB trunk
         static const int rgb_serial = dev_env("HCM_RGB_SERIAL") ? atoi(dev_env("HCM_RGB_SERIAL")) : 1;
-        on((rgb_serial || ctx->host_frames) ? main_s : a0);        // (staged frames: behind their copy)
+        if (val.on) { mark("rgb.hi_end"); on(a0); mark("lorgb.start"); }
+        else on((rgb_serial || ctx->host_frames) ? main_s : a0);        // (staged frames: behind their copy)
         if (do_hi && do_lo && !rpair && !rshare && !ctx->cfg.ablate_rgb && !(skip & 2)) lo_rgb(rgb, rgb_dt, B, lb);
+        if (val.on) mark("lorgb.end");
         on(main_s);
         mark("rgb.end");
         chain_end();
-        if (multi) fork_join_end(4);
+        if (multi) fork_join_end(n_fork);
         chain_begin();
         mark("tail.start");
-        if (do_hi && do_lo && T == 1) { lo_early = &lb; lo_h_in_early = lo_h_in; }
+        if (do_hi && do_lo && T == 1 && !val.on) { lo_early = &lb; lo_h_in_early = lo_h_in; }
+        const bool val_fork = val.on && multi && !dry && !ctx->seg_mode;
+        if (val.on) {
+            // The low-level tail (sub-task embedding + masked scan + heads) has no input from the high-level model here: it goes to aux 2, beside the
+            // cross-modal block and the high-level scan.  Both scans release their per-step scratch as they go, so the low-level tail is enqueued first
+            // and the arena is then advanced past everything it touched: the two tails never share workspace.
+            if (val_fork) {
+                ck(hipEventRecord(ctx->ev_fork, main_s), "val tail fork record");
+                ck(hipStreamWaitEvent(a2, ctx->ev_fork, 0), "val tail fork wait");
+            }
+            on(multi ? a2 : main_s);
+            mark("lotail.start");
+            const size_t peak0 = ar.peak;
+            ar.peak = ar.mark();
+            lo_tail(B, lb, lo_h_in, mask, val_subtask, vel, ld_vel, stop, ld_stop, lo_h_out);
+            const size_t top = ar.peak;
+            if (top > ar.mark()) (void)ar.alloc(top - ar.mark());
+            if (peak0 > ar.peak) ar.peak = peak0;
+            mark("lotail.end");
+            on(main_s);
+        }
         if (do_hi) hi_tail(B, hb, hi_h_in, mask, logits, ld_logits, hi_h_out);
-        const int64_t* st_ids = subtask;
-        if (do_hi && do_lo) {
+        if (val.on) mark("tail.hi_end");
+        if (val_fork) {
+            ck(hipEventRecord(ctx->ev_join[2], a2), "val tail join record");
+            ck(hipStreamWaitEvent(main_s, ctx->ev_join[2], 0), "val tail join wait");
+        }
+        const int64_t* st_ids = val.on ? val_subtask : subtask;
+        if (do_hi && do_lo && !val.on) {
             // pred = argmax(output, dim=1)  (hierarchical_trainer.py:1098)
             if (!dry && !pred_fused) ck(launch_argmax(logits, ctx->pred_buf, B, ctx->cfg.num_actions, ld_logits, s), "argmax");
             st_ids = ctx->pred_buf;
         }
-        if (do_lo) lo_tail(B, lb, lo_h_in, mask, st_ids, vel, ld_vel, stop, ld_stop, lo_h_out);
+        if (do_lo && !val.on) lo_tail(B, lb, lo_h_in, mask, st_ids, vel, ld_vel, stop, ld_stop, lo_h_out);
+        if (val.on && !dry)
+            ck(launch_val_loss(logits, ld_logits, vel, ld_vel, stop, ld_stop, val.oracle, val.corrected, val.oracle_stop, val.result, B,
+                               ctx->cfg.num_actions, ctx->cfg.num_sub_tasks, ctx->cfg.lo_actions, s), "val loss");
         mark("tail.end");
         chain_end();
     }
@@ -1779,6 +1841,18 @@ void run_step(hcm_ctx* ctx, bool do_hi, bool do_lo, const void* rgb, int rgb_dt,
     f.T = T;
     f.step(do_hi, do_lo, rgb, rgb_dt, depth, ids, ids_dt, B, hi_h_in, lo_h_in, mask, subtask, logits, ld_logits, vel, ld_vel,
            stop, ld_stop, hi_h_out, lo_h_out);
+}
+
+// hcm_val_step; null label pointers = the sizing pass
+void run_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, const int64_t* oracle,
+                  const float* corrected, const float* oracle_stop, const float* hi_h_in, const float* lo_h_in, const float* mask, float* result,
+                  float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop) {
+    Fwd f(ctx);
+    f.T = T;
+    f.val.on = true;
+    f.val.oracle = oracle; f.val.corrected = corrected; f.val.oracle_stop = oracle_stop; f.val.result = result;
+    f.step(true, true, rgb, rgb_dt, depth, ids, ids_dt, T * N, hi_h_in, lo_h_in, mask, nullptr, logits, ctx->cfg.num_actions, vel,
+           ctx->cfg.lo_actions, stop, 1, hi_h_out, lo_h_out);
 }
 
 }  // namespace hcm

@@ -313,6 +313,13 @@ hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const
 hipError_t launch_argmax(const float* logits, int64_t* pred, int B, int n, int ld, hipStream_t s);
 // xh[b][col0 + j] = emb[subtask[b]][j]
 hipError_t launch_embed_rows(const float* emb, const int64_t* idx, float* y, int B, int D, int ld, int col0, int nrows, hipStream_t s);
+// hcm_val_step: subtask[r] = oracle[r] - 1, and num_sub_tasks where oracle[r] is 0 (padded row) or outside [0, num_sub_tasks]
+hipError_t launch_val_subtask(const int64_t* oracle, int64_t* subtask, int rows, int num_sub_tasks, hipStream_t s);
+// hcm_val_step: the validation criteria over `rows` rows in one launch of one workgroup (fixed summation order, no atomics); result = 8 floats
+// (include/hcm.h).  logits [rows][A] (ld_logits), vel [rows][n_vel] (ld_vel), stop [rows] (ld_stop); oracle (rows,) int64, corrected (rows, n_vel),
+// oracle_stop (rows,)
+hipError_t launch_val_loss(const float* logits, int ld_logits, const float* vel, int ld_vel, const float* stop, int ld_stop, const int64_t* oracle,
+                           const float* corrected, const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, int n_vel, hipStream_t s);
 // fp16 range calibration: slot[0] = max(slot[0], bits of max |x|), slot[1] += number of non-finite elements; x is [rows][ld], cols used
 hipError_t launch_absmax(const void* x, int dt, int rows, int cols, int ld, unsigned* slot, hipStream_t s);
 // generic converts

@@ -460,6 +460,63 @@ class HCMEngine:
                                                      h_out.data_ptr(), self._stream()), self._h)
         return vel, stop, h_out
 
+    def val_step(self, observations, corrected_actions, oracle_stop, hi_hidden, lo_hidden, masks, result=None, return_outputs=False):
+        """The teacher-forced validation step, HierarchicalTrainer._update_agent_val (hierarchical_trainer.py:562-631), in one library
+        call (hcm_val_step): both models on the T*N frames of `observations` -- the low-level one fed the oracle's sub-task
+        observations["vln_oracle_action_sensor"] (0 = padded row, k = sub-task k - 1; any integer or float dtype, (T*N,) or (T*N,1) as the
+        trainer carries it, :580) -- and the criteria.  Returns (result, hi_hidden', lo_hidden'), plus (logits, vel, stop) BEFORE any masking
+        with return_outputs=True.  result is the (8,) f32 device tensor of include/hcm.h: [high-level loss, action loss, stop loss, correct,
+        total, stop rows, out-of-range labels, 0]; it is written into `result` when given, so that a caller can keep a table of them and
+        read once (check_val_result).  Does not synchronise."""
+        with torch.cuda.device(self.device):
+            rgb, depth, ids, lens, TN = self._obs(observations, True)
+            hh = self._hidden(hi_hidden)
+            N = hh.shape[1]
+            lh = self._hidden(lo_hidden, N)
+            if TN % N:
+                raise ValueError(f"{TN} frames is not a multiple of the hidden batch {N}")
+            m = self._mask(masks, TN)
+            oracle = observations["vln_oracle_action_sensor"]
+            if not isinstance(oracle, torch.Tensor):
+                oracle = torch.as_tensor(np.asarray(oracle))
+            if oracle.numel() != TN:
+                raise ValueError(f"vln_oracle_action_sensor must hold {TN} entries, got {tuple(oracle.shape)}")
+            oracle = oracle.to(self.device, non_blocking=True).reshape(TN).to(torch.int64).contiguous()      # .squeeze(1).to(dtype=torch.int64), :580
+            ca = self._dev(corrected_actions, (torch.float32,))
+            os_ = self._dev(oracle_stop, (torch.float32,))
+            if tuple(ca.shape) != (TN, self.cfg.lo_actions) or os_.numel() != TN:
+                raise ValueError(f"corrected_actions must be ({TN},{self.cfg.lo_actions}) and oracle_stop ({TN},1), got {tuple(ca.shape)} and {tuple(os_.shape)}")
+            if result is None:
+                result = torch.empty(8, device=self.device, dtype=torch.float32)
+            elif (not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.numel() != 8 or not result.is_contiguous()
+                  or result.device.type != self.device.type or (self.device.index is not None and result.device.index != self.device.index)):
+                raise ValueError("result must be a contiguous (8,) float32 tensor on the engine's device")
+            hh2, lh2 = torch.empty_like(hh), torch.empty_like(lh)
+            logits = vel = stop = None
+            if return_outputs:
+                logits = torch.empty(TN, self.cfg.num_actions, device=self.device, dtype=torch.float32)
+                vel = torch.empty(TN, self.cfg.lo_actions, device=self.device, dtype=torch.float32)
+                stop = torch.empty(TN, 1, device=self.device, dtype=torch.float32)
+            _lib.check(self._lib.hcm_val_step(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(), _TORCH_DT[ids.dtype],
+                                              _ptr(lens), TN // N, N, ids.shape[1], oracle.data_ptr(), ca.data_ptr(), os_.data_ptr(),
+                                              hh.data_ptr(), lh.data_ptr(), m.data_ptr(), result.data_ptr(), hh2.data_ptr(), lh2.data_ptr(),
+                                              _ptr(logits), _ptr(vel), _ptr(stop), self._stream()), self._h)
+        if return_outputs:
+            return result, hh2, lh2, (logits, vel, stop)
+        return result, hh2, lh2
+
+    @staticmethod
+    def check_val_result(result):
+        """Host-side check of one or more val_step results ((8,) or (n,8), any device; synchronises if on the GPU): raises ValueError when a call
+        saw vln_oracle_action_sensor values outside [0, num_sub_tasks] (result[6]).  Returns the results as a CPU tensor."""
+        r = torch.as_tensor(result).detach().to("cpu", torch.float32).reshape(-1, 8)
+        bad = r[:, 6]
+        if bool((bad != 0).any()):
+            where = [int(i) for i in torch.nonzero(bad).reshape(-1)]
+            raise ValueError(f"vln_oracle_action_sensor holds {int(bad.sum())} value(s) outside [0, num_sub_tasks] (val_step call(s) {where}): "
+                             "such rows were treated as padded")
+        return r
+
     def act(self, observations, hi_hidden, lo_hidden, masks, out=None, reuse_instruction=False, host_frames=False, gather=False):
         """reuse_instruction=True: the caller asserts that every environment's instruction is the one of the previous act() call
         (no episode ended): BERT and the instruction stream of the cross-modal block are not recomputed (hcm_act_ex).  Off in
