@@ -434,7 +434,7 @@ int hcm_op_conv2d_gn(const void* x, const void* w_ohwi, const float* gamma, cons
 int hcm_op_bottleneck_tail(const void* x, const void* w2, const float* b2, const void* w3, const float* b3, const void* identity,
                            void* y, int dtype, int B, int H, int W, int C1, int stride, void* stream);
 /* hcm_op_bottleneck_tail plus the NEXT block's 1x1 reduction from the output tile, still one launch:
- *   o1 = relu(conv1x1(y, w1) + b1),  w1 [CN][4*C1], CN = 64 or 128 (128 only when C1 = 128 ... or C1 = 64), o1 (B,Ho,Wo,CN).
+ *   o1 = relu(conv1x1(y, w1) + b1),  w1 [CN][4*C1], CN = 64 or 128 with C1 = 64, 128 or 256 with C1 = 128, 256 with C1 = 256; o1 (B,Ho,Wo,CN).
  * Bit-identical to hcm_op_conv2d applied three times. */
 int hcm_op_bottleneck_tail_next(const void* x, const void* w2, const float* b2, const void* w3, const float* b3, const void* identity,
                                 void* y, const void* w1, const float* b1, void* o1, int dtype, int B, int H, int W, int C1, int stride,
@@ -445,6 +445,14 @@ int hcm_op_bottleneck_tail_next(const void* x, const void* w2, const float* b2, 
 int hcm_op_bottleneck_tail_ds(const void* x, const void* w2, const float* b2, const void* w3ds, const float* b3ds, const void* xd,
                               void* y, const void* w1, const float* b1, void* o1, int dtype, int B, int H, int W, int stride,
                               void* stream);
+/* The general form of the three operators above, with the hi|lo PAIR layout of the step: `groups` independent bottlenecks whose channels lie
+ * side by side in every pixel -- x (B,H,W,groups*C1), identity and y (B,Ho,Wo,groups*4*C1), o1 (B,Ho,Wo,groups*CN), xd (B,H,W,groups*64*KD);
+ * weights and biases [groups][...] as for one bottleneck.  Either `identity` (KD = 0, xd = NULL) or the folded down-sample operand xd with
+ * w3 = [W3 | Wds] ([4*C1][C1 + 64*KD]) and b3 = b3 + bds.  (C1, CN, KD) as built: (64, 64|128, 0), (128, 128|256, 0), (256, 256, 0), (64, 64, 1), (128, 128, 4);
+ * anything else is HCM_ERR_ARG.  The KD = 0 forms are bit-identical to hcm_op_conv2d applied three times per group. */
+int hcm_op_bottleneck_stage(const void* x, const void* w2, const float* b2, const void* w3, const float* b3, const void* identity,
+                            const void* xd, void* y, const void* w1, const float* b1, void* o1, int dtype, int B, int H, int W, int C1,
+                            int stride, int CN, int KD, int groups, void* stream);
 /* conv2d (no bias) + GroupNorm(groups) (+ residual) (+ ReLU) for LARGE maps (Ho*Wo a multiple of 64 and >= 256, 16-bit dtypes): the
  * conv's epilogue emits the GroupNorm partial sums from its f32 tile image, one more launch normalises in place (the GN-ResNet
  * layers at 64x64 .. 16x16; resnet_encoders.py:37-101 / habitat resnet.py GroupNorm(ngroups)). */

@@ -1245,6 +1245,23 @@ int hcm_op_bottleneck_tail_ds(const void* x, const void* w2, const float* b2, co
     b.xd = xd; b.xdC = 64; b.KD = 1;
     return op_rc(launch_bneck23(b, op_dt(dtype), (hipStream_t)stream));
 }
+int hcm_op_bottleneck_stage(const void* x, const void* w2, const float* b2, const void* w3, const float* b3, const void* identity,
+                            const void* xd, void* y, const void* w1, const float* b1, void* o1, int dtype, int B, int H, int W, int C1,
+                            int stride, int CN, int KD, int groups, void* stream) {
+    if (!w1 || groups < 1 || KD < 0 || (xd != nullptr) != (KD > 0) || (xd && identity)) return HCM_ERR_ARG;
+    const int C3 = 4 * C1, K3 = C1 + 64 * KD;
+    Bneck23 b;
+    b.x = x; b.w2 = w2; b.b2 = b2; b.w3 = w3; b.b3 = b3; b.res = identity; b.y = y;
+    b.B = B; b.H = H; b.W = W; b.C1 = C1; b.stride = stride; b.xC = groups * C1; b.ldy = b.ldr = groups * C3;
+    b.w1 = w1; b.b1 = b1; b.o1 = o1; b.CN = CN; b.ldo = groups * CN;
+    b.xd = xd; b.xdC = xd ? groups * 64 * KD : 0; b.KD = KD;
+    if (groups > 1) {
+        b.groups = groups; b.g_x = C1; b.g_w2 = (long long)C1 * 9 * C1; b.g_b2 = C1;
+        b.g_w3 = (long long)C3 * K3; b.g_b3 = C3; b.g_y = C3;
+        b.g_w1 = (long long)CN * C3; b.g_b1 = CN; b.g_o1 = CN; b.g_xd = 64 * KD;
+    }
+    return op_rc(launch_bneck23(b, op_dt(dtype), (hipStream_t)stream));
+}
 int hcm_op_conv2d_gn(const void* x, const void* w_ohwi, const float* gamma, const float* beta, const void* residual, void* y,
                      int dtype, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int groups, float eps,
                      int relu, void* stream) {

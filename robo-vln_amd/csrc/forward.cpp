@@ -489,11 +489,13 @@ struct Fwd {
             static const bool no_next = dev_env("HCM_NO_BNECK_NEXT") != nullptr;
             static const bool no_256 = dev_env("HCM_NO_BNECK256") != nullptr;        // layer3 (256 mid channels) as a launch per conv (A/B, toggle test)
             static const bool force_256 = dev_env("HCM_FORCE_BNECK256") != nullptr;   // ... fused whatever the grid size (the toggle test's small batch)
+            static const bool no_next256 = dev_env("HCM_NO_BNECK_NEXT256") != nullptr;   // layer2's last block without layer3's first reduction (A/B, toggle test)
             const BottleneckW* nb = bi + 1 < t.blocks.size() ? &t.blocks[bi + 1] : nullptr;
             static const int next_only = dev_env("HCM_BNECK_NEXT_ONLY") ? atoi(dev_env("HCM_BNECK_NEXT_ONLY")) : 0;   // A/B aid: 64 or 128 = only blocks with that many mid channels
             const bool next = nb && !no_next && (!next_only || next_only == b.c2.Cout) && nb->c1.KH == 1 && nb->c1.KW == 1 && nb->c1.Cin == b.c3.Cout && nb->c1.Kp == nb->c1.Cin &&
                               nb->c1.bias && nb->c1.groups == b.c2.groups && nb->c1.dt == b.c2.dt &&
-                              ((nb->c1.Cout == b.c2.Cout && (nb->c1.Cout == 64 || nb->c1.Cout == 128 || nb->c1.Cout == 256)) || (b.c2.Cout == 64 && nb->c1.Cout == 128));
+                              ((nb->c1.Cout == b.c2.Cout && (nb->c1.Cout == 64 || nb->c1.Cout == 128 || nb->c1.Cout == 256)) || (b.c2.Cout == 64 && nb->c1.Cout == 128) ||
+                               (b.c2.Cout == 128 && nb->c1.Cout == 256 && !no_next256));
             // (256 mid channels -- layer3: only the "tail + next block's reduction" form exists, so the layer's last block stays a launch per conv)
             // ... and only when its 128-pixel tiles fill the chip (one 149 KB workgroup per CU: a tile's ~70 us are a latency chain that a small grid
             // cannot hide -- B = 16: 69 us fused vs 34 us as three launches; B = 64: 83 vs 111)
@@ -507,8 +509,12 @@ struct Fwd {
                 // layer1's first block: its 1x1 down-sample conv (64 -> 256, same stride) rides in the expansion GEMM as 64 more K columns
                 // ([W3 | Wds], bias b3 + bds): no down-sample launch, no identity tensor.  One rounding instead of two on that path, so
                 // not bit-identical to the separate launches (closer to the fp32 oracle)
-                const bool dsfold = b.has_ds && !no_dsfold && next && b.c3ds.w && b.c2.Cout == 64 && nb->c1.Cout == 64 && b.ds.Cin == 64 &&
-                                    b.c3ds.Kp == 128 && b.c3ds.groups == b.c2.groups && x.C == b.c2.groups * 64;
+                // ... and layer2's (256 -> 512, stride 2) as 256 more (HCM_NO_BNECK_DSFOLD128=1, development build: that one as its own launch)
+                static const bool no_dsfold128 = dev_env("HCM_NO_BNECK_DSFOLD128") != nullptr;
+                const int dsC = b.has_ds ? b.ds.Cin : 0;
+                const bool dsfold = b.has_ds && !no_dsfold && next && b.c3ds.w && nb->c1.Cout == b.c2.Cout &&
+                                    ((b.c2.Cout == 64 && dsC == 64) || (b.c2.Cout == 128 && dsC == 256 && !no_dsfold128)) &&
+                                    b.c3ds.Kp == b.c2.Cout + dsC && b.c3ds.groups == b.c2.groups && x.C == b.c2.groups * dsC;
                 if (b.has_ds && !dsfold) {
                     conv(b.ds, x, sb, b.stride, 0, nullptr, ACT_NONE, Ho2, Wo2);
                     idt = sb;
@@ -531,8 +537,8 @@ struct Fwd {
                     }
                     if (dsfold) {
                         q.w3 = b.c3ds.w; q.b3 = b.c3ds.bias; q.res = nullptr;
-                        q.xd = x.p; q.xdC = x.C; q.KD = 1;
-                        if (b.c2.groups > 1) { q.g_w3 = (long long)b.c3ds.Cout * b.c3ds.Kp; q.g_xd = 64; }
+                        q.xd = x.p; q.xdC = x.C; q.KD = dsC / 64;
+                        if (b.c2.groups > 1) { q.g_w3 = (long long)b.c3ds.Cout * b.c3ds.Kp; q.g_xd = dsC; }
                     }
                     ck(launch_bneck23(q, b.c2.dt, s), "bottleneck tail");
                     calib_check(sc, b.c2.dt, B * Ho2 * Wo2, CO(b.c3), CO(b.c3));        // the block output (the mid tensor never leaves LDS)

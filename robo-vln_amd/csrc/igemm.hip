@@ -2303,11 +2303,20 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
 // NWB - 1 tiles are requested with the halo block, so that all nine are in flight within the first four iterations.  The identity rows are
 // requested right BEHIND the last weight tile instead of first: vmcnt retires in order, so with them in front every wait of phase A also
 // waited for the tile's 64 KB of identity (an earlier halo form with a 4-deep ring and the identity in front measured no gain for exactly
-// that reason).  MFMA sequence and f32 operations unchanged: bit-identical to the NWB = 0 form.  Needs stride 1, C1 = 64, a tile of whole rows
+// that reason).  MFMA sequence and f32 operations unchanged: bit-identical to the NWB = 0 form.  Needs stride 1, C1 = 64 or 128, a tile of whole rows
 // of one image, W a multiple of 16 (launch_bneck23 checks; else NWB = 0).
 // W1B = 1: ONE buffer for the reduction's weight slice instead of two (the 128-pixel tile of the folded-down-sample block needs the 8 KB: its
 // parked tile is two K blocks deep).  The slice is then requested behind the top-of-slice barrier -- every wave has left the previous
 // reduction -- and waited for at the slice-block barrier, a whole expansion + epilogue later.
+// C1 = 128, CN = 256 (layer2's last block + layer3 block 0's 512 -> 256 reduction): the reduction's weight slice is 32 KB, so W1B = 1 at either
+// tile size -- 99 KB at BM = 128 (one workgroup per CU, as the stage's other blocks), 75 KB at BM = 64; acc3 is 8 accumulator tiles per 16 pixels.
+// K order of the reduction: the eight 64-channel slices of the block output in ascending order, two MFMA K steps each -- the order of the
+// stand-alone 1x1 launch's K loop, hence the same bits.
+// KD > 0 (a stage's first block, its 1x1 down-sample conv folded into the expansion GEMM; built: C1 = 64 / KD = 1 and C1 = 128 / KD = 4): the
+// block input's pixel (oy * stride, ox * stride) is gathered into KD more parked K blocks behind the mid tile (stage_xd: unconditional requests,
+// out-of-range sentinel for rows past M, so every wave has the same number in its queue), w3 is [W3 | Wds].  K order of the expansion accumulation,
+// fixed: the mid tile's C1 / 64 blocks ascending, then the KD down-sample blocks ascending, two MFMA K steps per block, all into the same acc2;
+// bias b3 + bds; no identity rows.  One rounding fewer than the separate launches on the identity path.
 template <typename T, int BM, int C1, int CN, int KD = 0, bool PROF = false, int NWB = 0, int W1B = 2>
 __global__ __launch_bounds__(512, (C1 >= 256 || (BM == 128 && C1 == 128)) ? 2 : 4) void bneck231r_kernel(Bneck231Dev qq) {
     // phase timing (HCM_IGEMM_PROF=1 builds, read through hcm_debug_igemm_prof): per-wave cycle totals [0] prologue up to the first barrier,
@@ -2327,7 +2336,7 @@ __global__ __launch_bounds__(512, (C1 >= 256 || (BM == 128 && C1 == 128)) ? 2 : 
     constexpr int WM2 = 4, WN2 = 2;                // phase B: BM / 4 pixels x 32 channels (of a slice) or CN / 2 channels (reduction) per wave
     constexpr int TMB = BM / WM2 / 16;
     constexpr int TN2 = SW / WN2 / 16;             // 2: one pair
-    constexpr int TN3 = CN / WN2 / 16;             // 2 or 4: one or two pairs
+    constexpr int TN3 = CN / WN2 / 16;             // 2, 4 or 8: one, two or four pairs
     constexpr int A_IT = BM / 8 / NW, B_IT = C1 / 8 / NW;
     constexpr int TILE_BYTES = (BM + C1) * 128;
     constexpr int KT1 = C1 / BK;
@@ -3401,7 +3410,7 @@ hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s) {
     if (dt != DT_BF16 && dt != DT_F16) return hipErrorInvalidValue;
     if ((b.C1 != 64 && b.C1 != 128 && b.C1 != 256) || (!b.res && !b.xd) || !b.b2 || !b.b3 || b.stride < 1) return hipErrorInvalidValue;
     if (b.C1 == 256 && (!b.w1 || b.CN != 256 || b.xd)) return hipErrorInvalidValue;        // 256 mid channels: only the tail + next-reduction form is built
-    if (b.xd && (b.C1 != 64 || b.KD != 1 || !b.w1 || b.CN != 64 || (b.xdC % 8))) return hipErrorInvalidValue;   // the one folded-down-sample shape built
+    if (b.xd && (!b.w1 || (b.xdC % 8) || !((b.C1 == 64 && b.KD == 1 && b.CN == 64) || (b.C1 == 128 && b.KD == 4 && b.CN == 128)))) return hipErrorInvalidValue;   // the two folded-down-sample shapes built
     const int C3 = 4 * b.C1;
     const int ldy = b.ldy ? b.ldy : C3, ldr = b.ldr ? b.ldr : C3, xC = b.xC ? b.xC : b.C1;
     if ((ldy % 8) || (ldr % 8) || (xC % 8)) return hipErrorInvalidValue;
@@ -3429,7 +3438,7 @@ hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s) {
     const int BM = b.C1 == 128 ? 64 : 128;
     const int KT1 = b.C1 / 64;
     if (b.w1) {
-        if (!b.b1 || !b.o1 || (b.CN != 64 && b.CN != 128 && b.CN != 256) || (b.C1 == 128 && b.CN != 128) || ((b.C1 == 256) != (b.CN == 256))) return hipErrorInvalidValue;
+        if (!b.b1 || !b.o1 || (b.CN != 64 && b.CN != 128 && b.CN != 256) || (b.C1 == 128 && b.CN == 64) || (b.C1 == 64 && b.CN == 256) || (b.C1 == 256 && b.CN != 256)) return hipErrorInvalidValue;
         const int ldo = b.ldo ? b.ldo : b.CN;
         if (ldo % 8) return hipErrorInvalidValue;
         Bneck231Dev qq;
@@ -3443,6 +3452,21 @@ hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s) {
             const size_t xdb = (((size_t)d.B * d.H * d.W - 1) * b.xdC + b.KD * 64) * 2;
             if (xdb >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
             qq.xd = (const char*)b.xd; qq.xdC = b.xdC; qq.xd_bytes = (unsigned)xdb; qq.g_xd = b.g_xd;
+            if (b.C1 == 128) {
+                // layer2 block 0 (256-channel block input, stride 2): the PARKED form -- the mid tile's two K blocks and the four gathered xd blocks (48 KB),
+                // a six-block expansion-weight slice (48 KB), the slice block, two reduction-weight buffers, biases: 138.5 KB, ONE 64-pixel workgroup per CU
+                // (phase A's classic ring lives in the same bytes before that; the halo form needs stride 1).  Register form only.
+                const size_t lp = (size_t)2 * (2 + b.KD) * 64 * 128 + (size_t)64 * 128 + (size_t)2 * b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
+                const size_t rp = 3 * (size_t)(64 + b.C1) * 128;
+                const size_t ldsp = lp > rp ? lp : rp;
+                if (ldsp > 160 * 1024) return hipErrorInvalidValue;
+                const void* fp = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 128, 4>)
+                                               : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 128, 4>);
+                hipError_t ep = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (ep != hipSuccess) return ep;
+                void* ap[] = {&qq};
+                return hipLaunchKernel(fp, dim3((d.M + 63) / 64, d.groups), dim3(512), ap, ldsp, s);
+            }
             const int BMd = 64;
             // register-epilogue form (bneck231r_kernel, the default) or the LDS-image form (HCM_BNECK_IMAGE=1: A/B and the toggle test); bit-identical
             static const bool image_d = dev_env("HCM_BNECK_IMAGE") != nullptr;
@@ -3503,6 +3527,45 @@ hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s) {
                 return hipLaunchKernel(f2, dim3(((tiles + 3) / 4) * 8, 1), dim3(512), a2, lds256, s);
             }
             return hipLaunchKernel(f2, dim3((d.M + BM - 1) / BM, d.groups), dim3(512), a2, lds256, s);
+        }
+        if (b.C1 == 128 && b.CN == 256) {
+            // the LAST block of a 128-mid-channel stage (RGB layer2) + the next stage's first reduction, 512 -> 256.  The reduction's weight slice is
+            // 32 KB, so ONE buffer for it whatever the tile (W1B = 1).  128-pixel tiles in one 99 KB workgroup per CU where the grid fills the chip, as
+            // for the stage's other blocks (round 4: a tile streams the block's weights from L2 whatever its size); else 64-pixel tiles, 75 KB, two per
+            // CU.  Register form only (HCM_BNECK_IMAGE does not apply).  HCM_BNECK128_BM64=1 (development build): the 64-pixel tiles.
+            static const bool no_halo2 = dev_env("HCM_NO_BNECK_HALO") != nullptr;
+            static const bool bm64_2 = dev_env("HCM_BNECK128_BM64") != nullptr;
+            const void* f3 = nullptr;
+            size_t lds3 = 0;
+            int BM3 = 64;
+            if (!no_halo2 && !bm64_2 && b.stride == 1 && d.W % 16 == 0 && 128 % d.W == 0 && (d.Ho * d.Wo) % 128 == 0 && (long)d.groups * (d.M / 128) >= 192) {
+                const size_t halo = (size_t)KT1 * ((((128 / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 8192;
+                size_t lds = (size_t)KT1 * 128 * 128 + (size_t)KT1 * 64 * 128 + (size_t)128 * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
+                if (halo > lds) lds = halo;
+                if (lds <= 112 * 1024) {
+                    BM3 = 128; lds3 = lds;
+                    f3 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 128, 256, 0, false, kHaloRing, 1>)
+                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 128, 256, 0, false, kHaloRing, 1>);
+                }
+            }
+            if (!f3) {
+                lds3 = (size_t)KT1 * 64 * 128 + (size_t)KT1 * 64 * 128 + (size_t)64 * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
+                const size_t halo = (size_t)KT1 * ((((64 / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 8192;
+                if (!no_halo2 && b.stride == 1 && d.W % 16 == 0 && 64 % d.W == 0 && (d.Ho * d.Wo) % 64 == 0 && halo <= 80 * 1024) {
+                    if (halo > lds3) lds3 = halo;
+                    f3 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 256, 0, false, kHaloRing, 1>)
+                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 256, 0, false, kHaloRing, 1>);
+                } else {
+                    const size_t ring3 = 3 * (size_t)(64 + b.C1) * 128;
+                    if (ring3 > lds3) lds3 = ring3;
+                    f3 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 256, 0, false, 0, 1>)
+                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 256, 0, false, 0, 1>);
+                }
+            }
+            hipError_t e3 = hipFuncSetAttribute(f3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e3 != hipSuccess) return e3;
+            void* a3[] = {&qq};
+            return hipLaunchKernel(f3, dim3((d.M + BM3 - 1) / BM3, d.groups), dim3(512), a3, lds3, s);
         }
         static const bool image = dev_env("HCM_BNECK_IMAGE") != nullptr;
         size_t lds1 = image ? (size_t)KT1 * BM * 128 + (size_t)KT1 * 64 * 128 + (64 * 132 * 4 / 2 + 1024) + (size_t)BM * 128 + (size_t)b.CN * 128

@@ -114,7 +114,7 @@ struct Bneck23 {
     int groups = 1;              // hi|lo pair: element offsets per group
     long long g_x = 0, g_w2 = 0, g_b2 = 0, g_w3 = 0, g_b3 = 0, g_y = 0;
     // optional: the NEXT block's 1x1 reduction relu(y @ w1^T + b1) from the output tile in the same launch (bneck231_kernel):
-    // w1 [CN][4*C1], CN = 64 or 128, o1 [M][ldo]
+    // w1 [CN][4*C1], o1 [M][ldo]; (C1, CN) = (64, 64 | 128), (128, 128 | 256), (256, 256) -- CN = 2 * C1 is a stage's last block feeding the next stage's first reduction
     const void* w1 = nullptr; const float* b1 = nullptr; void* o1 = nullptr;
     int CN = 0, ldo = 0;
     long long g_w1 = 0, g_b1 = 0, g_o1 = 0;

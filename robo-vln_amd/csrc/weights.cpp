@@ -441,7 +441,7 @@ static TrunkW make_tv_trunk(hcm_ctx* ctx, Uploader& up, int model, const std::st
             b.c2 = make_conv_bn(ctx, dt, up, model, p + "conv2.weight", p + "bn2");
             b.c3 = make_conv_bn(ctx, dt, up, model, p + "conv3.weight", p + "bn3");
             if (bi == 0) { b.has_ds = true; b.ds = make_conv_bn(ctx, dt, up, model, p + "downsample.0.weight", p + "downsample.1"); }
-            if (li == 0 && bi == 0 && dt != DT_F32) b.c3ds = make_c3ds(ctx, dt, up, {model}, p);
+            if (li <= 1 && bi == 0 && dt != DT_F32) b.c3ds = make_c3ds(ctx, dt, up, {model}, p);
             t.blocks.push_back(b);
         }
     t.out_c = 2048;
@@ -597,6 +597,8 @@ static void bn_fold(hcm_ctx* ctx, int model, const std::string& bn, int C, std::
 }
 // Expansion conv3 and the block's 1x1 down-sample conv (both BN-folded) K-concatenated for the fused bottleneck launch that folds the
 // down-sample into the expansion GEMM: rows [W3 * s3 | Wds * sds] of K = C1 + Cd, bias b3 + bds, one block per model (group).
+// Range fold (hcm_ctx::rgb_fold): behind the stem a fold touches biases only, inside bn_fold -- both halves come from bn_fold here, so b3 + bds
+// carries the factor exactly as c3's and ds's own biases do, and both operands (mid tile, block input) already carry it.
 static ConvW make_c3ds(hcm_ctx* ctx, int dt, Uploader& up, const std::vector<int>& models, const std::string& p) {
     ConvW c;
     c.dt = dt;
@@ -692,7 +694,7 @@ static TrunkW make_tv_trunk_pair(hcm_ctx* ctx, Uploader& up, const std::string& 
             b.c2 = make_conv_bn_pair(ctx, dt, up, p + "conv2.weight", p + "bn2");
             b.c3 = make_conv_bn_pair(ctx, dt, up, p + "conv3.weight", p + "bn3");
             if (bi == 0) { b.has_ds = true; b.ds = make_conv_bn_pair(ctx, dt, up, p + "downsample.0.weight", p + "downsample.1"); }
-            if (li == 0 && bi == 0 && dt != DT_F32) b.c3ds = make_c3ds(ctx, dt, up, {HCM_HIGH, HCM_LOW}, p);
+            if (li <= 1 && bi == 0 && dt != DT_F32) b.c3ds = make_c3ds(ctx, dt, up, {HCM_HIGH, HCM_LOW}, p);
             t.blocks.push_back(b);
         }
     t.out_c = 2048;
