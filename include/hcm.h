@@ -343,6 +343,19 @@ int hcm_cma_create(const hcm_cma_config* cfg, hcm_handle* out);
  *   the tensor it was given and returns it; here h_out may alias h_in to get the same effect. */
 int hcm_cma_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int L,
                     const float* h_in, const float* mask, float* out, float* stop, float* h_out, void* stream);
+/* Training / validation path of the flat trainer: `self.actor_critic(batch)` on a whole truncated-BPTT chunk (robo_vln_trainer.py:516-518 and
+ * :553-555) -- T*N rows at once, time-major (row t*N + n), with an (R,N,hidden) state, so that RNNStateEncoder.forward takes seq_forward
+ * (state_encoder.py:83-133) for BOTH state encoders (cma.py:262-270, :313-318).
+ *   rgb (T*N,H,W,3), depth (T*N,H,W,1), ids (T*N,L) with 0 = padding (the trainer's collate repeats an episode's padded instruction at every step);
+ *   masks (T*N,); h_in / h_out (R,N,hidden), first half state_encoder, second half second_state_encoder, h_out may alias h_in;
+ *   out (T*N,num_actions), stop (T*N,1).
+ * Order: the three encoder chains and the token-side projections on all T*N rows; the masked T-step scan of the first encoder; both attention
+ * stages and second_state_compress on all rows; the scan of the second encoder; linear / stop_linear over all rows in one launch.  A scan is one
+ * input-projection GEMM over all rows plus ONE launch per time step (csrc/state_scan.hip) for hidden = 512 and, for other sizes, the
+ * per-step launches of the single-step call.  T = 1 is hcm_cma_forward (same bits).  No synchronisation, no allocation: capturable by the caller.
+ * HCM_ERR_ARG: T < 1, N < 1, T*N > max_batch, L outside [1, instr_len], a null pointer; HCM_ERR_STATE: not a CMANet handle. */
+int hcm_cma_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int L,
+                        const float* h_in, const float* masks, float* out, float* stop, float* h_out, void* stream);
 
 /* ---- Seq2SeqNet flat baseline (paper_configs/seq2seq_robo.yaml, seq2seq_robo_pm.yaml) ----
  * `Seq2SeqNet` (models/seq2seq.py:21-189; constructed at robo_vln_trainer.py:333-339 whenever MODEL.CMA.use is false) behind the same
@@ -554,6 +567,14 @@ int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, 
  * label tensors as hcm_val_step takes them, result (8,) as it writes them; any rows >= 1 (one workgroup, rows strided over its 256 threads). */
 int hcm_op_val_loss(const float* logits, const float* vel, const float* stop, const int64_t* oracle_subtask, const float* corrected_actions,
                     const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, void* stream);
+/* The state-encoder scan of hcm_cma_forward_seq on its own (csrc/state_scan.hip): T masked steps of nn.LSTM (rnn_type HCM_LSTM, gates i,f,g,o) or
+ * nn.GRU (HCM_GRU, gates r,z,n) from the input projection of every row, one launch per step.
+ *   pre (T*N, G*hidden) = x W_ih^T + bias (LSTM: b_ih + b_hh, b_hh = NULL here; GRU: b_ih, and b_hh (3*hidden,) is added inside the step)
+ *   w_hh (G*hidden, hidden) as torch stores it (re-laid out for the kernel by this call); h_in / h_out (R,N,hidden), R = 2 (h, c) / 1, may alias
+ *   masks (T*N,): the state is multiplied by masks[t*N + n] in front of step t; seq_out (T*N,hidden) = h_t of every row.
+ * hidden must be 512 (HCM_ERR_ARG otherwise); any T, N >= 1.  Synchronises the stream (it owns temporary buffers). */
+int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,
+                      int T, int N, int hidden, int rnn_type, void* stream);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,39 @@ class CMAEngine:
                                                  stop.data_ptr(), h_out.data_ptr(), st), self._h)
         return out, stop, h_out
 
+    def forward_seq(self, observations, hidden, masks, T, N):
+        """Training / validation path (RNNStateEncoder.seq_forward for both state encoders): observations hold T*N rows, time-major (the
+        instruction repeated at every step, as the trainer's collate does; a (1, L) instruction is expanded); hidden (R,N,hidden); masks (T*N,).
+        -> (output (T*N,num_actions), stop_out (T*N,1), rnn_hidden_states (R,N,hidden))"""
+        c = self.cfg
+        with torch.cuda.device(self.device):
+            rgb = self._dev(observations["rgb"], (torch.float32, torch.uint8))
+            depth = self._dev(observations["depth"], (torch.float32,))
+            B = rgb.shape[0]
+            if B != T * N:
+                raise ValueError(f"expected {T * N} frames (T*N), got {B}")
+            if tuple(rgb.shape[1:]) != (*c.rgb_shape, 3):
+                raise ValueError(f"rgb must be (T*N,{c.rgb_shape[0]},{c.rgb_shape[1]},3), got {tuple(rgb.shape)}")
+            if tuple(depth.shape) != (B, c.depth_hw, c.depth_hw, 1):
+                raise ValueError(f"depth must be (T*N,{c.depth_hw},{c.depth_hw},1), got {tuple(depth.shape)}")
+            ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
+            if ids.dim() != 2 or ids.shape[0] not in (1, B) or not 1 <= ids.shape[1] <= c.instr_len:
+                raise ValueError(f"instruction must be (T*N or 1, L <= {c.instr_len}), got {tuple(ids.shape)}")
+            ids = ids.expand(B, ids.shape[1]).contiguous()
+            h_in = self._dev(hidden, (torch.float32,))
+            R = self.num_recurrent_layers
+            if tuple(h_in.shape) != (R, N, c.hidden):
+                raise ValueError(f"rnn_hidden_states must be ({R},{N},{c.hidden}), got {tuple(h_in.shape)}")
+            m = self._dev(masks, (torch.float32,)).reshape(B, -1)[:, 0].contiguous()
+            out = torch.empty(B, c.num_actions, device=self.device, dtype=torch.float32)
+            stop = torch.empty(B, 1, device=self.device, dtype=torch.float32)
+            h_out = torch.empty_like(h_in)
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(self._lib.hcm_cma_forward_seq(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(),
+                                                     _TORCH_DT[ids.dtype], T, N, ids.shape[1], h_in.data_ptr(), m.data_ptr(), out.data_ptr(),
+                                                     stop.data_ptr(), h_out.data_ptr(), st), self._h)
+        return out, stop, h_out
+
     def _forward_graph(self, rgb, depth, ids, h_in, m, B):
         c = self.cfg
         if self._gstream is None:
@@ -208,6 +241,14 @@ class CMANet:
     def forward(self, batch):
         observations, rnn_hidden_states, prev_actions, masks = batch
         out, stop, hidden = self.engine.forward(observations, rnn_hidden_states, masks)
+        if isinstance(observations, dict) and "instruction" in observations:
+            del observations["instruction"]
+        return out, stop, hidden
+
+    def seq_forward(self, batch, T, N):
+        """The training / validation call (robo_vln_trainer.py:516-518, :553-555): T*N frames at once with an (R,N,hidden) state."""
+        observations, rnn_hidden_states, prev_actions, masks = batch
+        out, stop, hidden = self.engine.forward_seq(observations, rnn_hidden_states, masks, T, N)
         if isinstance(observations, dict) and "instruction" in observations:
             del observations["instruction"]
         return out, stop, hidden

@@ -17,7 +17,7 @@ void build_spec_cma(hcm_ctx* ctx);
 void prepare_cma(hcm_ctx* ctx);
 void run_refresh_instruction(hcm_ctx* ctx, const void* ids, int ids_dt, int B, const int32_t* idx, int n);   // L = ctx->cur_L
 void run_cma(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, const float* h_in,
-             const float* mask, float* out, float* stop, float* h_out);
+             const float* mask, float* out, float* stop, float* h_out, int T = 1);
 void build_spec_s2s(hcm_ctx* ctx);
 void prepare_s2s(hcm_ctx* ctx);
 void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,
@@ -439,6 +439,10 @@ static void dry_run(hcm_ctx* h, int B) {
     h->cur_lens = nullptr;
     if (h->kind == 1) {
         run_cma(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B, nullptr, nullptr, nullptr, nullptr, nullptr);
+        // hcm_cma_forward_seq: the scans' buffers on top of the step's.  What they hold grows with the rows (the projections, both sequence
+        // buffers: T = B, N = 1 has all B rows whatever B's divisors) or with N (the per-step path's ping-pong state: largest at T = 2)
+        for (int T : {2, 3, B})
+            if (T >= 2 && T <= B) run_cma(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, T);
         return;
     }
     if (h->kind == 2) {                                // the step with one instruction per row, and the sequence path at T = 2, 3 (as below)
@@ -879,6 +883,27 @@ int hcm_cma_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* d
     const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)rgb_dtype, (uint64_t)ids_dtype, (uint64_t)rgb, (uint64_t)depth, (uint64_t)ids,
                                        (uint64_t)h_in, (uint64_t)mask, (uint64_t)out, (uint64_t)stop, (uint64_t)h_out, (uint64_t)stream};
     return run_graphed(h, key, stream, [&]() { run_cma(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, h_in, mask, out, stop, h_out); });
+}
+
+int hcm_cma_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int L,
+                        const float* h_in, const float* masks, float* out, float* stop, float* h_out, void* stream) {
+    REQUIRE(h, HCM_ERR_ARG, "null handle");
+    REQUIRE(h->kind == 1, HCM_ERR_STATE, "not a CMANet handle (hcm_cma_create)");
+    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
+    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
+    if (T == 1) return hcm_cma_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, N, L, h_in, masks, out, stop, h_out, stream);
+    int rc = check_fwd(h, T * N);
+    if (rc) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(rgb && depth && ids && h_in && masks && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    h->stream = (hipStream_t)stream;
+    try {
+        run_cma(h, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, h_in, masks, out, stop, h_out, T);
+    } catch (const std::exception& e) {
+        return fail(h, HCM_ERR_HIP, e.what());
+    }
+    return HCM_OK;
 }
 
 // argument checks of the two Seq2SeqNet entry points that do not need a finalized handle come first, so that a caller's mistake is reported as
@@ -1557,6 +1582,25 @@ int hcm_op_val_loss(const float* logits, const float* vel, const float* stop, co
         return HCM_ERR_ARG;
     return op_rc(launch_val_loss(logits, A, vel, 2, stop, 1, oracle_subtask, corrected_actions, oracle_stop, result, rows, A, num_sub_tasks, 2,
                                  (hipStream_t)stream));
+}
+
+int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,
+                      int T, int N, int hidden, int rnn_type, void* stream) {
+    if (!pre || !w_hh || !h_in || !masks || !seq_out || !h_out || T < 1 || N < 1 || !state_scan_ok(hidden)) return HCM_ERR_ARG;
+    if (rnn_type != HCM_LSTM && rnn_type != HCM_GRU) return HCM_ERR_ARG;
+    const int G = rnn_type == HCM_LSTM ? 4 : 3;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t wn = (size_t)hidden * hidden * 4;
+    std::vector<float> w((size_t)G * hidden * hidden), packed(wn);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(w.data(), w_hh, w.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return HCM_ERR_HIP;
+    state_scan_pack(w.data(), packed.data(), hidden, G);
+    float* ws = nullptr;
+    if (hipMalloc((void**)&ws, wn * 4) != hipSuccess) return HCM_ERR_NOMEM;
+    hipError_t e = hipMemcpy(ws, packed.data(), wn * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_state_scan(pre, ws, b_hh, h_in, masks, seq_out, h_out, nullptr, nullptr, T, N, hidden, rnn_type == HCM_GRU ? 1 : 0, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    return op_rc(e != hipSuccess ? e : e2);
 }
 
 int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, int C, void* stream) {

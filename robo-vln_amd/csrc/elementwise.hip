@@ -1155,6 +1155,20 @@ hipError_t launch_gru_cell(const float* gi, const float* gh, const float* h_in, 
     return hipGetLastError();
 }
 
+// linear / stop_linear over a whole (rows, Hd) sequence buffer: the sequence calls' heads behind a scan that keeps h_t of every row
+__global__ void heads_rows_kernel(const float* __restrict__ h, int Hd, Heads hd) {
+    extern __shared__ float hs[];
+    const int b = blockIdx.x;
+    for (int j = threadIdx.x; j < Hd; j += blockDim.x) hs[j] = h[(size_t)b * Hd + j];
+    __syncthreads();
+    heads_eval(hs, Hd, hd, b);
+}
+hipError_t launch_heads_rows(const float* hs, int rows, int Hd, const Heads& heads, hipStream_t s) {
+    if (rows < 1 || heads.pred) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(heads_rows_kernel, dim3(rows), dim3(256), Hd * sizeof(float), s, hs, Hd, heads);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ range check (fp16 calibration)
 // slot[0] = max |x| as float bits (non-negative floats order like unsigned ints), slot[1] = count of non-finite elements
 template <typename T>

@@ -881,7 +881,9 @@ struct Fwd {
     // RNNStateEncoder.forward (models/decoder/state_encoder.py:135-137): single_forward when the feature batch equals
     // the hidden batch, else seq_forward (:83-133) -- T steps over (T*N) feature rows with per-step masking (the
     // reference masks at segment starts only; inside a segment every mask is 1, so per-step masking is identical).
-    void rnn_scan(const RnnW& w, float* xh, int ld, int T, int N, const float* h_in, const float* mask, float* h_out, const Heads& heads) {
+    // seq (optional, T > 1): (T*N, hidden) -- h_t of every row, copied out behind each step
+    void rnn_scan(const RnnW& w, float* xh, int ld, int T, int N, const float* h_in, const float* mask, float* h_out, const Heads& heads,
+                  float* seq = nullptr) {
         if (T == 1) { rnn_step(w, xh, ld, N, h_in, mask, h_out, heads); return; }
         const int R = ctx->cfg.rnn_type == HCM_LSTM ? 2 : 1;
         float* pp[2] = {alloc_f((size_t)R * N * ctx->cfg.hidden), alloc_f((size_t)R * N * ctx->cfg.hidden)};
@@ -897,8 +899,30 @@ struct Fwd {
             const size_t m = ar.mark();
             rnn_step(w, xh + (size_t)t * N * ld, ld, N, cur, mask + (size_t)t * N, dst, hd);
             ar.release(m);
+            if (seq && !dry) ck(hipMemcpyAsync(seq + (size_t)t * N * ctx->cfg.hidden, dst, (size_t)N * ctx->cfg.hidden * 4, hipMemcpyDeviceToDevice, s), "scan: h_t row block");
             cur = dst;
         }
+    }
+
+    // The sequence calls' scan that keeps h_t of every row (T > 1; CMANet: the attention stage between its two encoders needs `state` for all rows).
+    // Where state_scan.hip serves the hidden size: the x half of the gate products for all T*N rows in one GEMM (xh rows are [x | h*mask]: the h
+    // columns are not read), then one launch per step + the guard's reduction; the heads over the whole sequence buffer in one launch.  Otherwise, and
+    // with HCM_NO_STATE_SCAN (development build, the A/B of tools/bench_cma_seq.py): rnn_scan, heads inside its cells.
+    void state_scan(const RnnW& w, float* xh, int ld, int T, int N, const float* h_in, const float* mask, float* h_out, float* seq, const Heads& heads) {
+        const int H = ctx->cfg.hidden;
+        const bool gru = ctx->cfg.rnn_type != HCM_LSTM;
+        static const bool off = dev_env("HCM_NO_STATE_SCAN") != nullptr;
+        if (off || !w.scan_w || w.early != w.in || w.in % 4) { rnn_scan(w, xh, ld, T, N, h_in, mask, h_out, heads, seq); return; }
+        const int G = gru ? 3 : 4, rows = T * N;
+        float* pre = alloc_f((size_t)rows * G * H);
+        unsigned* flags = (unsigned*)alloc_f((size_t)rows * (H / kScanUnits));
+        LinW ih = gru ? w.ih : w.cat;                  // LSTM: the first `in` columns of [W_ih | W_hh], bias b_ih + b_hh; GRU: W_ih, bias b_ih
+        ih.K = w.in;
+        linear(ih, xh, rows, ld, pre, G * H, ACT_NONE, true);
+        if (dry) return;
+        unsigned* bad = ctx->calib_buf ? ctx->calib_buf + hcm_ctx::kStepBadWord : nullptr;
+        ck(launch_state_scan(pre, w.scan_w, gru ? w.hh.bias : nullptr, h_in, mask, seq, h_out, flags, bad, T, N, H, gru ? 1 : 0, s), "state scan");
+        if (heads.out0 || heads.out1) ck(launch_heads_rows(seq, rows, H, heads, s), "heads over the sequence");
     }
 
     // rnn_in tap: the logical input x (without the h*mask block that sits between its early and late columns)
@@ -1499,8 +1523,12 @@ struct Fwd {
         if (!dry) ck(launch_mean_rows(rgb_tok, rmean, dt, B, 16, rC, rC, rC, 0, s), "rgb mean");
         linear(w.rgb_linear, rmean, B, rC, xh1, ld1, ACT_RELU, true);
         linear(w.depth_linear, dep_tok, B, dS * dC, xh1 + c.rgb_out, ld1, ACT_RELU, true);
-        rnn_step(w.rnn1, xh1, ld1, B, h_in, mask, h_out, Heads{});
-        const float* state = h_out;                               // new h of the first encoder: (B, H)
+        // T > 1 (hcm_cma_forward_seq): the rows are T*N frames, time-major, the state (R,N,H) per encoder; `state` is then h_t of every row
+        const int N = B / T;
+        float* seq1 = T > 1 ? alloc_f((size_t)B * H) : nullptr;
+        if (T == 1) rnn_step(w.rnn1, xh1, ld1, B, h_in, mask, h_out, Heads{});
+        else state_scan(w.rnn1, xh1, ld1, T, N, h_in, mask, h_out, seq1, Heads{});
+        const float* state = T == 1 ? h_out : seq1;               // new h of the first encoder: (B, H)
         tap("cma.state", state, false, {B, H});
         // x = [state | text | rgb | depth] (cma.py:309-311)
         const int ldc = H + C + c.rgb_out + c.depth_out;
@@ -1531,7 +1559,8 @@ struct Fwd {
         Heads hd;
         hd.w0 = w.lin_w; hd.b0 = w.lin_b; hd.out0 = out; hd.r0 = c.num_actions; hd.ld0 = c.num_actions;
         hd.w1 = w.stop_w; hd.b1 = w.stop_b; hd.out1 = stop; hd.r1 = 1; hd.ld1 = 1;
-        rnn_step(w.rnn2, xh2, ld2, B, h_in + (size_t)R * B * H, mask, h_out + (size_t)R * B * H, hd);
+        if (T == 1) rnn_step(w.rnn2, xh2, ld2, B, h_in + (size_t)R * B * H, mask, h_out + (size_t)R * B * H, hd);
+        else state_scan(w.rnn2, xh2, ld2, T, N, h_in + (size_t)R * N * H, mask, h_out + (size_t)R * N * H, alloc_f((size_t)B * H), hd);
     }
 
 
@@ -1869,8 +1898,9 @@ void run_refresh_instruction(hcm_ctx* ctx, const void* ids, int ids_dt, int B, c
     f.refresh_instruction(ids, ids_dt, B, idx, n);
 }
 void run_cma(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, const float* h_in,
-             const float* mask, float* out, float* stop, float* h_out) {
+             const float* mask, float* out, float* stop, float* h_out, int T) {
     Fwd f(ctx);
+    f.T = T;
     f.cma_step(rgb, rgb_dt, depth, ids, ids_dt, B, h_in, mask, out, stop, h_out);
 }
 void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,

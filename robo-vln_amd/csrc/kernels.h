@@ -272,6 +272,18 @@ hipError_t launch_lstm_cell(const float* gates, const float* h_in, const float* 
 // GRU cell from gi, gh [B][3H] (r,z,n); h = h_in[0]*mask; writes h_out (1,B,H)
 hipError_t launch_gru_cell(const float* gi, const float* gh, const float* h_in, const float* mask, float* h_out,
                            int B, int Hd, const Heads& heads, hipStream_t s);
+// The action heads of `rows` hidden states in one launch (hs [rows][Hd] f32): what the cells above do for their own sample, for a whole sequence buffer
+hipError_t launch_heads_rows(const float* hs, int rows, int Hd, const Heads& heads, hipStream_t s);
+// State-encoder scan (state_scan.hip): T masked recurrent steps from the input projection of every row, ONE launch per step.
+//   pre [T*N][G*H] = x W_ih^T + bias (G = 4 LSTM i,f,g,o: bias b_ih + b_hh / 3 GRU r,z,n: bias b_ih); bhh [G*H] added to the recurrent product, or null
+//   ws = W_hh in scan order (state_scan_pack): [H/16 unit slices][H (k)][16 units][4 gates] (GRU: 4th slot 0) -- a workgroup's slice is contiguous
+//   h_in / h_out (R,N,H) with R = 2 (h, c) for LSTM, 1 for GRU; may alias.  mask [T*N].  seq [T*N][H] = h_t of every row (also the state the next
+//   step reads; c is updated in place in h_out).  flags [T*N][H/16] scratch words; bad = overflow-guard word or null.
+constexpr int kScanUnits = 16;
+bool state_scan_ok(int H);
+void state_scan_pack(const float* w_hh, float* out, int H, int G);       // host-side re-layout of torch's (G*H, H)
+hipError_t launch_state_scan(const float* pre, const float* ws, const float* bhh, const float* h_in, const float* mask, float* seq, float* h_out,
+                             unsigned* flags, unsigned* bad, int T, int N, int H, int gru, hipStream_t s);
 // split-K: fixed-order sum of S f32 partial results [S][M][N] + bias + activation (see Fwd::linear)
 // How many K slices a skinny long-K linear layer is cut into (forward.cpp Fwd::linear and hcm_op_linear use the same rule, so an operator call
 // reproduces the model path bit for bit): powers of two while the (64 x 32-tile) grid stays under 256 workgroups and a slice keeps >= 256 columns

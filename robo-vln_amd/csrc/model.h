@@ -101,6 +101,7 @@ struct RnnW {
     // depend only on the encoders' own projections and the previous state, so that GEMM runs beside the cross-modal block
     // and only the `in - early` late columns are multiplied in the serial tail (LSTM only; GRU keeps early = in).
     int early = 0;
+    float* scan_w = nullptr;   // W_hh in the order of state_scan.hip (state_scan_pack), CMANet's two encoders when the kernel serves `hidden`; else null
     int xcol(int j) const { return j < early ? j : j + (cat.w ? cat.N / 4 : 0); }
 };
 struct HighW {

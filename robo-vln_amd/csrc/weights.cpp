@@ -1103,6 +1103,15 @@ void prepare_cma(hcm_ctx* ctx) {
     w.compress = make_linear(up, {&T_(ctx, M, "second_state_compress.0.weight")}, {&T_(ctx, M, "second_state_compress.0.bias")}, DT_F32);
     w.rnn1 = make_rnn(ctx, up, M, "state_encoder.rnn.");
     w.rnn2 = make_rnn(ctx, up, M, "second_state_encoder.rnn.");
+    // hcm_cma_forward_seq: W_hh of both state encoders once more, in the order of the one-launch-per-step scan (state_scan.hip)
+    if (state_scan_ok(c.hidden)) {
+        const int G = c.rnn_type == HCM_LSTM ? 4 : 3;
+        std::vector<float> t((size_t)c.hidden * c.hidden * 4);
+        state_scan_pack(T_(ctx, M, "state_encoder.rnn.weight_hh_l0").f.data(), t.data(), c.hidden, G);
+        w.rnn1.scan_w = up.f32(t);
+        state_scan_pack(T_(ctx, M, "second_state_encoder.rnn.weight_hh_l0").f.data(), t.data(), c.hidden, G);
+        w.rnn2.scan_w = up.f32(t);
+    }
     w.scale = T_(ctx, M, "_scale").f[0];                  // registered buffer: 1 / sqrt(hidden / 2) (cma.py:147)
     w.lin_w = up.f32(T_(ctx, M, "linear.weight").f);
     w.lin_b = up.f32(T_(ctx, M, "linear.bias").f);
