@@ -409,6 +409,41 @@ int hcm_s2s_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* d
 int hcm_s2s_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int B_instr,
                         int L, const float* h_in, const float* masks, float* out, float* stop, float* progress, float* h_out, void* stream);
 
+/* The flat trainer's validation step, RoboVLNTrainer._update_agent_val (robo_vln_trainer.py:544-575, driven by val_epoch :726-813): the model on the
+ * chunk's T*N time-major frames and the three criteria, in one call.  CMANet and Seq2SeqNet handles only (an HCM handle: HCM_ERR_STATE; the
+ * hierarchical pair has hcm_val_step).  Rows, masks, h_in / h_out (R,N,hidden) with R = hcm_query(HCM_NUM_RECURRENT_LAYERS), aliasing, L and the
+ * T*N <= max_batch rule are those of the handle kind's own sequence call, hcm_cma_forward_seq / hcm_s2s_forward_seq; T = 1 is legal.
+ *   ids               (B_instr,L)  CMANet: B_instr must be T*N; Seq2SeqNet: T*N, or 1 = one instruction for every frame (seq2seq.py:163)
+ *   corrected_actions (T*N,num_actions) f32  (:557-561)
+ *   oracle_stop       (T*N,1)      f32    -1 = padded row (:563)
+ *   progress          (T*N,)       f32    observations["progress"]: required on a Seq2SeqNet handle created with progress_monitor = 1 (the loss of
+ *                                  seq2seq.py:176-185), and NULL -- as progress_hat -- on every other handle (HCM_ERR_ARG otherwise)
+ * The forward is `output, stop_out, h' = actor_critic((obs, h, prev_actions, masks))` (:553-555) with the launches of the sequence call.
+ *   result (8,) f32 device out:
+ *     [0] action loss: output set to 0 wherever corrected_actions == 0, element by element, then MSELoss(): the mean over ALL num_actions*T*N
+ *         elements (:557-561)
+ *     [1] stop loss: BCEWithLogitsLoss() over the rows with oracle_stop != -1 (:563-566), as max(x,0) - x*y + log1p(exp(-|x|))
+ *     [2] aux loss: AuxLosses.reduce(~action_mask[:,0]) (:569-570; common/aux_losses.py:27-33) = the mean over the rows with
+ *         corrected_actions[r,0] != 0 of (tanh(progress_monitor(x))[r] - progress[r])^2, weight 1.0: the model hands PROGRESS_MONITOR.alpha to
+ *         register_loss in the `masks` position (seq2seq.py:181-185 against aux_losses.py:15), so the configured alpha never arrives and the
+ *         default of 1.0 applies -- reproduced.  Exactly 0 when the handle has no progress monitor (nothing registered: reduce returns 0.0)
+ *     [3] rows that entered the stop loss;  [4] rows that entered the aux mean (0 without the monitor);  [5..7] 0
+ *   Empty selections give what torch gives: 0/0 = NaN in [1], and in [2] with the monitor on.  That NaN is a result, not a fault: it does not
+ *   touch the overflow guard (HCM_STEP_NONFINITE).  NaN / inf in a selected row's model outputs propagate into the loss as in torch.
+ *   out (T*N,num_actions) / stop (T*N,1) / progress_hat (T*N,1): optional outputs (NULL = not wanted): the model's outputs BEFORE any masking,
+ *   bit-identical -- as is h_out -- to what the sequence call writes for the same inputs.  With the monitor on the progress head runs
+ *   whether or not progress_hat is wanted (into workspace otherwise).
+ * All f32 arithmetic of the criteria is done in a fixed order by one workgroup: two calls on the same inputs give the same eight words.
+ * No host synchronisation, no allocation, nothing read back: the call may be enqueued inside a stream capture (after one eager call at the
+ * same shape, which performs the one-time kernel attribute setup).  The call itself is never replayed from a graph of the library's own.
+ * The epoch on top (zero state per batch, chunks of tbptt_steps rows, the state carried, "Val Loss Epoch" = the mean over chunks of
+ * [0] + [1] + [2]) is robo-vln_amd/validate.py FlatValidator. */
+int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
+                      int T, int N, int B_instr, int L,
+                      const float* corrected_actions, const float* oracle_stop, const float* progress,
+                      const float* h_in, const float* masks, float* result, float* h_out,
+                      float* out, float* stop, float* progress_hat, void* stream);
+
 /* ---- test / profiling hooks (not part of the drop-in surface) ---- */
 
 /* Enable capture of named intermediate activations during the next forward calls. */
@@ -567,6 +602,11 @@ int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, 
  * label tensors as hcm_val_step takes them, result (8,) as it writes them; any rows >= 1 (one workgroup, rows strided over its 256 threads). */
 int hcm_op_val_loss(const float* logits, const float* vel, const float* stop, const int64_t* oracle_subtask, const float* corrected_actions,
                     const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, void* stream);
+/* The criterion launch of hcm_flat_val_step on its own (csrc/elementwise.hip, flat_val_loss_kernel): out (rows, num_actions), stop (rows, 1),
+ * progress_hat (rows, 1) and progress (rows,) -- both NULL = no progress monitor, result[2] = 0 -- corrected_actions (rows, num_actions),
+ * oracle_stop (rows, 1), result (8,) as hcm_flat_val_step writes them; any rows >= 1 (one workgroup, rows strided over its 256 threads). */
+int hcm_op_flat_val_loss(const float* out, const float* stop, const float* progress_hat, const float* corrected_actions, const float* oracle_stop,
+                         const float* progress, float* result, int rows, int num_actions, void* stream);
 /* The state-encoder scan of hcm_cma_forward_seq on its own (csrc/state_scan.hip): T masked steps of nn.LSTM (rnn_type HCM_LSTM, gates i,f,g,o) or
  * nn.GRU (HCM_GRU, gates r,z,n) from the input projection of every row, one launch per step.
  *   pre (T*N, G*hidden) = x W_ih^T + bias (LSTM: b_ih + b_hh, b_hh = NULL here; GRU: b_ih, and b_hh (3*hidden,) is added inside the step)

@@ -76,6 +76,7 @@ EXPORTS = {
     "hcm_val_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hcm_flat_val_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
     "hcm_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hcm_act_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -126,6 +127,7 @@ EXPORTS = {
     "hcm_op_conv2d_gn_pool": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 11 + [C.c_float, C.c_void_p]),
     "hcm_op_conv2d_gn_res2": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 9 + [C.c_float, C.c_int, C.c_void_p]),
     "hcm_op_val_loss": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
+    "hcm_op_flat_val_loss": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_void_p]),
     "hcm_op_state_scan": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
 }

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .config import CMAConfig
-from .policy import _TORCH_DT, _np32
+from .policy import _TORCH_DT, _np32, _ptr
 
 
 def _to_struct(cfg: CMAConfig, max_batch, precision):
@@ -34,6 +34,36 @@ def _to_struct(cfg: CMAConfig, max_batch, precision):
     s.instr_rnn = _lib.HCM_LSTM if cfg.instr_rnn == "LSTM" else _lib.HCM_GRU
     s.ablate_instruction, s.ablate_depth, s.ablate_rgb = int(cfg.ablate_instruction), int(cfg.ablate_depth), int(cfg.ablate_rgb)
     return s
+
+
+def _val_labels(eng, rows, hidden, corrected_actions, oracle_stop, masks, result):
+    """Argument handling shared by CMAEngine.val_step and S2SEngine.val_step: the state (R,N,hidden), the labels as the trainer's collate carries
+    them -- corrected_actions (rows,num_actions), oracle_stop (rows,) or (rows,1), masks (rows,) or (rows,2) -- and the caller's result row.
+    -> (h_in, N, corrected, oracle_stop, masks[:,0], result), all contiguous f32 on the engine's device."""
+    c = eng.cfg
+    h_in = eng._dev(hidden, (torch.float32,))
+    R = eng.num_recurrent_layers
+    if h_in.dim() != 3 or h_in.shape[0] != R or h_in.shape[2] != c.hidden or h_in.shape[1] < 1:
+        raise ValueError(f"hidden must be ({R},N,{c.hidden}), got {tuple(h_in.shape)}")
+    N = h_in.shape[1]
+    if rows % N:
+        raise ValueError(f"{rows} frames is not a multiple of the hidden batch {N}")
+    ca = eng._dev(corrected_actions, (torch.float32,))
+    if tuple(ca.shape) != (rows, c.num_actions):
+        raise ValueError(f"corrected_actions must be ({rows},{c.num_actions}), got {tuple(ca.shape)}")
+    os_ = eng._dev(oracle_stop, (torch.float32,))
+    if tuple(os_.shape) not in ((rows,), (rows, 1)):
+        raise ValueError(f"oracle_stop must be ({rows},) or ({rows},1), got {tuple(os_.shape)}")
+    m = eng._dev(masks, (torch.float32,))
+    if tuple(m.shape) not in ((rows,), (rows, 1), (rows, 2)):
+        raise ValueError(f"masks must be ({rows},) or ({rows},2), got {tuple(m.shape)}")
+    m = m.reshape(rows, -1)[:, 0].contiguous()                  # masks[:,0] (cma.py:219, seq2seq.py:172)
+    if result is None:
+        result = torch.empty(8, device=eng.device, dtype=torch.float32)
+    elif (not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.numel() != 8 or not result.is_contiguous()
+          or result.device.type != eng.device.type or (eng.device.index is not None and result.device.index != eng.device.index)):
+        raise ValueError("result must be a contiguous (8,) float32 tensor on the engine's device")
+    return h_in, N, ca, os_, m, result
 
 
 class CMAEngine:
@@ -160,6 +190,44 @@ class CMAEngine:
                                                      _TORCH_DT[ids.dtype], T, N, ids.shape[1], h_in.data_ptr(), m.data_ptr(), out.data_ptr(),
                                                      stop.data_ptr(), h_out.data_ptr(), st), self._h)
         return out, stop, h_out
+
+    def val_step(self, observations, corrected_actions, oracle_stop, hidden, masks, result=None, return_outputs=False):
+        """The flat trainer's validation step, `_update_agent_val` (robo_vln_trainer.py:544-575), in one library call (hcm_flat_val_step): the
+        model on the chunk's T*N time-major rows of `observations` (N = hidden.shape[1]) and the criteria.  Returns (result, hidden'), plus
+        (out, stop, None) BEFORE any masking with return_outputs=True -- the third place is Seq2SeqNet's progress_hat; CMANet has no progress
+        monitor.  result is the (8,) f32 device tensor of include/hcm.h: [action loss, stop loss, aux loss (0 here), stop rows, aux rows (0), 0, 0,
+        0]; it is written into `result` when given, so that a caller can keep a table of them and read once.  Does not synchronise."""
+        c = self.cfg
+        with torch.cuda.device(self.device):
+            rgb = self._dev(observations["rgb"], (torch.float32, torch.uint8))
+            depth = self._dev(observations["depth"], (torch.float32,))
+            B = rgb.shape[0]
+            if rgb.dim() != 4 or tuple(rgb.shape[1:]) != (*c.rgb_shape, 3):
+                raise ValueError(f"rgb must be (T*N,{c.rgb_shape[0]},{c.rgb_shape[1]},3), got {tuple(rgb.shape)}")
+            if tuple(depth.shape) != (B, c.depth_hw, c.depth_hw, 1):
+                raise ValueError(f"depth must be ({B},{c.depth_hw},{c.depth_hw},1), got {tuple(depth.shape)}")
+            ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
+            if ids.dim() != 2 or ids.shape[0] not in (1, B) or not 1 <= ids.shape[1] <= c.instr_len:
+                raise ValueError(f"instruction must be (T*N or 1, L <= {c.instr_len}), got {tuple(ids.shape)}")
+            ids = ids.expand(B, ids.shape[1]).contiguous()                       # cma.py:226
+            h_in, N, ca, os_, m, result = _val_labels(self, B, hidden, corrected_actions, oracle_stop, masks, result)
+            h_out = torch.empty_like(h_in)
+            out = stop = None
+            if return_outputs:
+                out = torch.empty(B, c.num_actions, device=self.device, dtype=torch.float32)
+                stop = torch.empty(B, 1, device=self.device, dtype=torch.float32)
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(self._lib.hcm_flat_val_step(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(), _TORCH_DT[ids.dtype],
+                                                   B // N, N, B, ids.shape[1], ca.data_ptr(), os_.data_ptr(), None, h_in.data_ptr(), m.data_ptr(),
+                                                   result.data_ptr(), h_out.data_ptr(), _ptr(out), _ptr(stop), None, st), self._h)
+        if return_outputs:
+            return result, h_out, (out, stop, None)
+        return result, h_out
+
+    @staticmethod
+    def check_val_result(result):
+        """One or more val_step results ((8,) or (n,8), any device; synchronises if on the GPU) as a CPU tensor: the one read of an epoch."""
+        return torch.as_tensor(result).detach().to("cpu", torch.float32).reshape(-1, 8)
 
     def _forward_graph(self, rgb, depth, ids, h_in, m, B):
         c = self.cfg

@@ -29,6 +29,9 @@ void run_step(hcm_ctx* ctx, bool do_hi, bool do_lo, const void* rgb, int rgb_dt,
 void run_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, const int64_t* oracle,
                   const float* corrected, const float* oracle_stop, const float* hi_h_in, const float* lo_h_in, const float* mask, float* result,
                   float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop);
+void run_flat_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, int Bi,
+                       const float* corrected, const float* oracle_stop, const float* progress, const float* h_in, const float* mask, float* result,
+                       float* h_out, float* out, float* stop, float* progress_hat);
 }  // namespace hcm
 
 using namespace hcm;
@@ -443,11 +446,19 @@ static void dry_run(hcm_ctx* h, int B) {
         // buffers: T = B, N = 1 has all B rows whatever B's divisors) or with N (the per-step path's ping-pong state: largest at T = 2)
         for (int T : {2, 3, B})
             if (T >= 2 && T <= B) run_cma(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, T);
+        // hcm_flat_val_step: the same shapes with every optional output row (out, stop) in the workspace
+        for (int T : {1, 2, 3, B})
+            if (T <= B) run_flat_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, T, B / T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr);
         return;
     }
     if (h->kind == 2) {                                // the step with one instruction per row, and the sequence path at T = 2, 3 (as below)
-        for (int T = 1; T <= 3 && T <= B; ++T)
+        for (int T = 1; T <= 3 && T <= B; ++T) {
             run_s2s(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B / T * T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, T);
+            // hcm_flat_val_step: out, stop and -- with the progress monitor, whose head runs whether or not its rows are wanted -- progress_hat in the workspace
+            run_flat_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, T, B / T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, nullptr);
+        }
         return;
     }
     const bool hi = h->cfg.build_high != 0, lo = h->cfg.build_low != 0;
@@ -1021,6 +1032,40 @@ int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* dept
     return HCM_OK;
 }
 
+int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int B_instr, int L,
+                      const float* corrected_actions, const float* oracle_stop, const float* progress, const float* h_in, const float* masks,
+                      float* result, float* h_out, float* out, float* stop, float* progress_hat, void* stream) {
+    REQUIRE(h, HCM_ERR_ARG, "null handle");
+    REQUIRE(h->kind == 1 || h->kind == 2, HCM_ERR_STATE,
+            "hcm_flat_val_step needs a CMANet or Seq2SeqNet handle (hcm_cma_create / hcm_s2s_create): the hierarchical pair is validated by hcm_val_step");
+    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
+    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
+    REQUIRE(result, HCM_ERR_ARG, "null result");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    const bool monitor = h->kind == 2 && h->s2s_cfg.progress_monitor;
+    if (h->kind == 1)
+        REQUIRE(B_instr == T * N, HCM_ERR_ARG, "B_instr must be T*N on a CMANet handle: one instruction row per frame (hcm_cma_forward_seq)");
+    else
+        REQUIRE(B_instr == 1 || B_instr == T * N, HCM_ERR_ARG,
+                "B_instr must be 1 (one instruction for every frame, seq2seq.py:163) or the number of frames");
+    REQUIRE(monitor || (!progress && !progress_hat), HCM_ERR_ARG,
+            "progress and progress_hat must be NULL: the handle has no progress monitor (hcm_s2s_config.progress_monitor)");
+    REQUIRE(!monitor || progress, HCM_ERR_ARG,
+            "null progress: the handle was created with PROGRESS_MONITOR.use, the auxiliary loss needs observations[\"progress\"]");
+    int rc = check_fwd(h, T * N);
+    if (rc) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(rgb && depth && ids && corrected_actions && oracle_stop && h_in && masks && h_out, HCM_ERR_ARG, "null pointer");
+    h->stream = (hipStream_t)stream;
+    try {
+        run_flat_val_step(h, rgb, rgb_dtype, depth, ids, ids_dtype, T, N, B_instr, corrected_actions, oracle_stop, progress, h_in, masks, result, h_out,
+                          out, stop, progress_hat);
+    } catch (const std::exception& e) {
+        return fail(h, HCM_ERR_HIP, e.what());
+    }
+    return HCM_OK;
+}
+
 int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
                const int32_t* lengths, int B, int L, const float* hi_h_in, const float* lo_h_in, const float* mask, float* record, float* hi_h_out, float* lo_h_out,
                int flags, void* stream) {
@@ -1582,6 +1627,14 @@ int hcm_op_val_loss(const float* logits, const float* vel, const float* stop, co
         return HCM_ERR_ARG;
     return op_rc(launch_val_loss(logits, A, vel, 2, stop, 1, oracle_subtask, corrected_actions, oracle_stop, result, rows, A, num_sub_tasks, 2,
                                  (hipStream_t)stream));
+}
+
+int hcm_op_flat_val_loss(const float* out, const float* stop, const float* progress_hat, const float* corrected_actions, const float* oracle_stop,
+                         const float* progress, float* result, int rows, int num_actions, void* stream) {
+    if (!out || !stop || !corrected_actions || !oracle_stop || !result || rows < 1 || num_actions < 1 || (progress_hat == nullptr) != (progress == nullptr))
+        return HCM_ERR_ARG;
+    return op_rc(launch_flat_val_loss(out, num_actions, stop, 1, progress_hat, 1, corrected_actions, oracle_stop, progress, result, rows, num_actions,
+                                      (hipStream_t)stream));
 }
 
 int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,

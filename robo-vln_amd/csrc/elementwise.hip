@@ -1732,6 +1732,83 @@ hipError_t launch_val_loss(const float* logits, int ld_logits, const float* vel,
     return hipGetLastError();
 }
 
+// The criteria of the flat trainer's _update_agent_val (robo_vln_trainer.py:544-575) over the rows of one CMANet / Seq2SeqNet call, f32:
+//   result[0] MSELoss of out.masked_fill(corrected == 0, 0) against corrected, mean over all num_actions * rows elements (:557-561)
+//   result[1] BCEWithLogitsLoss of stop against oracle_stop over the rows with oracle_stop != -1 (:563-566)
+//   result[2] AuxLosses.reduce(~action_mask[:, 0]) (:569-570, common/aux_losses.py:27-33): the mean over the rows with corrected[r, 0] != 0 of
+//             (progress_hat[r] - progress[r])^2, the loss Seq2SeqNet registers (seq2seq.py:176-185), times a weight of 1.0 -- the model passes
+//             PROGRESS_MONITOR.alpha in the `masks` slot of register_loss(name, loss, masks=None, alpha=1.0), so the configured alpha never
+//             arrives and the weight is the default; reproduced here.  progress_hat == NULL (nothing registered): reduce returns 0.0.
+//   result[3] rows that entered the stop loss;  result[4] rows that entered the aux mean (0 without the monitor);  result[5..7] 0
+// Empty selections: 0 / 0 = NaN in result[1], and in result[2] with the monitor on, as torch's mean over an empty tensor.
+// Launch shape and order of summation as val_loss_kernel's: ONE workgroup of kValLossThreads threads, thread t adds its rows t, t + 256, ...
+// in row order, a xor butterfly per wave, lane 0 of wave 0 adds the four waves' sums in wave order.  No atomics; counts are integers until
+// the final store.
+__global__ __launch_bounds__(kValLossThreads) void flat_val_loss_kernel(const float* __restrict__ out, int ld_out, const float* __restrict__ stop, int ld_stop,
+                                                                        const float* __restrict__ progress_hat, int ld_prog,
+                                                                        const float* __restrict__ corrected, const float* __restrict__ oracle_stop,
+                                                                        const float* __restrict__ progress, float* __restrict__ result, int rows,
+                                                                        int num_actions) {
+    float mse = 0.f, bce = 0.f, aux = 0.f;
+    int n_stop = 0, n_aux = 0;
+    const bool monitor = progress_hat != nullptr && progress != nullptr;
+    for (int r = threadIdx.x; r < rows; r += kValLossThreads) {
+        for (int j = 0; j < num_actions; ++j) {
+            const float c = corrected[(size_t)r * num_actions + j];
+            const float v = c == 0.f ? 0.f : out[(size_t)r * ld_out + j];
+            const float d = v - c;
+            mse += d * d;
+        }
+        const float y = oracle_stop[r];
+        if (y != -1.f) {
+            const float x = stop[(size_t)r * ld_stop];
+            bce += (fmaxf(x, 0.f) - x * y) + log1pf(expf(-fabsf(x)));
+            ++n_stop;
+        }
+        if (monitor && corrected[(size_t)r * num_actions] != 0.f) {
+            const float d = progress_hat[(size_t)r * ld_prog] - progress[r];
+            aux += d * d;
+            ++n_aux;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mse += __shfl_xor(mse, o, 64); bce += __shfl_xor(bce, o, 64); aux += __shfl_xor(aux, o, 64);
+        n_stop += __shfl_xor(n_stop, o, 64); n_aux += __shfl_xor(n_aux, o, 64);
+    }
+    constexpr int NW = kValLossThreads / 64;
+    __shared__ float fs[NW][3];
+    __shared__ int is[NW][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        fs[wave][0] = mse; fs[wave][1] = bce; fs[wave][2] = aux;
+        is[wave][0] = n_stop; is[wave][1] = n_aux;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float f[3] = {0.f, 0.f, 0.f};
+        int n[2] = {0, 0};
+        for (int w = 0; w < NW; ++w) {
+            for (int k = 0; k < 3; ++k) f[k] += fs[w][k];
+            for (int k = 0; k < 2; ++k) n[k] += is[w][k];
+        }
+        result[0] = f[0] / ((float)rows * (float)num_actions);
+        result[1] = f[1] / (float)n[0];
+        result[2] = monitor ? f[2] / (float)n[1] : 0.f;
+        result[3] = (float)n[0];
+        result[4] = (float)n[1];
+        result[5] = 0.f;
+        result[6] = 0.f;
+        result[7] = 0.f;
+    }
+}
+hipError_t launch_flat_val_loss(const float* out, int ld_out, const float* stop, int ld_stop, const float* progress_hat, int ld_prog,
+                                const float* corrected, const float* oracle_stop, const float* progress, float* result, int rows, int num_actions,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(flat_val_loss_kernel, dim3(1), dim3(kValLossThreads), 0, s, out, ld_out, stop, ld_stop, progress_hat, ld_prog, corrected,
+                       oracle_stop, progress, result, rows, num_actions);
+    return hipGetLastError();
+}
+
 template <typename T>
 __global__ void to_f32_kernel(const T* __restrict__ x, float* __restrict__ y, size_t n) {
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) y[e] = Tr<T>::ld(x + e);

@@ -969,6 +969,15 @@ struct Fwd {
         const float* oracle_stop = nullptr;
         float* result = nullptr;
     } val;
+    // hcm_flat_val_step (the flat trainer's validation step, robo_vln_trainer.py:544-575): cma_step / s2s_step with their own launches, then one
+    // criterion launch on the caller's stream.  fval.on with null labels = the sizing pass of hcm_finalize.
+    struct FlatVal {
+        bool on = false;
+        const float* corrected = nullptr;
+        const float* oracle_stop = nullptr;
+        const float* progress = nullptr;      // observations["progress"]: Seq2SeqNet handles with the progress monitor only
+        float* result = nullptr;
+    } fval;
 
 
     HiBufs hi_alloc(int B) {
@@ -1425,6 +1434,10 @@ struct Fwd {
         const bool multi = ctx->concurrent && !ctx->taps_on;
         hipStream_t main_s = ctx->stream;
         hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s;
+        if (fval.on) {                                            // outputs the caller did not ask for still feed the criteria: workspace rows
+            if (!out) out = alloc_f((size_t)B * c.num_actions);
+            if (!stop) stop = alloc_f((size_t)B);
+        }
         // buffers shared across the forked chains
         use(ctx->dt_vla);
         void* rgb_tok = alloc_t((size_t)B * 16 * rC);
@@ -1561,6 +1574,10 @@ struct Fwd {
         hd.w1 = w.stop_w; hd.b1 = w.stop_b; hd.out1 = stop; hd.r1 = 1; hd.ld1 = 1;
         if (T == 1) rnn_step(w.rnn2, xh2, ld2, B, h_in + (size_t)R * B * H, mask, h_out + (size_t)R * B * H, hd);
         else state_scan(w.rnn2, xh2, ld2, T, N, h_in + (size_t)R * N * H, mask, h_out + (size_t)R * N * H, alloc_f((size_t)B * H), hd);
+        // CMANet registers no auxiliary loss (hcm_cma_config.progress_monitor must be 0): AuxLosses.reduce returns 0.0
+        if (fval.on && !dry)
+            ck(launch_flat_val_loss(out, c.num_actions, stop, 1, nullptr, 1, fval.corrected, fval.oracle_stop, nullptr, fval.result, B, c.num_actions, s),
+               "flat val loss");
     }
 
 
@@ -1590,6 +1607,11 @@ struct Fwd {
         hipStream_t main_s = ctx->stream;
         hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s;
         const int ldx = lw.rnn.in + c.hidden;
+        if (fval.on) {                                            // outputs the caller did not ask for still feed the criteria: workspace rows
+            if (!out) out = alloc_f((size_t)B * c.num_actions);
+            if (!stop) stop = alloc_f((size_t)B);
+            if (!progress && m.progress_monitor) progress = alloc_f((size_t)B);      // the head runs whether or not the caller wants its rows
+        }
         float* xh = alloc_f((size_t)B * ldx);
         LoBufs lb;                                                // the low-level model's encoder paths write [depth | rgb] at its column 0
         lb.xh = xh + Hi; lb.ldx = ldx;
@@ -1659,6 +1681,9 @@ struct Fwd {
         if (progress) { hd.w2 = w.pm_w; hd.b2 = w.pm_b; hd.out2 = progress; hd.r2 = 1; hd.ld2 = 1; }
         rnn_scan(lw.rnn, xh, ldx, T, B / T, h_in, mask, h_out, hd);
         tap_rnn_in("s2s.rnn_in", lw.rnn, xh, ldx, B);
+        if (fval.on && !dry)
+            ck(launch_flat_val_loss(out, c.num_actions, stop, 1, progress, 1, fval.corrected, fval.oracle_stop, progress ? fval.progress : nullptr,
+                                    fval.result, B, c.num_actions, s), "flat val loss");
     }
 
 
@@ -1908,5 +1933,16 @@ void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, cons
     Fwd f(ctx);
     f.T = T;
     f.s2s_step(rgb, rgb_dt, depth, ids, ids_dt, B, Bi, h_in, mask, out, stop, progress, h_out);
+}
+// hcm_flat_val_step on a CMANet (Bi unused, progress pointers null) or Seq2SeqNet handle; null label pointers = the sizing pass
+void run_flat_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, int Bi,
+                       const float* corrected, const float* oracle_stop, const float* progress, const float* h_in, const float* mask, float* result,
+                       float* h_out, float* out, float* stop, float* progress_hat) {
+    Fwd f(ctx);
+    f.T = T;
+    f.fval.on = true;
+    f.fval.corrected = corrected; f.fval.oracle_stop = oracle_stop; f.fval.progress = progress; f.fval.result = result;
+    if (ctx->kind == 1) f.cma_step(rgb, rgb_dt, depth, ids, ids_dt, T * N, h_in, mask, out, stop, h_out);
+    else f.s2s_step(rgb, rgb_dt, depth, ids, ids_dt, T * N, Bi, h_in, mask, out, stop, progress_hat, h_out);
 }
 }  // namespace hcm

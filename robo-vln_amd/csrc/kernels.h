@@ -332,6 +332,12 @@ hipError_t launch_val_subtask(const int64_t* oracle, int64_t* subtask, int rows,
 // oracle_stop (rows,)
 hipError_t launch_val_loss(const float* logits, int ld_logits, const float* vel, int ld_vel, const float* stop, int ld_stop, const int64_t* oracle,
                            const float* corrected, const float* oracle_stop, float* result, int rows, int A, int num_sub_tasks, int n_vel, hipStream_t s);
+// hcm_flat_val_step: the flat trainer's validation criteria (robo_vln_trainer.py:544-575) over `rows` rows, launch shape and summation order as
+// launch_val_loss; result = 8 floats (include/hcm.h).  out [rows][num_actions] (ld_out), stop [rows] (ld_stop), progress_hat [rows] (ld_prog);
+// corrected (rows, num_actions), oracle_stop (rows,), progress (rows,).  progress_hat / progress NULL = no progress monitor: result[2] = 0
+hipError_t launch_flat_val_loss(const float* out, int ld_out, const float* stop, int ld_stop, const float* progress_hat, int ld_prog,
+                                const float* corrected, const float* oracle_stop, const float* progress, float* result, int rows, int num_actions,
+                                hipStream_t s);
 // fp16 range calibration: slot[0] = max(slot[0], bits of max |x|), slot[1] += number of non-finite elements; x is [rows][ld], cols used
 hipError_t launch_absmax(const void* x, int dt, int rows, int cols, int ld, unsigned* slot, hipStream_t s);
 // generic converts

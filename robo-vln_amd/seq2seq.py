@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .cma import _val_labels
 from .config import S2SConfig
 from .policy import _TORCH_DT, _np32, _ptr
 
@@ -164,6 +165,39 @@ class S2SEngine:
                                                      _TORCH_DT[ids.dtype], T, N, ids.shape[0], ids.shape[1], h_in.data_ptr(), m.data_ptr(),
                                                      out.data_ptr(), stop.data_ptr(), _ptr(prog), h_out.data_ptr(), st), self._h)
         return out, stop, prog, h_out
+
+    def val_step(self, observations, corrected_actions, oracle_stop, hidden, masks, result=None, return_outputs=False):
+        """The flat trainer's validation step, `_update_agent_val` (robo_vln_trainer.py:544-575), in one library call (hcm_flat_val_step): the
+        model on the chunk's T*N time-major rows of `observations` (N = hidden.shape[1]) and the criteria.  With PROGRESS_MONITOR.use,
+        observations["progress"] ((T*N,) or (T*N,1)) is the target of the auxiliary loss the reference registers at seq2seq.py:176-185.  Returns
+        (result, hidden'), plus (out, stop, progress_hat or None) BEFORE any masking with return_outputs=True.  result is the (8,) f32 device
+        tensor of include/hcm.h: [action loss, stop loss, aux loss, stop rows, aux rows, 0, 0, 0]; it is written into `result` when given, so
+        that a caller can keep a table of them and read once.  Does not synchronise."""
+        c = self.cfg
+        with torch.cuda.device(self.device):
+            rgb, depth, ids, B = self._inputs(observations, None)
+            h_in, N, ca, os_, m, result = _val_labels(self, B, hidden, corrected_actions, oracle_stop, masks, result)
+            prog = None
+            if c.progress_monitor:
+                if "progress" not in observations:
+                    raise ValueError("observations['progress'] is missing: the engine was built with progress_monitor=True")
+                prog = self._dev(observations["progress"], (torch.float32,))
+                if tuple(prog.shape) not in ((B,), (B, 1)):
+                    raise ValueError(f"observations['progress'] must be ({B},) or ({B},1), got {tuple(prog.shape)}")
+            h_out = torch.empty_like(h_in)
+            out, stop, prog_hat = self._outputs(B) if return_outputs else (None, None, None)
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(self._lib.hcm_flat_val_step(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(), _TORCH_DT[ids.dtype],
+                                                   B // N, N, ids.shape[0], ids.shape[1], ca.data_ptr(), os_.data_ptr(), _ptr(prog), h_in.data_ptr(),
+                                                   m.data_ptr(), result.data_ptr(), h_out.data_ptr(), _ptr(out), _ptr(stop), _ptr(prog_hat), st), self._h)
+        if return_outputs:
+            return result, h_out, (out, stop, prog_hat)
+        return result, h_out
+
+    @staticmethod
+    def check_val_result(result):
+        """One or more val_step results ((8,) or (n,8), any device; synchronises if on the GPU) as a CPU tensor: the one read of an epoch."""
+        return torch.as_tensor(result).detach().to("cpu", torch.float32).reshape(-1, 8)
 
     def _forward_graph(self, rgb, depth, ids, h_in, m, B):
         c = self.cfg
