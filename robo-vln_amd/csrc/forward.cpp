@@ -381,6 +381,22 @@ struct Fwd {
         //  k.. and of the compression conv, HCM_SKIP_GN_APPLY=1 the stand-alone normalisation passes)
         static const int gn_stop = dev_env("HCM_GN_STOP") ? atoi(dev_env("HCM_GN_STOP")) : -1;
         const bool dry_saved = dry;
+        // behind a layer's last block (3 + 4 + 6 + 3 bottlenecks): tap its output, stamp the layer's end (lo..hi: the layers a run kernel is built for; tapped = false: stamp only)
+        auto layer_end = [&](int lo = 1, int hi = 4, bool tapped = true) {
+            const int layer = bidx == 3 ? 1 : bidx == 7 ? 2 : bidx == 13 ? 3 : bidx == 16 ? 4 : 0;
+            if (layer < lo || layer > hi) return;
+            if (tapped) tap(tapname + "_layer" + std::to_string(layer), x.p, true, {B, x.H, x.W, x.C});
+            mark(tapname + ".layer" + std::to_string(layer) + "_end");
+        };
+        // weights, GroupNorm parameters and (range-folded) eps of a run of identity bottlenecks, for DepthL3 / DepthBlk
+        auto fill_run = [&](auto& q, size_t first, size_t run) {
+            for (size_t r = 0; r < run; ++r) {
+                const BottleneckW& bb = t.blocks[first + r];
+                q.w1[r] = bb.c1.w; q.w2[r] = bb.c2.w; q.w3[r] = bb.c3.w;
+                q.g1[r] = bb.n1.gamma; q.b1[r] = bb.n1.beta; q.g2[r] = bb.n2.gamma; q.b2[r] = bb.n2.beta; q.g3[r] = bb.n3.gamma; q.b3[r] = bb.n3.beta;
+                q.eps1[r] = 1e-5f * bb.c1.fold * bb.c1.fold; q.eps2[r] = 1e-5f * bb.c2.fold * bb.c2.fold; q.eps3[r] = 1e-5f * bb.c3.fold * bb.c3.fold;
+            }
+        };
         for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
             if (t.gn && gn_stop >= 0 && (int)bi >= gn_stop) dry = true;
             // GroupNorm trunk, 8 x 8 maps, 512 / 128 channels, 16 groups per trunk (the depth encoder's layer3 at 256-pixel frames): the run of
@@ -403,12 +419,7 @@ struct Fwd {
                     if (!dry) {
                         DepthL3 q;
                         q.x = x.p; q.y = slot[fo]; q.ld = x.C; q.B = B; q.groups = t.blocks[bi].c1.groups; q.nblocks = (int)run;
-                        for (size_t r = 0; r < run; ++r) {
-                            const BottleneckW& bb = t.blocks[bi + r];
-                            q.w1[r] = bb.c1.w; q.w2[r] = bb.c2.w; q.w3[r] = bb.c3.w;
-                            q.g1[r] = bb.n1.gamma; q.b1[r] = bb.n1.beta; q.g2[r] = bb.n2.gamma; q.b2[r] = bb.n2.beta; q.g3[r] = bb.n3.gamma; q.b3[r] = bb.n3.beta;
-                            q.eps1[r] = 1e-5f * bb.c1.fold * bb.c1.fold; q.eps2[r] = 1e-5f * bb.c2.fold * bb.c2.fold; q.eps3[r] = 1e-5f * bb.c3.fold * bb.c3.fold;
-                        }
+                        fill_run(q, bi, run);
                         ck(launch_depth_l3(q, t.blocks[bi].c1.dt, s), "depth layer3 run");
                         calib_check(slot[fo], t.blocks[bi].c1.dt, B * 64, x.C, x.C);
                     }
@@ -416,7 +427,7 @@ struct Fwd {
                     xi = fo;
                     bidx += (int)run;
                     bi += run - 1;
-                    if (bidx == 13) { tap(tapname + "_layer3", x.p, true, {B, x.H, x.W, x.C}); mark(tapname + ".layer3_end"); }
+                    layer_end(3, 3);
                     continue;
                 }
             }
@@ -442,12 +453,7 @@ struct Fwd {
                     if (!dry) {
                         DepthBlk q;
                         q.x = x.p; q.y = slot[fo]; q.ld = x.C; q.B = B; q.groups = t.blocks[bi].c1.groups; q.nblocks = (int)run; q.side = x.H; q.C = Cb; q.CM = Cm;
-                        for (size_t r = 0; r < run; ++r) {
-                            const BottleneckW& bb = t.blocks[bi + r];
-                            q.w1[r] = bb.c1.w; q.w2[r] = bb.c2.w; q.w3[r] = bb.c3.w;
-                            q.g1[r] = bb.n1.gamma; q.b1[r] = bb.n1.beta; q.g2[r] = bb.n2.gamma; q.b2[r] = bb.n2.beta; q.g3[r] = bb.n3.gamma; q.b3[r] = bb.n3.beta;
-                            q.eps1[r] = 1e-5f * bb.c1.fold * bb.c1.fold; q.eps2[r] = 1e-5f * bb.c2.fold * bb.c2.fold; q.eps3[r] = 1e-5f * bb.c3.fold * bb.c3.fold;
-                        }
+                        fill_run(q, bi, run);
                         ck(launch_depth_blk(q, t.blocks[bi].c1.dt, s), "depth layer1/2 run");
                         calib_check(slot[fo], t.blocks[bi].c1.dt, B * x.H * x.W, x.C, x.C);
                     }
@@ -455,7 +461,7 @@ struct Fwd {
                     xi = fo;
                     bidx += (int)run;
                     bi += run - 1;
-                    if (bidx == 3 || bidx == 7) mark(tapname + ".layer" + std::to_string(bidx == 3 ? 1 : 2) + "_end");
+                    layer_end(1, 2, false);
                     continue;
                 }
             }
@@ -493,15 +499,14 @@ struct Fwd {
             const BottleneckW* nb = bi + 1 < t.blocks.size() ? &t.blocks[bi + 1] : nullptr;
             static const int next_only = dev_env("HCM_BNECK_NEXT_ONLY") ? atoi(dev_env("HCM_BNECK_NEXT_ONLY")) : 0;   // A/B aid: 64 or 128 = only blocks with that many mid channels
             const bool next = nb && !no_next && (!next_only || next_only == b.c2.Cout) && nb->c1.KH == 1 && nb->c1.KW == 1 && nb->c1.Cin == b.c3.Cout && nb->c1.Kp == nb->c1.Cin &&
-                              nb->c1.bias && nb->c1.groups == b.c2.groups && nb->c1.dt == b.c2.dt &&
-                              ((nb->c1.Cout == b.c2.Cout && (nb->c1.Cout == 64 || nb->c1.Cout == 128 || nb->c1.Cout == 256)) || (b.c2.Cout == 64 && nb->c1.Cout == 128) ||
-                               (b.c2.Cout == 128 && nb->c1.Cout == 256 && !no_next256));
+                              nb->c1.bias && nb->c1.groups == b.c2.groups && nb->c1.dt == b.c2.dt && bneck23_ok(b.c2.dt, b.c2.Cout, nb->c1.Cout, 0) &&
+                              !(b.c2.Cout == 128 && nb->c1.Cout == 256 && no_next256);
             // (256 mid channels -- layer3: only the "tail + next block's reduction" form exists, so the layer's last block stays a launch per conv)
             // ... and only when its 128-pixel tiles fill the chip (one 149 KB workgroup per CU: a tile's ~70 us are a latency chain that a small grid
             // cannot hide -- B = 16: 69 us fused vs 34 us as three launches; B = 64: 83 vs 111)
             const long tiles256 = (long)b.c2.groups * (((long)B * ((x.H + 2 - 3) / b.stride + 1) * ((x.W + 2 - 3) / b.stride + 1) + 127) / 128);
-            const bool c1_ok = b.c2.Cout == 64 || b.c2.Cout == 128 || (b.c2.Cout == 256 && next && !no_256 && (tiles256 >= 192 || force_256));
-            if (!t.gn && !no_tail && (b.c2.dt == DT_BF16 || b.c2.dt == DT_F16) && c1_ok && b.c2.KH == 3 &&
+            const bool c1_ok = bneck23_ok(b.c2.dt, b.c2.Cout, next ? nb->c1.Cout : 0, 0) && (b.c2.Cout != 256 || (!no_256 && (tiles256 >= 192 || force_256)));
+            if (!t.gn && !no_tail && c1_ok && b.c2.KH == 3 &&
                 b.c2.Cin == b.c2.Cout && b.c2.Kp == 9 * b.c2.Cin && b.c3.Cout == 4 * b.c2.Cout && b.c3.Kp == b.c2.Cout && b.c2.bias && b.c3.bias &&
                 b.c3.groups == b.c2.groups) {
                 const void* idt = x.p;
@@ -512,8 +517,8 @@ struct Fwd {
                 // ... and layer2's (256 -> 512, stride 2) as 256 more (HCM_NO_BNECK_DSFOLD128=1, development build: that one as its own launch)
                 static const bool no_dsfold128 = dev_env("HCM_NO_BNECK_DSFOLD128") != nullptr;
                 const int dsC = b.has_ds ? b.ds.Cin : 0;
-                const bool dsfold = b.has_ds && !no_dsfold && next && b.c3ds.w && nb->c1.Cout == b.c2.Cout &&
-                                    ((b.c2.Cout == 64 && dsC == 64) || (b.c2.Cout == 128 && dsC == 256 && !no_dsfold128)) &&
+                const bool dsfold = b.has_ds && !no_dsfold && next && b.c3ds.w && dsC % 64 == 0 && bneck23_ok(b.c2.dt, b.c2.Cout, nb->c1.Cout, dsC / 64) &&
+                                    !(b.c2.Cout == 128 && no_dsfold128) &&
                                     b.c3ds.Kp == b.c2.Cout + dsC && b.c3ds.groups == b.c2.groups && x.C == b.c2.groups * dsC;
                 if (b.has_ds && !dsfold) {
                     conv(b.ds, x, sb, b.stride, 0, nullptr, ACT_NONE, Ho2, Wo2);
@@ -547,10 +552,7 @@ struct Fwd {
                 x = Act{sc, B, Ho2, Wo2, CO(b.c3)};
                 xi = fr[2];
                 ++bidx;
-                if (bidx == 3 || bidx == 7 || bidx == 13 || bidx == 16) {
-                    tap(tapname + "_layer" + std::to_string(bidx == 3 ? 1 : bidx == 7 ? 2 : bidx == 13 ? 3 : 4), x.p, true, {B, x.H, x.W, x.C});
-                    mark(tapname + ".layer" + std::to_string(bidx == 3 ? 1 : bidx == 7 ? 2 : bidx == 13 ? 3 : 4) + "_end");
-                }
+                layer_end();
                 continue;
             }
             Act o2{sb, B, Ho2, Wo2, CO(b.c2)};
@@ -585,10 +587,7 @@ struct Fwd {
             x = Act{sc, B, Ho2, Wo2, CO(b.c3)};
             xi = fr[2];
             ++bidx;
-            if (bidx == 3 || bidx == 7 || bidx == 13 || bidx == 16) {
-                tap(tapname + "_layer" + std::to_string(bidx == 3 ? 1 : bidx == 7 ? 2 : bidx == 13 ? 3 : 4), x.p, true, {B, x.H, x.W, x.C});
-                mark(tapname + ".layer" + std::to_string(bidx == 3 ? 1 : bidx == 7 ? 2 : bidx == 13 ? 3 : 4) + "_end");
-            }
+            layer_end();
         }
         flush(xpend);
         if (t.gn) {

@@ -1761,6 +1761,38 @@ __global__ __launch_bounds__(64 * NW) void igemm_dma_kernel(IGemmDev p) {
 // full write + read of the M x C1 tensor per block, and one launch).  Phase B multiplies that tile with the expansion weights, 128
 // output channels at a time (weights streamed by LDS-DMA, the next slice requested while the current one's epilogue runs),
 // through the shared epilogue in two row slabs.  Same MFMA instruction and k order as the two stand-alone launches: bit-identical.
+//
+// Dynamic LDS of the three bottleneck kernels, used by the kernel (offsets) and by launch_bneck23 (bytes to ask for).  Phase A's ring of whole
+// tap tiles -- or the halo block + weight-unit ring -- and the phase-B regions live in the SAME bytes, one after the other in time: a launch asks
+// for the larger of the two.
+template <int BM, int C1> struct Bneck23Layout {
+    static constexpr int TILE_BYTES = (BM + C1) * 128;                     // phase A: a tap tile of the pixels + one of the 3x3 weights
+    static constexpr int T_BYTES = C1 / 64 * BM * 128;                     // phase B: the parked mid tile,
+    static constexpr int W3_BYTES = C1 / 64 * 128 * 128;                   //   a 128-channel slice of the expansion weights,
+    static constexpr int IMG_BYTES = BM / 2 * (128 + 4) * 4;               //   the shared epilogue's f32 image of one of its two row slabs
+    static constexpr int phase_b_bytes = T_BYTES + W3_BYTES + IMG_BYTES, ring_bytes = 3 * TILE_BYTES;
+};
+// bneck231r_kernel (IMAGE = false) and bneck231_kernel (IMAGE = true: the shared epilogue's f32 image slab between the expansion-weight slice and the
+// slice block, one buffer for the reduction's weight slice, biases read from global memory)
+template <int BM, int C1, int CN, int KD, int W1B, bool IMAGE = false> struct Bneck231Layout {
+    static constexpr int KT1 = C1 / 64, KTB = KT1 + KD;                    // K blocks of phase B: the parked mid tile, then the down-sample input
+    static constexpr int TILE_BYTES = Bneck23Layout<BM, C1>::TILE_BYTES;   // phase A's ring of tap tiles is the same in all three kernels
+    static constexpr int T_BYTES = KTB * BM * 128, W3_BYTES = KTB * 64 * 128;      // parked operand blocks; a 64-channel slice of the expansion weights
+    static constexpr int IMG_OFF = T_BYTES + W3_BYTES;
+    static constexpr int IMG_BYTES = IMAGE ? 64 * (128 + 4) * 4 / 2 + 1024 : 0;     // >= 64 x (64+4) f32 and >= the reduction's slabs
+    static constexpr int YS_OFF = IMG_OFF + IMG_BYTES, YS_BYTES = BM * 128;        // the slice block: the reduction's MFMA operand
+    static constexpr int W1_OFF = YS_OFF + YS_BYTES, W1_BYTES = CN * 128;          // W1B buffers for the reduction's weight slice
+    static constexpr int BIAS_OFF = W1_OFF + W1B * W1_BYTES;                       // f32: the expansion's 4 * C1 biases, then the reduction's CN
+    static constexpr int BIAS_BYTES = IMAGE ? 0 : (4 * C1 + CN) * 4;
+    static constexpr int phase_b_bytes = BIAS_OFF + BIAS_BYTES, ring_bytes = 3 * TILE_BYTES;
+    // halo phase A on a W-wide map: BM / W + 2 rows of W + 2 pixels, padded to a multiple of 8 LDS rows of 128 B per 64-channel block (HRP in the
+    // kernel), then the ring of 8 KB weight units
+    static constexpr int HALO_UNIT_BYTES = 8192;
+    static constexpr int halo_rows(int W) { return ((BM / W + 2) * (W + 2) + 7) & ~7; }
+    static constexpr int halo_block_bytes(int rows) { return KT1 * rows * 128; }               // (rows = halo_rows(W), W <= BM <= 128: far inside an int)
+    static constexpr size_t halo_bytes(int W, int ring_depth) { return (size_t)halo_block_bytes(halo_rows(W)) + (size_t)ring_depth * HALO_UNIT_BYTES; }
+};
+
 struct BneckDev {
     IGemmDev a;                  // phase A: x, w (3x3), bias, geometry, M, N = C1, K = Kp = 9*C1, groups / g_x / g_w / g_b
     const char* w3; const float* b3; const char* res; char* y;
@@ -1776,10 +1808,10 @@ __global__ __launch_bounds__(512) void bneck23_kernel(BneckDev q) {
     constexpr int TN1 = C1 / WNc / 16;             // phase A: C1 / 4 channels per wave
     constexpr int TN2 = 128 / WNc / 16;            // phase B: 32 of the slice's 128 channels per wave
     constexpr int A_IT = BM / 8 / NW, B_IT = C1 / 8 / NW;
-    constexpr int TILE_BYTES = (BM + C1) * 128;
+    using L = Bneck23Layout<BM, C1>;
+    constexpr int TILE_BYTES = L::TILE_BYTES, T_BYTES = L::T_BYTES, W3_BYTES = L::W3_BYTES;
     constexpr int KT1 = C1 / BK;                   // K tiles of phase B
     constexpr int NT = 4 * C1 / 128;               // 128-channel output slices
-    constexpr int T_BYTES = KT1 * BM * 128, W3_BYTES = KT1 * 128 * 128;
     constexpr int E_RPP = 64 * NW / (128 / 8), E_NP = BM / E_RPP;
     static_assert(A_IT >= 1 && B_IT >= 1 && TN1 >= 1 && sizeof(T) == 2, "bneck23 tile");
 
@@ -2010,16 +2042,13 @@ __global__ __launch_bounds__(512, 4) void bneck231_kernel(Bneck231Dev qq) {     
     constexpr int TN2 = SW / WNc / 16;             // 1: 16 of the slice's 64 channels per wave
     constexpr int TN3 = CN / WNc / 16;             // reduction output: CN / 4 channels per wave
     constexpr int A_IT = BM / 8 / NW, B_IT = C1 / 8 / NW;
-    constexpr int TILE_BYTES = (BM + C1) * 128;
+    using L = Bneck231Layout<BM, C1, CN, KD, 1, true>;
+    constexpr int TILE_BYTES = L::TILE_BYTES, T_BYTES = L::T_BYTES, IMG_OFF = L::IMG_OFF, IMG_BYTES = L::IMG_BYTES, YS_OFF = L::YS_OFF, W1_OFF = L::W1_OFF;
     constexpr int KT1 = C1 / BK;
     constexpr int NT = 4 * C1 / SW;
     constexpr int KTB = KT1 + KD;                  // K blocks of phase B: the parked tile, then the down-sample input
-    constexpr int T_BYTES = KTB * BM * 128, W3_BYTES = KTB * SW * 128;
     constexpr int E_RPP = 64 * NW / (SW / 8), E_NP = BM / E_RPP;          // 64 rows per pass
     constexpr int ESPLIT = BM / E_RPP;                                     // image slab = one pass = 64 rows
-    constexpr int IMG_BYTES = 64 * (128 + 4) * 4 / 2 + 1024;               // >= 64 x (64+4) f32 and >= the reduction's slabs
-    constexpr int YS_OFF = T_BYTES + W3_BYTES + IMG_BYTES, YS_BYTES = BM * 128;
-    constexpr int W1_OFF = YS_OFF + YS_BYTES;
     constexpr int R_RPP = 64 * NW / (CN / 8), R_SPLIT = BM / R_RPP;        // reduction epilogue: image slabs of one pass
     static_assert(A_IT >= 1 && B_IT >= 1 && TN1 >= 1 && TN3 >= 1 && sizeof(T) == 2, "bneck231 tile");
     static_assert(R_RPP * (CN + 4) * 4 <= IMG_BYTES && 64 * (SW + 4) * 4 <= IMG_BYTES, "image slab");
@@ -2240,7 +2269,7 @@ __global__ __launch_bounds__(512, 4) void bneck231_kernel(Bneck231Dev qq) {     
             }
         }
         // epilogue of the slice: to HBM and, rounded, into the slice block (its first barrier also says: every wave is done with the weights)
-        igemm_epilogue_split<T, BM, SW, NW, WMc, E_NP, ESPLIT>(pe, acc2, smem + T_BYTES + W3_BYTES, m0, nt * SW, tid, wm, wn, fr, fg, rpre[nt], KD == 0,
+        igemm_epilogue_split<T, BM, SW, NW, WMc, E_NP, ESPLIT>(pe, acc2, smem + IMG_OFF, m0, nt * SW, tid, wm, wn, fr, fg, rpre[nt], KD == 0,
                                                                smem + YS_OFF);
         if (nt + 1 < NT) stage_w3(nt + 1);                 // (after the epilogue's barriers: the expansion weights are dead)
         __syncthreads();                                   // slice block complete
@@ -2278,7 +2307,7 @@ __global__ __launch_bounds__(512, 4) void bneck231_kernel(Bneck231Dev qq) {     
     pr.act = ACT_RELU; pr.out_f32 = 0; pr.gn_cg = 0;
     __syncthreads();
     const uint4 none[1] = {make_uint4(0u, 0u, 0u, 0u)};
-    igemm_epilogue_split<T, BM, CN, NW, WMc, 1, R_SPLIT>(pr, acc3, smem + T_BYTES + W3_BYTES, m0, 0, tid, wm, wn, fr, fg, none, false);
+    igemm_epilogue_split<T, BM, CN, NW, WMc, 1, R_SPLIT>(pr, acc3, smem + IMG_OFF, m0, 0, tid, wm, wn, fr, fg, none, false);
 }
 
 // bneck231_kernel with REGISTER epilogues (round 3).  The f32 LDS image of the shared epilogue -- write the accumulators, barrier, read
@@ -2338,14 +2367,11 @@ __global__ __launch_bounds__(512, (C1 >= 256 || (BM == 128 && C1 == 128)) ? 2 : 
     constexpr int TN2 = SW / WN2 / 16;             // 2: one pair
     constexpr int TN3 = CN / WN2 / 16;             // 2, 4 or 8: one, two or four pairs
     constexpr int A_IT = BM / 8 / NW, B_IT = C1 / 8 / NW;
-    constexpr int TILE_BYTES = (BM + C1) * 128;
+    using L = Bneck231Layout<BM, C1, CN, KD, W1B>;
+    constexpr int TILE_BYTES = L::TILE_BYTES, T_BYTES = L::T_BYTES, YS_OFF = L::YS_OFF, W1_OFF = L::W1_OFF, W1_BYTES = L::W1_BYTES, BIAS_OFF = L::BIAS_OFF;
     constexpr int KT1 = C1 / BK;
     constexpr int NT = 4 * C1 / SW;
     constexpr int KTB = KT1 + KD;
-    constexpr int T_BYTES = KTB * BM * 128, W3_BYTES = KTB * SW * 128;
-    constexpr int YS_OFF = T_BYTES + W3_BYTES, YS_BYTES = BM * 128;
-    constexpr int W1_OFF = YS_OFF + YS_BYTES, W1_BYTES = CN * 128;      // two buffers
-    constexpr int BIAS_OFF = W1_OFF + W1B * W1_BYTES;                   // f32: the expansion's 4 * C1 biases, then the reduction's CN
     static_assert(A_IT >= 1 && B_IT >= 1 && TN1 >= 1 && TMB >= 1 && TN2 == 2 && TN3 % 2 == 0 && sizeof(T) == 2, "bneck231r tile");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2501,14 +2527,14 @@ __global__ __launch_bounds__(512, (C1 >= 256 || (BM == 128 && C1 == 128)) ? 2 : 
         constexpr int UK = C1 == 64 ? 64 : 32;               // k per unit
         constexpr int UPT = C1 / UK;                         // units per tap: 1 / 4
         constexpr int NK = 9 * UPT, D = NWB - 1, NID = (KD == 0 && !ID_STREAM) ? NT * TMB : 0;
-        static_assert(NWB >= 2 && (C1 == 64 || C1 == 128) && C1 * UK * 2 == 8192, "halo phase A: 8 KB weight units");
+        static_assert(NWB >= 2 && (C1 == 64 || C1 == 128) && C1 * UK * 2 == L::HALO_UNIT_BYTES, "halo phase A: 8 KB weight units");
         constexpr int ND0 = D < NK ? D : NK;                 // weight units requested with the halo block
         constexpr int ID_AT = NK - 1 - D;                    // the iteration that requests the last weight unit (< 0: all went out up front)
         // halo geometry: the tile is R whole rows of one image's W-wide map; halo rows hy = 0 .. R + 1 <-> input rows oy0 - 1 + hy, columns
         // hx = 0 .. W + 1 <-> input columns hx - 1; HRP (a multiple of 8) LDS rows of 128 B per 64-channel block
-        const int Wm = p.W, Wp = Wm + 2, R = BM / Wm, HR = (R + 2) * Wp, HRP = (HR + 7) & ~7;
+        const int Wm = p.W, Wp = Wm + 2, R = BM / Wm, HR = (R + 2) * Wp, HRP = L::halo_rows(Wm);
         const int img = m0 / HoWo, oy0 = (m0 - img * HoWo) / Wm, pix0 = img * p.H * p.W;
-        const unsigned WR_OFF = (unsigned)(KT1 * HRP * 128);
+        const unsigned WR_OFF = (unsigned)L::halo_block_bytes(HRP);
         {
             const int n_instr = KT1 * HRP / 8;
             for (int i = wave; i < n_instr; i += NW) {
@@ -2527,12 +2553,12 @@ __global__ __launch_bounds__(512, (C1 >= 256 || (BM == 128 && C1 == 128)) ? 2 : 
             if constexpr (C1 == 64) {
                 const int n = wave * 8 + rin;
                 const unsigned off = (unsigned)(n * p.Kp + u * BK + c * CH) * 2u;
-                dma16(__builtin_amdgcn_readfirstlane(lds_base + WR_OFF + slot * 8192 + wave * 1024), off, rw);
+                dma16(__builtin_amdgcn_readfirstlane(lds_base + WR_OFF + slot * L::HALO_UNIT_BYTES + wave * 1024), off, rw);
             } else {
                 const int row = lane >> 2, n = wave * 16 + row;
                 const int src = (lane & 3) ^ ((4 - (row >> 2)) & 3);
                 const unsigned off = (unsigned)(n * p.Kp + u * UK + src * CH) * 2u;
-                dma16(__builtin_amdgcn_readfirstlane(lds_base + WR_OFF + slot * 8192 + wave * 1024), off, rw);
+                dma16(__builtin_amdgcn_readfirstlane(lds_base + WR_OFF + slot * L::HALO_UNIT_BYTES + wave * 1024), off, rw);
             }
         };
         int hr0[TM];
@@ -2546,7 +2572,7 @@ __global__ __launch_bounds__(512, (C1 >= 256 || (BM == 128 && C1 == 128)) ? 2 : 
             constexpr int u = decltype(U)::value;
             constexpr int tap = u / UPT, kh = tap / 3, kw = tap - kh * 3;
             const int dhr = kh * Wp + kw;
-            const char* sb = smem + WR_OFF + (u % NWB) * 8192;
+            const char* sb = smem + WR_OFF + (u % NWB) * L::HALO_UNIT_BYTES;
             if constexpr (C1 == 64) {
                 const char* sa = smem;
 #pragma unroll
@@ -3405,18 +3431,129 @@ hipError_t launch_igemm(const IGemm& g, int dt, hipStream_t s) {
 
 
 constexpr int kHaloRing = 5, kHaloRingD = 5;       // weight-tile ring depth of the halo phase A (128-pixel tiles / the 64-pixel tile of the folded down-sample block)
+// Dynamic LDS a launch form may ask for.  A CU has 160 KB: up to 80 KB, two workgroups share it (the forms built with 4 waves per SIMD count on that)
+constexpr size_t kLdsOnePerCu = 160 * 1024, kLdsTwoPerCu = kLdsOnePerCu / 2;
+// ... and the halo forms on 128-pixel tiles of 128 mid channels, one workgroup per CU either way, take maps up to this much halo block + weight ring:
+constexpr size_t kLdsBm128Cn128 = 96 * 1024;       // CN = 128 (84 KB of phase-B regions): W <= 32 (92 KB)
+constexpr size_t kLdsBm128Cn256 = 112 * 1024;      // CN = 256 (99 KB of phase-B regions): W <= 64 (106 KB)
+
+// Which (mid channels, next reduction's channels, folded down-sample K blocks) the bottleneck kernels are built for; CN = 0: no next reduction,
+// KD = 0: identity rows instead of a folded down-sample conv.  The one list: launch_bneck23 validates with it, Fwd::trunk plans with it.
+bool bneck23_ok(int dt, int C1, int CN, int KD) {
+    if (dt != DT_BF16 && dt != DT_F16) return false;
+    if (KD) return (C1 == 64 && CN == 64 && KD == 1) || (C1 == 128 && CN == 128 && KD == 4);       // layer1 / layer2 block 0
+    if (C1 == 64) return CN == 0 || CN == 64 || CN == 128;
+    if (C1 == 128) return CN == 0 || CN == 128 || CN == 256;
+    return C1 == 256 && CN == 256;             // 256 mid channels: only the tail + next-reduction form is built
+}
+
+// A launch form: the kernel for the dtype, the dynamic LDS it needs and its grid of BM-pixel tiles (xcd_tiles: see Bneck231Dev)
+struct BneckForm { const void* fn; size_t lds; dim3 grid; int xcd_tiles; };
+
+template <int BM, int C1> static BneckForm form23(int dt, const IGemmDev& d) {
+    using L = Bneck23Layout<BM, C1>;
+    static_assert(L::phase_b_bytes <= kLdsOnePerCu && L::ring_bytes <= kLdsOnePerCu, "bneck23 LDS");
+    return {dt == DT_BF16 ? reinterpret_cast<const void*>(bneck23_kernel<bf16, BM, C1>) : reinterpret_cast<const void*>(bneck23_kernel<f16, BM, C1>),
+            (size_t)std::max(L::phase_b_bytes, L::ring_bytes), dim3((d.M + BM - 1) / BM, d.groups), 0};
+}
+template <int BM, int C1, int CN, int KD = 0> static BneckForm form231(int dt, const IGemmDev& d) {      // the LDS-image form
+    using L = Bneck231Layout<BM, C1, CN, KD, 1, true>;
+    static_assert(L::phase_b_bytes <= kLdsOnePerCu && L::ring_bytes <= kLdsOnePerCu, "bneck231 LDS");
+    return {dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231_kernel<bf16, BM, C1, CN, KD>) : reinterpret_cast<const void*>(bneck231_kernel<f16, BM, C1, CN, KD>),
+            (size_t)std::max(L::phase_b_bytes, L::ring_bytes), dim3((d.M + BM - 1) / BM, d.groups), 0};
+}
+// the register-epilogue form.  NWB = 0: phase A's 3-deep ring of whole tap tiles; NWB > 0: the halo block of the W-wide map + NWB weight units (the
+// caller has checked halo_tile_ok and compares .lds with the form's ceiling).  PROF (development build): the phase-timed kernel, built for f16 only
+template <int BM, int C1, int CN, int KD = 0, int NWB = 0, int W1B = 2, bool PROF = false> static BneckForm form231r(int dt, const IGemmDev& d) {
+    using L = Bneck231Layout<BM, C1, CN, KD, W1B>;
+    static_assert(L::phase_b_bytes <= kLdsOnePerCu && L::ring_bytes <= kLdsOnePerCu, "bneck231r LDS");
+    const void* fn = reinterpret_cast<const void*>(bneck231r_kernel<f16, BM, C1, CN, KD, PROF, NWB, W1B>);
+    if constexpr (!PROF) if (dt == DT_BF16) fn = reinterpret_cast<const void*>(bneck231r_kernel<bf16, BM, C1, CN, KD, PROF, NWB, W1B>);
+    const size_t phase_a = NWB > 0 ? L::halo_bytes(d.W, NWB) : (size_t)L::ring_bytes;
+    return {fn, std::max((size_t)L::phase_b_bytes, phase_a), dim3((d.M + BM - 1) / BM, d.groups), 0};
+}
+// ... of a stage's ordinary blocks (C1 -> CN = C1, or a 64-channel stage's last block): the phase-timed kernel while HCM_IGEMM_PROF is on
+template <int BM, int C1, int CN, int NWB> static BneckForm form231r_plain(int dt, const IGemmDev& d) {
+#ifdef HCM_DEV_KNOBS
+    if constexpr (C1 == CN) if (prof_on() && dt == DT_F16) return form231r<BM, C1, CN, 0, NWB, 2, true>(dt, d);
+#endif
+    return form231r<BM, C1, CN, 0, NWB>(dt, d);
+}
+// halo phase A (see bneck231r_kernel) needs stride 1, W a multiple of 16 and BM-pixel tiles that are whole rows of one image
+static bool halo_tile_ok(const IGemmDev& d, int BM) { return d.stride == 1 && d.W % 16 == 0 && BM % d.W == 0 && (d.Ho * d.Wo) % BM == 0; }
+
+// The launch form of a validated bottleneck (bneck23_ok holds for C1 / CN / KD; CN = 0: no next reduction, KD = 0: no folded down-sample): the first rule that applies
+static BneckForm choose_bneck_form(int dt, int C1, int CN, int KD, const IGemmDev& d) {
+    // register-epilogue form (bneck231r_kernel, the default) or the LDS-image form (HCM_BNECK_IMAGE=1: A/B and the toggle test); bit-identical
+    static const bool image = dev_env("HCM_BNECK_IMAGE") != nullptr;
+    static const bool halo = dev_env("HCM_NO_BNECK_HALO") == nullptr;
+    static const bool ds128 = dev_env("HCM_NO_BNECK_DS128") == nullptr;
+    static const bool bm128 = dev_env("HCM_BNECK128_BM64") == nullptr;          // HCM_BNECK128_BM64=1 (development build): 128 mid channels on 64-pixel tiles only
+    static const bool xcd = dev_env("HCM_NO_BNECK_XCD") == nullptr;
+    // 128 mid channels on 128-pixel tiles, one workgroup per CU: only where that grid fills the chip
+    const bool fills128 = (long)d.groups * (d.M / 128) >= 192;
+    BneckForm f;
+    if (CN == 0) return C1 == 64 ? form23<128, 64>(dt, d) : form23<64, 128>(dt, d);
+    if (KD == 4)
+        // layer2 block 0 (256-channel block input, stride 2): the PARKED form -- the mid tile's two K blocks and the four gathered xd blocks (48 KB),
+        // a six-block expansion-weight slice (48 KB), the slice block, two reduction-weight buffers, biases: 138.5 KB, ONE 64-pixel workgroup per CU
+        // (phase A's classic ring lives in the same bytes before that; the halo form needs stride 1).  Register form only.
+        return form231r<64, 128, 128, 4>(dt, d);
+    if (KD == 1) {
+        // layer1 block 0
+        if (image) return form231<64, 64, 64, 1>(dt, d);
+        // 128-pixel tiles (one buffer for the reduction's weight slice, halo phase A) where the map allows: per-tile fixed costs halve
+        if (halo && ds128 && halo_tile_ok(d, 128) && (f = form231r<128, 64, 64, 1, kHaloRing, 1>(dt, d)).lds <= kLdsTwoPerCu) return f;
+        if (halo && halo_tile_ok(d, 64) && (f = form231r<64, 64, 64, 1, kHaloRingD>(dt, d)).lds <= kLdsTwoPerCu) return f;
+        return form231r<64, 64, 64, 1>(dt, d);
+    }
+    if (C1 == 256) {
+        // RGB layer3 (16 x 16 maps at 256-pixel frames): 128-pixel tiles, one workgroup per CU (149 KB: the parked 128 x 256 tile 64 KB, a 32 KB
+        // expansion-weight slice, the 16 KB slice block, ONE 32 KB buffer for the reduction's weight slice, 5 KB of biases; phase A's 3-deep ring
+        // of 48 KB tap tiles lives in the same bytes before that), identity rows streamed two slices deep (ID_STREAM)
+        f = form231r<128, 256, 256, 0, 0, 1>(dt, d);
+        if (d.groups == 2 && xcd) {             // the hi | lo pair split over the XCDs (see Bneck231Dev): a 1-D grid of 8 workgroups per 4 tiles
+            f.xcd_tiles = f.grid.x;
+            f.grid = dim3((f.xcd_tiles + 3) / 4 * 8, 1);
+        }
+        return f;
+    }
+    if (C1 == 128 && CN == 256) {
+        // the LAST block of a 128-mid-channel stage (RGB layer2) + the next stage's first reduction, 512 -> 256.  The reduction's weight slice is
+        // 32 KB, so ONE buffer for it whatever the tile (W1B = 1).  128-pixel tiles in one 99 KB workgroup per CU where the grid fills the chip, as
+        // for the stage's other blocks (round 4: a tile streams the block's weights from L2 whatever its size); else 64-pixel tiles, 75 KB, two per
+        // CU.  Register form only (HCM_BNECK_IMAGE does not apply).
+        if (halo && bm128 && fills128 && halo_tile_ok(d, 128) && (f = form231r<128, 128, 256, 0, kHaloRing, 1>(dt, d)).lds <= kLdsBm128Cn256) return f;
+        if (halo && halo_tile_ok(d, 64) && (f = form231r<64, 128, 256, 0, kHaloRing, 1>(dt, d)).lds <= kLdsTwoPerCu) return f;
+        return form231r<64, 128, 256, 0, 0, 1>(dt, d);
+    }
+    if (image) return C1 == 128 ? form231<64, 128, 128>(dt, d) : CN == 64 ? form231<128, 64, 64>(dt, d) : form231<128, 64, 128>(dt, d);
+    // round 4: 128 mid channels (layer2) on 128-PIXEL tiles, one 92 KB workgroup per CU instead of two 64-pixel ones.  A tile streams the block's
+    // 557 KB of weights (3x3 295 KB + expansion 131 KB + next reduction 131 KB) from L2 whatever its size: 2048 64-pixel tiles = 1.14 GB per launch
+    // (the pair at B = 64) against 0.39 GB of activations -- the launch was bound by that stream (134 us = 2.9 TB/s of HBM traffic, 0.28 of the
+    // matrix rate).
+    if (C1 == 128 && halo && bm128 && fills128 && halo_tile_ok(d, 128) && (f = form231r<128, 128, 128, 0, kHaloRing, 1>(dt, d)).lds <= kLdsBm128Cn128) return f;
+    // the stage's ordinary tile -- 64 pixels at 128 mid channels, 128 at 64 -- two workgroups per CU, with halo phase A where the map allows
+    // (the 3-deep ring of whole tap tiles is not used by that form: the phase-B regions or the halo block + weight ring decide)
+    if (halo && halo_tile_ok(d, C1 == 128 ? 64 : 128)) {
+        f = C1 == 128 ? form231r_plain<64, 128, 128, kHaloRing>(dt, d) : CN == 64 ? form231r_plain<128, 64, 64, kHaloRing>(dt, d) : form231r_plain<128, 64, 128, kHaloRing>(dt, d);
+        if (f.lds <= kLdsTwoPerCu) return f;
+    }
+    return C1 == 128 ? form231r_plain<64, 128, 128, 0>(dt, d) : CN == 64 ? form231r_plain<128, 64, 64, 0>(dt, d) : form231r_plain<128, 64, 128, 0>(dt, d);
+}
 
 hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s) {
-    if (dt != DT_BF16 && dt != DT_F16) return hipErrorInvalidValue;
-    if ((b.C1 != 64 && b.C1 != 128 && b.C1 != 256) || (!b.res && !b.xd) || !b.b2 || !b.b3 || b.stride < 1) return hipErrorInvalidValue;
-    if (b.C1 == 256 && (!b.w1 || b.CN != 256 || b.xd)) return hipErrorInvalidValue;        // 256 mid channels: only the tail + next-reduction form is built
-    if (b.xd && (!b.w1 || (b.xdC % 8) || !((b.C1 == 64 && b.KD == 1 && b.CN == 64) || (b.C1 == 128 && b.KD == 4 && b.CN == 128)))) return hipErrorInvalidValue;   // the two folded-down-sample shapes built
+    const int CN = b.w1 ? b.CN : 0, KD = b.xd ? b.KD : 0;
+    if (!bneck23_ok(dt, b.C1, CN, KD) || (!b.res && !b.xd) || !b.b2 || !b.b3 || b.stride < 1) return hipErrorInvalidValue;
+    if (b.xd && (b.KD < 1 || (b.xdC % 8))) return hipErrorInvalidValue;
+    if (b.w1 && (!b.b1 || !b.o1)) return hipErrorInvalidValue;
     const int C3 = 4 * b.C1;
-    const int ldy = b.ldy ? b.ldy : C3, ldr = b.ldr ? b.ldr : C3, xC = b.xC ? b.xC : b.C1;
-    if ((ldy % 8) || (ldr % 8) || (xC % 8)) return hipErrorInvalidValue;
-    BneckDev q;
+    const int ldy = b.ldy ? b.ldy : C3, ldr = b.ldr ? b.ldr : C3, xC = b.xC ? b.xC : b.C1, ldo = b.ldo ? b.ldo : b.CN;
+    if ((ldy % 8) || (ldr % 8) || (xC % 8) || (b.w1 && (ldo % 8))) return hipErrorInvalidValue;
+    Bneck231Dev qq;                    // (bneck23_kernel takes its first member alone)
+    BneckDev& q = qq.t;
     IGemmDev& d = q.a;
-    memset((void*)&q, 0, sizeof(q));
+    memset((void*)&qq, 0, sizeof(qq));
     d.x = (const char*)b.x; d.w = (const char*)b.w2; d.bias = b.b2;
     d.B = b.B; d.H = b.H; d.W = b.W; d.Cin = b.C1; d.xC = xC;
     d.Ho = (b.H + 2 - 3) / b.stride + 1; d.Wo = (b.W + 2 - 3) / b.stride + 1;
@@ -3426,222 +3563,25 @@ hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s) {
     d.kw_rcp = (65536 + 3 - 1) / 3;
     d.groups = b.groups > 1 ? b.groups : 1;
     d.g_x = b.g_x; d.g_w = b.g_w2; d.g_b = b.g_b2;
-    {
-        const size_t xb = (((size_t)d.B * d.H * d.W - 1) * d.xC + d.Cin) * 2, wb = (size_t)d.N * d.Kp * 2, w3b = (size_t)C3 * b.C1 * 2;
-        if (xb >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
-        d.x_bytes = (unsigned)xb; d.w_bytes = (unsigned)wb; q.w3_bytes = (unsigned)w3b;
-    }
+    const size_t xb = (((size_t)d.B * d.H * d.W - 1) * d.xC + d.Cin) * 2, xdb = (((size_t)d.B * d.H * d.W - 1) * b.xdC + KD * 64) * 2;
+    if (xb >= 0xFFFFFFF0ull || (b.xd && xdb >= 0xFFFFFFF0ull)) return hipErrorInvalidValue;
+    d.x_bytes = (unsigned)xb; d.w_bytes = (unsigned)((size_t)d.N * d.Kp * 2);
     q.w3 = (const char*)b.w3; q.b3 = b.b3; q.res = (const char*)b.res; q.y = (char*)b.y;
-    q.C3 = C3; q.Kp3 = b.C1 + (b.xd ? b.KD * 64 : 0); q.ldy3 = ldy; q.ldr3 = ldr;
+    q.C3 = C3; q.Kp3 = b.C1 + KD * 64; q.ldy3 = ldy; q.ldr3 = ldr;
     q.w3_bytes = (unsigned)((size_t)C3 * q.Kp3 * 2);
     q.g_w3 = b.g_w3; q.g_b3 = b.g_b3; q.g_y3 = b.g_y;
-    const int BM = b.C1 == 128 ? 64 : 128;
-    const int KT1 = b.C1 / 64;
     if (b.w1) {
-        if (!b.b1 || !b.o1 || (b.CN != 64 && b.CN != 128 && b.CN != 256) || (b.C1 == 128 && b.CN == 64) || (b.C1 == 64 && b.CN == 256) || (b.C1 == 256 && b.CN != 256)) return hipErrorInvalidValue;
-        const int ldo = b.ldo ? b.ldo : b.CN;
-        if (ldo % 8) return hipErrorInvalidValue;
-        Bneck231Dev qq;
-        qq.t = q;
         qq.w1 = (const char*)b.w1; qq.b1 = b.b1; qq.o1 = (char*)b.o1; qq.ldo = ldo;
         qq.w1_bytes = (unsigned)((size_t)b.CN * C3 * 2);
         qq.g_w1 = b.g_w1; qq.g_b1 = b.g_b1; qq.g_o1 = b.g_o1;
-        qq.xd = nullptr; qq.xdC = 0; qq.xd_bytes = 0; qq.g_xd = 0;
-        qq.xcd_tiles = 0;
-        if (b.xd) {
-            const size_t xdb = (((size_t)d.B * d.H * d.W - 1) * b.xdC + b.KD * 64) * 2;
-            if (xdb >= 0xFFFFFFF0ull) return hipErrorInvalidValue;
-            qq.xd = (const char*)b.xd; qq.xdC = b.xdC; qq.xd_bytes = (unsigned)xdb; qq.g_xd = b.g_xd;
-            if (b.C1 == 128) {
-                // layer2 block 0 (256-channel block input, stride 2): the PARKED form -- the mid tile's two K blocks and the four gathered xd blocks (48 KB),
-                // a six-block expansion-weight slice (48 KB), the slice block, two reduction-weight buffers, biases: 138.5 KB, ONE 64-pixel workgroup per CU
-                // (phase A's classic ring lives in the same bytes before that; the halo form needs stride 1).  Register form only.
-                const size_t lp = (size_t)2 * (2 + b.KD) * 64 * 128 + (size_t)64 * 128 + (size_t)2 * b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-                const size_t rp = 3 * (size_t)(64 + b.C1) * 128;
-                const size_t ldsp = lp > rp ? lp : rp;
-                if (ldsp > 160 * 1024) return hipErrorInvalidValue;
-                const void* fp = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 128, 4>)
-                                               : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 128, 4>);
-                hipError_t ep = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (ep != hipSuccess) return ep;
-                void* ap[] = {&qq};
-                return hipLaunchKernel(fp, dim3((d.M + 63) / 64, d.groups), dim3(512), ap, ldsp, s);
-            }
-            const int BMd = 64;
-            // register-epilogue form (bneck231r_kernel, the default) or the LDS-image form (HCM_BNECK_IMAGE=1: A/B and the toggle test); bit-identical
-            static const bool image_d = dev_env("HCM_BNECK_IMAGE") != nullptr;
-            size_t ldsd = image_d ? (size_t)2 * BMd * 128 + (size_t)2 * 64 * 128 + (64 * 132 * 4 / 2 + 1024) + (size_t)BMd * 128 + (size_t)b.CN * 128
-                                  : (size_t)2 * BMd * 128 + (size_t)2 * 64 * 128 + (size_t)BMd * 128 + (size_t)2 * b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-            const size_t ringd = 3 * (size_t)(BMd + b.C1) * 128;
-            if (ringd > ldsd) ldsd = ringd;
-            const void* fd = image_d ? (dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231_kernel<bf16, 64, 64, 64, 1>) : reinterpret_cast<const void*>(bneck231_kernel<f16, 64, 64, 64, 1>))
-                                     : (dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 64, 64, 1>) : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 64, 64, 1>));
-            // halo phase A (see bneck231r_kernel): a tile of whole rows of one image
-            static const bool no_halo_d = dev_env("HCM_NO_BNECK_HALO") != nullptr;
-            // 128-pixel tiles (one buffer for the reduction's weight slice, halo phase A) where the map allows: per-tile fixed costs halve
-            static const bool no_big_d = dev_env("HCM_NO_BNECK_DS128") != nullptr;
-            if (!image_d && !no_halo_d && !no_big_d && b.stride == 1 && d.W % 16 == 0 && 128 % d.W == 0 && (d.Ho * d.Wo) % 128 == 0) {
-                const size_t halo = (size_t)((((128 / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 64 * 128;
-                size_t lds = (size_t)2 * 128 * 128 + (size_t)2 * 64 * 128 + (size_t)128 * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-                if (halo > lds) lds = halo;
-                if (lds <= 80 * 1024) {
-                    const void* fb = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 64, 64, 1, false, kHaloRing, 1>)
-                                                   : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 64, 1, false, kHaloRing, 1>);
-                    hipError_t eb = hipFuncSetAttribute(fb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (eb != hipSuccess) return eb;
-                    void* ab[] = {&qq};
-                    return hipLaunchKernel(fb, dim3((d.M + 127) / 128, d.groups), dim3(512), ab, lds, s);
-                }
-            }
-            if (!image_d && !no_halo_d && b.stride == 1 && d.W % 16 == 0 && BMd % d.W == 0 && (d.Ho * d.Wo) % BMd == 0) {
-                const size_t halo = (size_t)((((BMd / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRingD * 64 * 128;
-                if (halo <= 80 * 1024) {
-                    ldsd = (size_t)2 * BMd * 128 + (size_t)2 * 64 * 128 + (size_t)BMd * 128 + (size_t)2 * b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-                    if (halo > ldsd) ldsd = halo;
-                    fd = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 64, 64, 1, false, kHaloRingD>)
-                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 64, 64, 1, false, kHaloRingD>);
-                }
-            }
-            hipError_t ed = hipFuncSetAttribute(fd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (ed != hipSuccess) return ed;
-            void* ad[] = {&qq};
-            return hipLaunchKernel(fd, dim3((d.M + BMd - 1) / BMd, d.groups), dim3(512), ad, ldsd, s);
-        }
-        if (b.C1 == 256) {
-            // RGB layer3 (16 x 16 maps at 256-pixel frames): 128-pixel tiles, one workgroup per CU (149 KB: the parked 128 x 256 tile 64 KB, a 32 KB
-            // expansion-weight slice, the 16 KB slice block, ONE 32 KB buffer for the reduction's weight slice, 5 KB of biases; phase A's 3-deep ring
-            // of 48 KB tap tiles lives in the same bytes before that), identity rows streamed two slices deep (ID_STREAM)
-            const size_t lb = (size_t)KT1 * BM * 128 + (size_t)KT1 * 64 * 128 + (size_t)BM * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-            const size_t ra = 3 * (size_t)(BM + b.C1) * 128;
-            const size_t lds256 = lb > ra ? lb : ra;
-            if (lds256 > 160 * 1024) return hipErrorInvalidValue;
-            const void* f2 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 256, 256, 0, false, 0, 1>)
-                                           : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 256, 256, 0, false, 0, 1>);
-            hipError_t e2 = hipFuncSetAttribute(f2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e2 != hipSuccess) return e2;
-            void* a2[] = {&qq};
-            static const bool no_xcd = dev_env("HCM_NO_BNECK_XCD") != nullptr;
-            if (d.groups == 2 && !no_xcd) {
-                const int tiles = (d.M + BM - 1) / BM;
-                qq.xcd_tiles = tiles;
-                return hipLaunchKernel(f2, dim3(((tiles + 3) / 4) * 8, 1), dim3(512), a2, lds256, s);
-            }
-            return hipLaunchKernel(f2, dim3((d.M + BM - 1) / BM, d.groups), dim3(512), a2, lds256, s);
-        }
-        if (b.C1 == 128 && b.CN == 256) {
-            // the LAST block of a 128-mid-channel stage (RGB layer2) + the next stage's first reduction, 512 -> 256.  The reduction's weight slice is
-            // 32 KB, so ONE buffer for it whatever the tile (W1B = 1).  128-pixel tiles in one 99 KB workgroup per CU where the grid fills the chip, as
-            // for the stage's other blocks (round 4: a tile streams the block's weights from L2 whatever its size); else 64-pixel tiles, 75 KB, two per
-            // CU.  Register form only (HCM_BNECK_IMAGE does not apply).  HCM_BNECK128_BM64=1 (development build): the 64-pixel tiles.
-            static const bool no_halo2 = dev_env("HCM_NO_BNECK_HALO") != nullptr;
-            static const bool bm64_2 = dev_env("HCM_BNECK128_BM64") != nullptr;
-            const void* f3 = nullptr;
-            size_t lds3 = 0;
-            int BM3 = 64;
-            if (!no_halo2 && !bm64_2 && b.stride == 1 && d.W % 16 == 0 && 128 % d.W == 0 && (d.Ho * d.Wo) % 128 == 0 && (long)d.groups * (d.M / 128) >= 192) {
-                const size_t halo = (size_t)KT1 * ((((128 / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 8192;
-                size_t lds = (size_t)KT1 * 128 * 128 + (size_t)KT1 * 64 * 128 + (size_t)128 * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-                if (halo > lds) lds = halo;
-                if (lds <= 112 * 1024) {
-                    BM3 = 128; lds3 = lds;
-                    f3 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 128, 256, 0, false, kHaloRing, 1>)
-                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 128, 256, 0, false, kHaloRing, 1>);
-                }
-            }
-            if (!f3) {
-                lds3 = (size_t)KT1 * 64 * 128 + (size_t)KT1 * 64 * 128 + (size_t)64 * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-                const size_t halo = (size_t)KT1 * ((((64 / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 8192;
-                if (!no_halo2 && b.stride == 1 && d.W % 16 == 0 && 64 % d.W == 0 && (d.Ho * d.Wo) % 64 == 0 && halo <= 80 * 1024) {
-                    if (halo > lds3) lds3 = halo;
-                    f3 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 256, 0, false, kHaloRing, 1>)
-                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 256, 0, false, kHaloRing, 1>);
-                } else {
-                    const size_t ring3 = 3 * (size_t)(64 + b.C1) * 128;
-                    if (ring3 > lds3) lds3 = ring3;
-                    f3 = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 256, 0, false, 0, 1>)
-                                       : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 256, 0, false, 0, 1>);
-                }
-            }
-            hipError_t e3 = hipFuncSetAttribute(f3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e3 != hipSuccess) return e3;
-            void* a3[] = {&qq};
-            return hipLaunchKernel(f3, dim3((d.M + BM3 - 1) / BM3, d.groups), dim3(512), a3, lds3, s);
-        }
-        static const bool image = dev_env("HCM_BNECK_IMAGE") != nullptr;
-        size_t lds1 = image ? (size_t)KT1 * BM * 128 + (size_t)KT1 * 64 * 128 + (64 * 132 * 4 / 2 + 1024) + (size_t)BM * 128 + (size_t)b.CN * 128
-                            : (size_t)KT1 * BM * 128 + (size_t)KT1 * 64 * 128 + (size_t)BM * 128 + (size_t)2 * b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-        const size_t ring1 = 3 * (size_t)(BM + b.C1) * 128;
-        if (ring1 > lds1) lds1 = ring1;
-        const void* f1;
-        if (image) {
-            if (dt == DT_BF16) f1 = b.C1 == 128 ? reinterpret_cast<const void*>(bneck231_kernel<bf16, 64, 128, 128>)
-                                  : b.CN == 64 ? reinterpret_cast<const void*>(bneck231_kernel<bf16, 128, 64, 64>) : reinterpret_cast<const void*>(bneck231_kernel<bf16, 128, 64, 128>);
-            else f1 = b.C1 == 128 ? reinterpret_cast<const void*>(bneck231_kernel<f16, 64, 128, 128>)
-                    : b.CN == 64 ? reinterpret_cast<const void*>(bneck231_kernel<f16, 128, 64, 64>) : reinterpret_cast<const void*>(bneck231_kernel<f16, 128, 64, 128>);
-        } else {
-            if (dt == DT_BF16) f1 = b.C1 == 128 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 128>)
-                                  : b.CN == 64 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 64, 64>) : reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 64, 128>);
-            else f1 = b.C1 == 128 ? reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 128>)
-                    : b.CN == 64 ? reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 64>) : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 128>);
-        }
-        static const bool no_halo = dev_env("HCM_NO_BNECK_HALO") != nullptr;
-        // round 4: 128 mid channels (layer2) on 128-PIXEL tiles, one 92 KB workgroup per CU instead of two 64-pixel ones.  A tile streams the block's
-        // 557 KB of weights (3x3 295 KB + expansion 131 KB + next reduction 131 KB) from L2 whatever its size: 2048 64-pixel tiles = 1.14 GB per launch
-        // (the pair at B = 64) against 0.39 GB of activations -- the launch was bound by that stream (134 us = 2.9 TB/s of HBM traffic, 0.28 of the
-        // matrix rate).  HCM_BNECK128_BM64=1 (development build): the 64-pixel tiles.
-        static const bool bm64 = dev_env("HCM_BNECK128_BM64") != nullptr;
-        if (!image && !no_halo && !bm64 && b.C1 == 128 && b.CN == 128 && b.stride == 1 && d.W % 16 == 0 && 128 % d.W == 0 && (d.Ho * d.Wo) % 128 == 0 &&
-            (long)d.groups * (d.M / 128) >= 192) {
-            const size_t halo = (size_t)KT1 * ((((128 / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 8192;
-            size_t lds = (size_t)KT1 * 128 * 128 + (size_t)KT1 * 64 * 128 + (size_t)128 * 128 + (size_t)b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-            if (halo > lds) lds = halo;
-            if (lds <= 96 * 1024) {
-                const void* fb = dt == DT_BF16 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 128, 128, 0, false, kHaloRing, 1>)
-                                               : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 128, 128, 0, false, kHaloRing, 1>);
-                hipError_t eb = hipFuncSetAttribute(fb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (eb != hipSuccess) return eb;
-                void* ab[] = {&qq};
-                return hipLaunchKernel(fb, dim3(d.M / 128, d.groups), dim3(512), ab, lds, s);
-            }
-        }
-        bool halo_on = false;
-        if (!image && !no_halo && b.stride == 1 && d.W % 16 == 0 && BM % d.W == 0 && (d.Ho * d.Wo) % BM == 0) {
-            const size_t halo = (size_t)KT1 * ((((BM / d.W + 2) * (d.W + 2)) + 7) & ~7) * 128 + (size_t)kHaloRing * 8192;
-            if (halo <= 80 * 1024) {
-                halo_on = true;
-                // (the 3-deep ring of whole tap tiles is not used by this form: the phase-B regions or the halo block + weight ring decide)
-                lds1 = (size_t)KT1 * BM * 128 + (size_t)KT1 * 64 * 128 + (size_t)BM * 128 + (size_t)2 * b.CN * 128 + (size_t)(4 * b.C1 + b.CN) * 4;
-                if (halo > lds1) lds1 = halo;
-                if (dt == DT_BF16) f1 = b.C1 == 128 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 64, 128, 128, 0, false, kHaloRing>)
-                                      : b.CN == 64 ? reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 64, 64, 0, false, kHaloRing>)
-                                                   : reinterpret_cast<const void*>(bneck231r_kernel<bf16, 128, 64, 128, 0, false, kHaloRing>);
-                else f1 = b.C1 == 128 ? reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 128, 0, false, kHaloRing>)
-                        : b.CN == 64 ? reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 64, 0, false, kHaloRing>)
-                                     : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 128, 0, false, kHaloRing>);
-            }
-        }
-#ifdef HCM_DEV_KNOBS
-        if (!image && prof_on() && dt == DT_F16 && b.C1 == 64 && b.CN == 64)
-            f1 = halo_on ? reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 64, 0, true, kHaloRing>) : reinterpret_cast<const void*>(bneck231r_kernel<f16, 128, 64, 64, 0, true>);
-        if (!image && prof_on() && dt == DT_F16 && b.C1 == 128 && b.CN == 128)
-            f1 = halo_on ? reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 128, 0, true, kHaloRing>) : reinterpret_cast<const void*>(bneck231r_kernel<f16, 64, 128, 128, 0, true>);
-#endif
-        (void)halo_on;
-        hipError_t e1 = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e1 != hipSuccess) return e1;
-        void* a1[] = {&qq};
-        return hipLaunchKernel(f1, dim3((d.M + BM - 1) / BM, d.groups), dim3(512), a1, lds1, s);
     }
-    size_t lds = (size_t)KT1 * BM * 128 + (size_t)KT1 * 128 * 128 + (size_t)(BM / 2) * (128 + 4) * 4;
-    const size_t ring = 3 * (size_t)(BM + b.C1) * 128;     // phase A: 3-deep ring
-    if (ring > lds) lds = ring;
-    const void* fn;
-    if (dt == DT_BF16) fn = b.C1 == 64 ? reinterpret_cast<const void*>(bneck23_kernel<bf16, 128, 64>) : reinterpret_cast<const void*>(bneck23_kernel<bf16, 64, 128>);
-    else fn = b.C1 == 64 ? reinterpret_cast<const void*>(bneck23_kernel<f16, 128, 64>) : reinterpret_cast<const void*>(bneck23_kernel<f16, 64, 128>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (b.xd) { qq.xd = (const char*)b.xd; qq.xdC = b.xdC; qq.xd_bytes = (unsigned)xdb; qq.g_xd = b.g_xd; }
+    const BneckForm f = choose_bneck_form(dt, b.C1, CN, KD, d);
+    qq.xcd_tiles = f.xcd_tiles;
+    hipError_t e = hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOnePerCu);
     if (e != hipSuccess) return e;
-    void* args[] = {&q};
-    return hipLaunchKernel(fn, dim3((d.M + BM - 1) / BM, d.groups), dim3(512), args, lds, s);
+    void* args[] = {&qq};
+    return hipLaunchKernel(f.fn, f.grid, dim3(512), args, f.lds, s);
 }
 
 

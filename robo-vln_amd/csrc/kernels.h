@@ -144,6 +144,8 @@ struct DepthBlk {
 };
 hipError_t launch_depth_blk(const DepthBlk& d, int dt, hipStream_t s);
 hipError_t launch_bneck23(const Bneck23& b, int dt, hipStream_t s);
+// is launch_bneck23 built for C1 mid channels, a next reduction to CN channels (0: none) and KD folded 64-channel down-sample blocks (0: identity rows)?
+bool bneck23_ok(int dt, int C1, int CN, int KD);
 
 // While tuning is on, the first launch of every new (shape, dtype) times all tile/staging variants on the real
 // operands and caches the fastest (process-wide); hcm_finalize() runs one tuning step at max_batch.

@@ -509,7 +509,9 @@ def test_bottleneck_tail_fused(prec, cfg):
                                  # 256 mid channels (RGB layer3; round 4): streamed identity rows, one workgroup per CU; ragged last tile, stride 2
                                  (2, 16, 16, 256, 1, 256), (3, 8, 8, 256, 1, 256), (1, 12, 20, 256, 1, 256), (2, 16, 16, 256, 2, 256), (96, 16, 16, 256, 1, 256),
                                  # 128 mid channels on 128-pixel tiles (taken from 192 tiles up)
-                                 (24, 32, 32, 128, 1, 128), (96, 16, 16, 128, 1, 128)])
+                                 (24, 32, 32, 128, 1, 128), (96, 16, 16, 128, 1, 128),
+                                 # 64 mid channels with a 128-wide reduction on a map whose width is no multiple of 16: the classic ring, no halo
+                                 (1, 12, 20, 64, 1, 128)])
 def test_bottleneck_tail_next_fused(prec, cfg):
     """Bottleneck tail + the next block's 1x1 reduction in one launch: both outputs BIT-identical to the three stand-alone convs."""
     lib, L = _lib()
@@ -582,7 +584,9 @@ def test_bottleneck_tail_next_ragged_tile_race_screen(cfg):
 
 
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
-@pytest.mark.parametrize("cfg", [(2, 16, 16, 1), (3, 17, 15, 1), (2, 16, 16, 2), (5, 9, 11, 2), (2, 64, 64, 1)])
+@pytest.mark.parametrize("cfg", [(2, 16, 16, 1), (3, 17, 15, 1), (2, 16, 16, 2), (5, 9, 11, 2), (2, 64, 64, 1),
+                                 # a 12 x 16 map (192 pixels): whole 64-pixel halo tiles of an image, but no whole 128-pixel ones
+                                 (2, 12, 16, 1)])
 def test_bottleneck_tail_downsample_folded(prec, cfg):
     """First bottleneck of a stage in one launch: the 1x1 down-sample conv rides in the expansion GEMM (K-concatenated weights) and the
     next block's reduction is computed from the output tile.  The identity is no longer rounded to the storage type before the add, so
