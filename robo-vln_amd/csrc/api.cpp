@@ -8,32 +8,6 @@
 
 #include "model.h"
 
-namespace hcm {
-void build_spec_high(hcm_ctx* ctx);
-void build_spec_low(hcm_ctx* ctx);
-void prepare_high(hcm_ctx* ctx);
-void prepare_low(hcm_ctx* ctx);
-void build_spec_cma(hcm_ctx* ctx);
-void prepare_cma(hcm_ctx* ctx);
-void run_refresh_instruction(hcm_ctx* ctx, const void* ids, int ids_dt, int B, const int32_t* idx, int n);   // L = ctx->cur_L
-void run_cma(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, const float* h_in,
-             const float* mask, float* out, float* stop, float* h_out, int T = 1);
-void build_spec_s2s(hcm_ctx* ctx);
-void prepare_s2s(hcm_ctx* ctx);
-void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,
-             const float* mask, float* out, float* stop, float* progress, float* h_out, int T = 1);
-void comm_destroy(hcm_ctx* ctx);
-void run_step(hcm_ctx* ctx, bool do_hi, bool do_lo, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt,
-              int B, const float* hi_h_in, const float* lo_h_in, const float* mask, const int64_t* subtask, float* logits,
-              int ld_logits, float* vel, int ld_vel, float* stop, int ld_stop, float* hi_h_out, float* lo_h_out, int T = 1);
-void run_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, const int64_t* oracle,
-                  const float* corrected, const float* oracle_stop, const float* hi_h_in, const float* lo_h_in, const float* mask, float* result,
-                  float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop);
-void run_flat_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, int Bi,
-                       const float* corrected, const float* oracle_stop, const float* progress, const float* h_in, const float* mask, float* result,
-                       float* h_out, float* out, float* stop, float* progress_hat);
-}  // namespace hcm
-
 using namespace hcm;
 
 static thread_local std::string g_create_err;
@@ -47,6 +21,7 @@ static int fail(hcm_ctx* h, int code, const std::string& msg) {
 
 static int check_fwd(hcm_ctx* h, int B);
 static int check_len(hcm_ctx* h, int L);
+static FwdCall frames(const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int rows, int L, void* stream);
 static void drop_instruction_cache(hcm_ctx* h);
 static bool rgb_dt_ok(int d);
 static bool ids_dt_ok(int d);
@@ -59,24 +34,24 @@ static void destroy_entry(hcm_ctx::GraphEntry& g) {
 }
 
 // replay of a segmented entry: the step's top-level fork / chain launches / join, in the order the capture pass recorded them
-static hipError_t replay_segments(hcm_ctx* h, const hcm_ctx::GraphEntry& g) {
+static hipError_t replay_segments(hcm_ctx* h, const hcm_ctx::GraphEntry& g, hipStream_t stream) {
     hipError_t e = hipSuccess;
     unsigned used = 0;                                   // aux streams that received a launch since the fork
     for (const auto& op : g.prog) {
         if (op.kind == 0) {
-            if ((e = hipEventRecord(h->ev_fork, h->stream)) != hipSuccess) return e;
+            if ((e = hipEventRecord(h->ev_fork, stream)) != hipSuccess) return e;
             for (int i = 0; i < op.n; ++i) if ((e = hipStreamWaitEvent(g.aux[i], h->ev_fork, 0)) != hipSuccess) return e;
             used = 0;
         } else if (op.kind == 1 || op.kind == 3) {
             if (op.kind == 1) e = hipGraphLaunch(op.exec, op.st);
             else e = hipMemcpyAsync(op.dst, op.src, op.bytes, hipMemcpyHostToDevice, op.st);
             if (e != hipSuccess) return e;
-            for (int i = 0; i < 4; ++i) if (op.st == g.aux[i] && op.st != h->stream) used |= 1u << i;
+            for (int i = 0; i < 4; ++i) if (op.st == g.aux[i] && op.st != stream) used |= 1u << i;
         } else {
             for (int i = 0; i < op.n; ++i) {
                 if (!(used & (1u << i))) continue;       // nothing ran there: the fork's wait alone orders nothing anybody needs
                 if ((e = hipEventRecord(h->ev_join[i], g.aux[i])) != hipSuccess) return e;
-                if ((e = hipStreamWaitEvent(h->stream, h->ev_join[i], 0)) != hipSuccess) return e;
+                if ((e = hipStreamWaitEvent(stream, h->ev_join[i], 0)) != hipSuccess) return e;
             }
         }
     }
@@ -85,10 +60,10 @@ static hipError_t replay_segments(hcm_ctx* h, const hcm_ctx::GraphEntry& g) {
 
 // Pick the side streams of the step's chains so that aux[1] (depth), aux[2] (BERT) and the caller's stream overlap pairwise (model.h).  The probe: two 150 us
 // one-wave spin kernels, one per stream -- side by side they take 150 us, on a shared hardware queue 300.
-static void pick_chain_streams(hcm_ctx* h) {
-    for (auto st : h->probed_for) if (st == h->stream) return;                    // (a caller that alternates between streams is probed once per stream)
+static void pick_chain_streams(hcm_ctx* h, hipStream_t stream) {
+    for (auto st : h->probed_for) if (st == stream) return;                    // (a caller that alternates between streams is probed once per stream)
     if (h->probed_for.size() >= 8) return;
-    h->probed_for.push_back(h->stream);
+    h->probed_for.push_back(stream);
     if (dev_env("HCM_NO_STREAM_PROBE")) return;
     constexpr double kSpinUs = 150.0;
     auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -108,11 +83,11 @@ static void pick_chain_streams(hcm_ctx* h) {
     std::vector<hipStream_t> cand;
     for (int i = 0; i < 4; ++i) if (h->aux[i]) cand.push_back(h->aux[i]);
     for (auto p : h->pool) if (p) cand.push_back(p);
-    (void)launch_spin(1, h->stream); (void)hipStreamSynchronize(h->stream);      // (code object loaded before anything is timed)
+    (void)launch_spin(1, stream); (void)hipStreamSynchronize(stream);      // (code object loaded before anything is timed)
     std::vector<hipStream_t> chosen;
     for (auto c : cand) {
         if (chosen.size() >= 2) break;
-        bool ok = overlap(h->stream, c);
+        bool ok = overlap(stream, c);
         for (auto k : chosen) ok = ok && overlap(k, c);
         if (ok) chosen.push_back(c);
     }
@@ -128,27 +103,39 @@ static void pick_chain_streams(hcm_ctx* h) {
     place(2, chosen[1]);
 }
 
-// hipGraph cache shared by the fused entry points: `key` = every argument that the enqueued work depends on (batch, dtypes,
-// all pointers, the stream); `run` enqueues the work on h->stream.  A key is run eagerly the first time it is seen (that also
+// graph-cache key of a call: every pointer and every scalar of its descriptor (stream and flags too), so that a field nobody thought of
+// cannot make two different calls share a captured graph
+static std::vector<uint64_t> call_key(const FwdCall& c, bool segmented) {
+    auto p = [](const void* q) { return (uint64_t)(uintptr_t)q; };
+    return {(uint64_t)c.do_hi | (uint64_t)c.do_lo << 1 | (uint64_t)c.reuse_instruction << 2 | (uint64_t)c.host_frames << 3 | (uint64_t)segmented << 4,
+            (uint64_t)c.val, (uint64_t)c.rgb_dt, (uint64_t)c.ids_dt, (uint64_t)c.rows, (uint64_t)c.T, (uint64_t)c.Bi, (uint64_t)c.L,
+            (uint64_t)c.ld_logits, (uint64_t)c.ld_vel, (uint64_t)c.ld_stop, p(c.stream), p(c.rgb), p(c.depth), p(c.ids), p(c.lens),
+            p(c.hi_h_in), p(c.lo_h_in), p(c.hi_h_out), p(c.lo_h_out), p(c.mask), p(c.subtask), p(c.logits), p(c.vel), p(c.stop), p(c.progress),
+            p(c.oracle), p(c.corrected), p(c.oracle_stop), p(c.progress_label), p(c.result)};
+}
+
+// hipGraph cache shared by the fused entry points, keyed by call_key().  A key is run eagerly the first time it is seen (that also
 // performs the one-time kernel attribute setup) and captured -- forked side streams included -- the second time; later
 // calls replay the instantiated graph.
 // segmented = HCM_ACT_CHAIN_GRAPHS: one linear graph per chain, captured by the step itself at its chain boundaries (model.h, SegOp).
-template <typename F>
-static int run_graphed(hcm_ctx* h, const std::vector<uint64_t>& key, void* stream, F run, bool segmented = false) {
+static int run_graphed(hcm_ctx* h, const FwdCall& call, bool segmented = false) {
+    const hipStream_t stream = call.stream;
+    auto run = [&]() { run_forward(h, call); };
     auto eager = [&]() -> int {
         try { run(); } catch (const std::exception& e) { return fail(h, HCM_ERR_HIP, e.what()); }
         ++h->eager_launches;
         return HCM_OK;
     };
-    if (segmented && stream != nullptr && !h->taps_on) pick_chain_streams(h);      // (once per caller stream; eager steps fork onto the same side streams)
+    if (segmented && stream != nullptr && !h->taps_on) pick_chain_streams(h, stream);      // (once per caller stream; eager steps fork onto the same side streams)
     // the legacy default stream cannot be captured; taps allocate and synchronise
     if (!h->use_graph || h->taps_on || stream == nullptr) return eager();
+    const std::vector<uint64_t> key = call_key(call, segmented);
     for (auto& g : h->graphs)
         if (g.key == key) {
             if (!g.prog.empty()) {
-                if (replay_segments(h, g) != hipSuccess) return fail(h, HCM_ERR_HIP, "replay of the step's chain graphs failed");
+                if (replay_segments(h, g, stream) != hipSuccess) return fail(h, HCM_ERR_HIP, "replay of the step's chain graphs failed");
             } else
-            if (hipGraphLaunch(g.exec, h->stream) != hipSuccess) return fail(h, HCM_ERR_HIP, "hipGraphLaunch failed");
+            if (hipGraphLaunch(g.exec, stream) != hipSuccess) return fail(h, HCM_ERR_HIP, "hipGraphLaunch failed");
             ++h->graph_launches;
             return HCM_OK;
         }
@@ -183,15 +170,15 @@ static int run_graphed(hcm_ctx* h, const std::vector<uint64_t>& key, void* strea
         }
         if (h->graphs.size() >= 8) { destroy_entry(h->graphs.front()); h->graphs.erase(h->graphs.begin()); }
         h->graphs.push_back(ge);
-        if (replay_segments(h, h->graphs.back()) != hipSuccess) return fail(h, HCM_ERR_HIP, "replay of the step's chain graphs failed");
+        if (replay_segments(h, h->graphs.back(), stream) != hipSuccess) return fail(h, HCM_ERR_HIP, "replay of the step's chain graphs failed");
         ++h->graph_launches;
         return HCM_OK;
     }
-    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return eager(); }
+    if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return eager(); }
     std::string cap_err;
     try { run(); } catch (const std::exception& e) { cap_err = e.what(); }
     hipGraph_t graph = nullptr;
-    hipError_t ce = hipStreamEndCapture(h->stream, &graph);
+    hipError_t ce = hipStreamEndCapture(stream, &graph);
     if (!cap_err.empty() || ce != hipSuccess || !graph) {
         if (graph) (void)hipGraphDestroy(graph);
         (void)hipGetLastError();
@@ -206,7 +193,7 @@ static int run_graphed(hcm_ctx* h, const std::vector<uint64_t>& key, void* strea
     if (ce != hipSuccess) { (void)hipGetLastError(); h->use_graph = false; return eager(); }
     if (h->graphs.size() >= 8) { destroy_entry(h->graphs.front()); h->graphs.erase(h->graphs.begin()); }
     h->graphs.push_back(ge);
-    if (hipGraphLaunch(ge.exec, h->stream) != hipSuccess) return fail(h, HCM_ERR_HIP, "hipGraphLaunch failed");
+    if (hipGraphLaunch(ge.exec, stream) != hipSuccess) return fail(h, HCM_ERR_HIP, "hipGraphLaunch failed");
     ++h->graph_launches;
     return HCM_OK;
 }
@@ -438,26 +425,25 @@ int hcm_load_tensor(hcm_handle h, int model, const char* key, const void* data, 
 static void dry_run(hcm_ctx* h, int B) {
     h->arena.dry = true;
     h->arena.peak = 0;
-    h->cur_L = h->cfg.instr_len;
-    h->cur_lens = nullptr;
+    FwdCall c;                                             // every pointer null: allocations only
+    c.L = h->cfg.instr_len;
+    auto run = [&](int rows, int T, FwdCall::Val val = FwdCall::kNoVal) { c.rows = c.Bi = rows; c.T = T; c.val = val; run_forward(h, c); };
     if (h->kind == 1) {
-        run_cma(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B, nullptr, nullptr, nullptr, nullptr, nullptr);
+        run(B, 1);
         // hcm_cma_forward_seq: the scans' buffers on top of the step's.  What they hold grows with the rows (the projections, both sequence
         // buffers: T = B, N = 1 has all B rows whatever B's divisors) or with N (the per-step path's ping-pong state: largest at T = 2)
         for (int T : {2, 3, B})
-            if (T >= 2 && T <= B) run_cma(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, T);
+            if (T >= 2 && T <= B) run(B / T * T, T);
         // hcm_flat_val_step: the same shapes with every optional output row (out, stop) in the workspace
         for (int T : {1, 2, 3, B})
-            if (T <= B) run_flat_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, T, B / T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                          nullptr, nullptr, nullptr, nullptr, nullptr);
+            if (T <= B) run(B / T * T, T, FwdCall::kFlatVal);
         return;
     }
     if (h->kind == 2) {                                // the step with one instruction per row, and the sequence path at T = 2, 3 (as below)
         for (int T = 1; T <= 3 && T <= B; ++T) {
-            run_s2s(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, B / T * T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, T);
+            run(B / T * T, T);
             // hcm_flat_val_step: out, stop and -- with the progress monitor, whose head runs whether or not its rows are wanted -- progress_hat in the workspace
-            run_flat_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, T, B / T, B / T * T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, nullptr);
+            run(B / T * T, T, FwdCall::kFlatVal);
         }
         return;
     }
@@ -465,25 +451,20 @@ static void dry_run(hcm_ctx* h, int B) {
     for (int T = 1; T <= 3 && T <= B; ++T) {
         const int rows = B / T * T;
         for (int which = 0; which < 3; ++which) {          // both (the fused step) / high alone / low alone
-            const bool dh = hi && which != 2, dl = lo && which != 1;
+            c.do_hi = hi && which != 2; c.do_lo = lo && which != 1;
             if ((which == 0 && !(hi && lo)) || (which == 1 && !hi) || (which == 2 && !lo)) continue;
-            if (which == 0 && T > 1) {                     // the fused step has no sequence form; hcm_val_step runs both models on T*N rows
-                run_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, T, rows / T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr);
-                continue;
-            }
-            if (which == 0)                                // ... and at T = 1 (its trunks are never shared, and it keeps its own label / output rows)
-                run_val_step(h, nullptr, DT_F32, nullptr, nullptr, DT_I64, 1, rows, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr);
-            run_step(h, dh, dl, nullptr, DT_F32, nullptr, nullptr, DT_I64, rows, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0,
-                     nullptr, 0, nullptr, nullptr, T);
+            // hcm_val_step runs both models on T*N rows; also at T = 1 (its trunks are never shared, and it keeps its own label / output rows)
+            if (which == 0) run(rows, T, FwdCall::kVal);
+            if (which == 0 && T > 1) continue;             // the fused step has no sequence form
+            run(rows, T);
         }
     }
     // hcm_refresh_instruction of every environment at once: a second BERT / instruction-stream scratch set on top of the persistent
     // step tensors -- with small frames and a long instruction that is more than any step needs
     if (hi && lo) {
         const size_t peak = h->arena.peak;
-        run_refresh_instruction(h, nullptr, DT_I64, B, nullptr, B);
+        c.rows = B;
+        run_refresh_instruction(h, c, nullptr, B);
         if (h->arena.peak < peak) h->arena.peak = peak;
     }
 }
@@ -500,6 +481,17 @@ static void free_device_weights(hcm_ctx* h) {
     h->hi = hcm::HighW();
     h->lo = hcm::LowW();
     h->s2s = hcm::S2sW();
+}
+// calibrate_run / the tuning step of hcm_finalize: whatever the handle holds, once, on the B rows of `c` with scratch state and outputs
+static FwdCall scratch_call(hcm_ctx* h, FwdCall c, float* hh, float* lh, float* hh2, float* lh2, float* mask, float* rec, const int64_t* subtask) {
+    const hcm_config& g = h->cfg;
+    c.mask = mask;
+    if (h->kind != 0) { c.lo_h_in = hh; c.lo_h_out = hh2; c.vel = rec; c.stop = rec + 8 * (size_t)c.rows; return c; }
+    c.do_hi = g.build_high != 0; c.do_lo = g.build_low != 0;
+    if (c.do_hi) { c.hi_h_in = hh; c.hi_h_out = hh2; c.logits = rec; c.ld_logits = c.do_lo ? 7 : g.num_actions; }
+    if (c.do_lo) { c.lo_h_in = lh; c.lo_h_out = lh2; c.vel = c.do_hi ? rec + 4 : rec; c.ld_vel = c.do_hi ? 7 : g.lo_actions; c.stop = c.do_hi ? rec + 6 : rec + 8; c.ld_stop = c.do_hi ? 7 : 1; }
+    if (!c.do_hi) { c.ids = nullptr; c.ids_dt = DT_I64; c.subtask = subtask; }
+    return c;
 }
 static int calibrate_run(hcm_ctx* h, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int L, hipStream_t stream,
                          int pass = 0) {
@@ -518,23 +510,11 @@ static int calibrate_run(hcm_ctx* h, const void* rgb, int rgb_dt, const float* d
     (void)hipMemsetAsync(h->calib_buf + 16, 0, (hcm_ctx::kCalibWords - 16) * 4, stream);
     const bool conc = h->concurrent;
     h->concurrent = false;                       // one stream: the hooks are plain launches in program order
-    h->stream = stream;
-    h->cur_L = L;
-    h->cur_lens = nullptr;
     h->calib = true;
     drop_instruction_cache(h);
     std::string err;
     try {
-        if (h->kind == 1)
-            run_cma(h, rgb, rgb_dt, depth, ids, ids_dt, B, hh, mask, rec, rec + 8 * (size_t)B, hh2);
-        else if (h->kind == 2)
-            run_s2s(h, rgb, rgb_dt, depth, ids, ids_dt, B, B, hh, mask, rec, rec + 8 * (size_t)B, nullptr, hh2);
-        else if (c.build_high && c.build_low)
-            run_step(h, true, true, rgb, rgb_dt, depth, ids, ids_dt, B, hh, lh, mask, nullptr, rec, 7, rec + 4, 7, rec + 6, 7, hh2, lh2);
-        else if (c.build_high)
-            run_step(h, true, false, rgb, rgb_dt, depth, ids, ids_dt, B, hh, nullptr, mask, nullptr, rec, c.num_actions, nullptr, 0, nullptr, 0, hh2, nullptr);
-        else
-            run_step(h, false, true, rgb, rgb_dt, depth, nullptr, DT_I64, B, nullptr, lh, mask, st, nullptr, 0, rec, c.lo_actions, rec + 8, 1, nullptr, lh2);
+        run_forward(h, scratch_call(h, frames(rgb, rgb_dt, depth, ids, ids_dt, B, L, stream), hh, lh, hh2, lh2, mask, rec, st));
     } catch (const std::exception& e) { err = e.what(); }
     h->calib = false;
     h->concurrent = conc;
@@ -766,16 +746,10 @@ int hcm_finalize(hcm_handle h) {
             float* rec = (float*)p;
             const bool conc = h->concurrent;
             h->concurrent = false;
-            h->stream = nullptr;
             igemm_set_tuning(true);
             std::string terr;
             try {
-                if (c.build_high && c.build_low)
-                    run_step(h, true, true, rgb, DT_F32, dep, ids, DT_I64, (int)B, hh, lh, mask, nullptr, rec, 7, rec + 4, 7, rec + 6, 7, hh2, lh2);
-                else if (c.build_high)
-                    run_step(h, true, false, rgb, DT_F32, dep, ids, DT_I64, (int)B, hh, nullptr, mask, nullptr, rec, c.num_actions, nullptr, 0, nullptr, 0, hh2, nullptr);
-                else
-                    run_step(h, false, true, rgb, DT_F32, dep, nullptr, DT_I64, (int)B, nullptr, lh, mask, (const int64_t*)ids, nullptr, 0, rec, c.lo_actions, rec + 8, 1, nullptr, lh2);
+                run_forward(h, scratch_call(h, frames(rgb, DT_F32, dep, ids, DT_I64, (int)B, c.instr_len, nullptr), hh, lh, hh2, lh2, mask, rec, (const int64_t*)ids));
             } catch (const std::exception& e) { terr = e.what(); }
             igemm_set_tuning(false);
             h->concurrent = conc;
@@ -825,6 +799,7 @@ int hcm_release_host_weights(hcm_handle h) {
     return HCM_OK;
 }
 
+// ---- the forward entry points: each makes its own checks, fills a descriptor (model.h, FwdCall) and runs it
 static int check_fwd(hcm_ctx* h, int B) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(h->finalized, HCM_ERR_STATE, "forward before hcm_finalize");
@@ -835,7 +810,13 @@ static int check_fwd(hcm_ctx* h, int B) {
 static int check_len(hcm_ctx* h, int L) {
     REQUIRE(L >= 1 && L <= h->cfg.instr_len, HCM_ERR_ARG,
             "instruction length " + std::to_string(L) + " outside [1, " + std::to_string(h->cfg.instr_len) + "] (hcm_config.instr_len is the maximum L)");
-    h->cur_L = L;
+    return HCM_OK;
+}
+// shape of a sequence call; the product in 64 bits, so that no T * N can wrap its way past max_batch
+static int check_seq(hcm_ctx* h, int T, int N) {
+    REQUIRE(h, HCM_ERR_ARG, "null handle");
+    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
+    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
     return HCM_OK;
 }
 // every entry point other than hcm_act_ex re-uses the workspace region that holds the cached instruction stream
@@ -844,42 +825,86 @@ static void drop_instruction_cache(hcm_ctx* h) { h->last_hi_batch = -1; h->last_
 static bool rgb_dt_ok(int d) { return d == HCM_F32 || d == HCM_U8; }
 static bool ids_dt_ok(int d) { return d == HCM_F32 || d == HCM_I32 || d == HCM_I64; }
 
-int hcm_high_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
-                     const int32_t* lengths, int B, int L, const float* h_in, const float* mask, float* logits, float* h_out, void* stream) {
-    int rc = check_fwd(h, B);
+// the observation part of a descriptor
+static FwdCall frames(const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int rows, int L, void* stream) {
+    FwdCall c;
+    c.rgb = rgb; c.rgb_dt = rgb_dt; c.depth = depth; c.ids = ids; c.ids_dt = ids_dt;
+    c.rows = c.Bi = rows; c.L = L; c.stream = (hipStream_t)stream;
+    return c;
+}
+// state, mask and outputs of a flat handle's one model
+static void flat_io(hcm_ctx* h, FwdCall& c, const float* h_in, const float* mask, float* out, float* stop, float* progress, float* h_out) {
+    c.lo_h_in = h_in; c.mask = mask; c.lo_h_out = h_out;
+    c.vel = out; c.ld_vel = h->cfg.num_actions; c.stop = stop; c.ld_stop = 1; c.progress = progress;
+}
+static int run_eager(hcm_ctx* h, const FwdCall& c) {
+    try { run_forward(h, c); } catch (const std::exception& e) { return fail(h, HCM_ERR_HIP, e.what()); }
+    return HCM_OK;
+}
+
+// hcm_high_forward (T = 1) and hcm_high_forward_seq
+static int high_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, const int32_t* lengths, int rows,
+                        int T, int L, const float* h_in, const float* mask, float* logits, float* h_out, void* stream) {
+    int rc = check_fwd(h, rows);
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
-    h->cur_lens = lengths;
     drop_instruction_cache(h);
     REQUIRE(h->cfg.build_high, HCM_ERR_STATE, "handle holds no high-level model");
     REQUIRE(rgb && depth && ids && h_in && mask && logits && h_out, HCM_ERR_ARG, "null pointer");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_step(h, true, false, rgb, rgb_dtype, depth, ids, ids_dtype, B, h_in, nullptr, mask, nullptr, logits, h->cfg.num_actions,
-                 nullptr, 0, nullptr, 0, h_out, nullptr);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
+    FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
+    c.do_hi = true; c.T = T; c.lens = lengths;
+    c.hi_h_in = h_in; c.mask = mask; c.logits = logits; c.ld_logits = h->cfg.num_actions; c.hi_h_out = h_out;
+    return run_eager(h, c);
 }
 
-int hcm_low_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int B, const float* h_in,
-                    const float* mask, const int64_t* subtask, float* vel, float* stop, float* h_out, void* stream) {
-    int rc = check_fwd(h, B);
+int hcm_high_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
+                     const int32_t* lengths, int B, int L, const float* h_in, const float* mask, float* logits, float* h_out, void* stream) {
+    return high_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, lengths, B, 1, L, h_in, mask, logits, h_out, stream);
+}
+
+int hcm_high_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
+                         const int32_t* lengths, int T, int N, int L, const float* h_in, const float* masks, float* logits, float* h_out, void* stream) {
+    if (const int rc = check_seq(h, T, N)) return rc;
+    return high_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, lengths, T * N, T, L, h_in, masks, logits, h_out, stream);
+}
+
+// hcm_low_forward (T = 1) and hcm_low_forward_seq
+static int low_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* depth, int rows, int T, const float* h_in, const float* mask,
+                       const int64_t* subtask, float* vel, float* stop, float* h_out, void* stream) {
+    int rc = check_fwd(h, rows);
     if (rc) return rc;
     drop_instruction_cache(h);
     REQUIRE(h->cfg.build_low, HCM_ERR_STATE, "handle holds no low-level model");
     REQUIRE(rgb && depth && h_in && mask && subtask && vel && stop && h_out, HCM_ERR_ARG, "null pointer");
     REQUIRE(rgb_dt_ok(rgb_dtype), HCM_ERR_ARG, "unsupported rgb dtype");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_step(h, false, true, rgb, rgb_dtype, depth, nullptr, DT_I64, B, nullptr, h_in, mask, subtask, nullptr, 0, vel,
-                 h->cfg.lo_actions, stop, 1, nullptr, h_out);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
+    FwdCall c = frames(rgb, rgb_dtype, depth, nullptr, DT_I64, rows, 0, stream);
+    c.do_lo = true; c.T = T;
+    c.lo_h_in = h_in; c.mask = mask; c.subtask = subtask; c.lo_h_out = h_out;
+    c.vel = vel; c.ld_vel = h->cfg.lo_actions; c.stop = stop; c.ld_stop = 1;
+    return run_eager(h, c);
+}
+
+int hcm_low_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int B, const float* h_in,
+                    const float* mask, const int64_t* subtask, float* vel, float* stop, float* h_out, void* stream) {
+    return low_forward(h, rgb, rgb_dtype, depth, B, 1, h_in, mask, subtask, vel, stop, h_out, stream);
+}
+
+int hcm_low_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int T, int N, const float* h_in,
+                        const float* masks, const int64_t* subtask, float* vel, float* stop, float* h_out, void* stream) {
+    if (const int rc = check_seq(h, T, N)) return rc;
+    return low_forward(h, rgb, rgb_dtype, depth, T * N, T, h_in, masks, subtask, vel, stop, h_out, stream);
+}
+
+// hcm_cma_forward (T = 1: through the graph cache) and hcm_cma_forward_seq at T > 1; the caller has checked the handle's kind, rows and L
+static int cma_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int rows, int T, int L,
+                       const float* h_in, const float* mask, float* out, float* stop, float* h_out, void* stream) {
+    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
+    c.T = T;
+    flat_io(h, c, h_in, mask, out, stop, nullptr, h_out);
+    return T == 1 ? run_graphed(h, c) : run_eager(h, c);
 }
 
 int hcm_cma_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int L,
@@ -888,120 +913,50 @@ int hcm_cma_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* d
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(h->kind == 1, HCM_ERR_STATE, "not a CMANet handle (hcm_cma_create)");
-    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    h->stream = (hipStream_t)stream;
-    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)rgb_dtype, (uint64_t)ids_dtype, (uint64_t)rgb, (uint64_t)depth, (uint64_t)ids,
-                                       (uint64_t)h_in, (uint64_t)mask, (uint64_t)out, (uint64_t)stop, (uint64_t)h_out, (uint64_t)stream};
-    return run_graphed(h, key, stream, [&]() { run_cma(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, h_in, mask, out, stop, h_out); });
+    return cma_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, 1, L, h_in, mask, out, stop, h_out, stream);
 }
 
 int hcm_cma_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int L,
                         const float* h_in, const float* masks, float* out, float* stop, float* h_out, void* stream) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(h->kind == 1, HCM_ERR_STATE, "not a CMANet handle (hcm_cma_create)");
-    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
-    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
-    if (T == 1) return hcm_cma_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, N, L, h_in, masks, out, stop, h_out, stream);
-    int rc = check_fwd(h, T * N);
+    int rc = check_seq(h, T, N);
     if (rc) return rc;
+    if (T == 1) return hcm_cma_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, N, L, h_in, masks, out, stop, h_out, stream);
+    if ((rc = check_fwd(h, T * N))) return rc;
     if ((rc = check_len(h, L))) return rc;
-    REQUIRE(rgb && depth && ids && h_in && masks && out && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_cma(h, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, h_in, masks, out, stop, h_out, T);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
+    return cma_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, T, L, h_in, masks, out, stop, h_out, stream);
 }
 
-// argument checks of the two Seq2SeqNet entry points that do not need a finalized handle come first, so that a caller's mistake is reported as
-// such whatever state the handle is in
-static int s2s_check_args(hcm_ctx* h, int rows, int B_instr, const float* progress) {
+// hcm_s2s_forward (through the graph cache) and hcm_s2s_forward_seq.  The argument checks that do not need a finalized handle come first, so
+// that a caller's mistake is reported as such whatever state the handle is in
+static int s2s_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int rows, int T, bool graphed,
+                       int B_instr, int L, const float* h_in, const float* mask, float* out, float* stop, float* progress, float* h_out, void* stream) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(h->kind == 2, HCM_ERR_STATE, "not a Seq2SeqNet handle (hcm_s2s_create)");
     REQUIRE(B_instr == 1 || B_instr == rows, HCM_ERR_ARG, "B_instr must be 1 (one instruction for every frame, seq2seq.py:163) or the number of frames");
     REQUIRE(h->s2s_cfg.progress_monitor || !progress, HCM_ERR_ARG,
             "progress must be NULL: the handle was created without PROGRESS_MONITOR.use (hcm_s2s_config.progress_monitor)");
-    return HCM_OK;
+    int rc = check_fwd(h, rows);
+    if (rc) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
+    c.T = T; c.Bi = B_instr;
+    flat_io(h, c, h_in, mask, out, stop, progress, h_out);
+    return graphed ? run_graphed(h, c) : run_eager(h, c);
 }
 
 int hcm_s2s_forward(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int B, int B_instr, int L,
                     const float* h_in, const float* mask, float* out, float* stop, float* progress, float* h_out, void* stream) {
-    int rc = s2s_check_args(h, B, B_instr, progress);
-    if (rc) return rc;
-    if ((rc = check_fwd(h, B))) return rc;
-    if ((rc = check_len(h, L))) return rc;
-    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    h->stream = (hipStream_t)stream;
-    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)B_instr, (uint64_t)L, (uint64_t)rgb_dtype, (uint64_t)ids_dtype, (uint64_t)rgb, (uint64_t)depth,
-                                       (uint64_t)ids, (uint64_t)h_in, (uint64_t)mask, (uint64_t)out, (uint64_t)stop, (uint64_t)progress, (uint64_t)h_out,
-                                       (uint64_t)stream, 1u};
-    return run_graphed(h, key, stream, [&]() { run_s2s(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, B_instr, h_in, mask, out, stop, progress, h_out); });
+    return s2s_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, B, 1, true, B_instr, L, h_in, mask, out, stop, progress, h_out, stream);
 }
 
 int hcm_s2s_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int B_instr,
                         int L, const float* h_in, const float* masks, float* out, float* stop, float* progress, float* h_out, void* stream) {
-    REQUIRE(h, HCM_ERR_ARG, "null handle");
-    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
-    int rc = s2s_check_args(h, T * N, B_instr, progress);
-    if (rc) return rc;
-    if ((rc = check_fwd(h, T * N))) return rc;
-    if ((rc = check_len(h, L))) return rc;
-    REQUIRE(rgb && depth && ids && h_in && masks && out && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_s2s(h, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, B_instr, h_in, masks, out, stop, progress, h_out, T);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
-}
-
-int hcm_high_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
-                         const int32_t* lengths, int T, int N, int L, const float* h_in, const float* masks, float* logits, float* h_out, void* stream) {
-    REQUIRE(h, HCM_ERR_ARG, "null handle");
-    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
-    int rc = check_fwd(h, T * N);
-    if (rc) return rc;
-    if ((rc = check_len(h, L))) return rc;
-    h->cur_lens = lengths;
-    drop_instruction_cache(h);
-    REQUIRE(h->cfg.build_high, HCM_ERR_STATE, "handle holds no high-level model");
-    REQUIRE(rgb && depth && ids && h_in && masks && logits && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_step(h, true, false, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, h_in, nullptr, masks, nullptr, logits, h->cfg.num_actions,
-                 nullptr, 0, nullptr, 0, h_out, nullptr, T);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
-}
-
-int hcm_low_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int T, int N, const float* h_in,
-                        const float* masks, const int64_t* subtask, float* vel, float* stop, float* h_out, void* stream) {
-    REQUIRE(h, HCM_ERR_ARG, "null handle");
-    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
-    int rc = check_fwd(h, T * N);
-    if (rc) return rc;
-    drop_instruction_cache(h);
-    REQUIRE(h->cfg.build_low, HCM_ERR_STATE, "handle holds no low-level model");
-    REQUIRE(rgb && depth && h_in && masks && subtask && vel && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype), HCM_ERR_ARG, "unsupported rgb dtype");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_step(h, false, true, rgb, rgb_dtype, depth, nullptr, DT_I64, T * N, nullptr, h_in, masks, subtask, nullptr, 0, vel,
-                 h->cfg.lo_actions, stop, 1, nullptr, h_out, T);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
+    if (const int rc = check_seq(h, T, N)) return rc;
+    return s2s_forward(h, rgb, rgb_dtype, depth, ids, ids_dtype, T * N, T, false, B_instr, L, h_in, masks, out, stop, progress, h_out, stream);
 }
 
 int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, const int32_t* lengths, int T, int N,
@@ -1010,26 +965,22 @@ int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* dept
                  void* stream) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(h->kind == 0, HCM_ERR_STATE, "hcm_val_step needs an HCM handle (hcm_create): the flat baselines have no high-level / low-level pair");
-    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
+    int rc = check_seq(h, T, N);
+    if (rc) return rc;
     REQUIRE(result, HCM_ERR_ARG, "null result");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
-    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
-    int rc = check_fwd(h, T * N);
-    if (rc) return rc;
+    if ((rc = check_fwd(h, T * N))) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_val_step needs both models in the handle");
     REQUIRE(rgb && depth && ids && oracle_subtask && corrected_actions && oracle_stop && hi_h_in && lo_h_in && masks && hi_h_out && lo_h_out,
             HCM_ERR_ARG, "null pointer");
-    h->cur_lens = lengths;
     drop_instruction_cache(h);
-    h->stream = (hipStream_t)stream;
-    try {
-        run_val_step(h, rgb, rgb_dtype, depth, ids, ids_dtype, T, N, oracle_subtask, corrected_actions, oracle_stop, hi_h_in, lo_h_in, masks, result,
-                     hi_h_out, lo_h_out, logits, vel, stop);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
+    FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, T * N, L, stream);
+    c.do_hi = c.do_lo = true; c.T = T; c.lens = lengths;
+    c.hi_h_in = hi_h_in; c.lo_h_in = lo_h_in; c.mask = masks; c.hi_h_out = hi_h_out; c.lo_h_out = lo_h_out;
+    c.logits = logits; c.ld_logits = h->cfg.num_actions; c.vel = vel; c.ld_vel = h->cfg.lo_actions; c.stop = stop; c.ld_stop = 1;
+    c.val = FwdCall::kVal; c.oracle = oracle_subtask; c.corrected = corrected_actions; c.oracle_stop = oracle_stop; c.result = result;
+    return run_eager(h, c);
 }
 
 int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int T, int N, int B_instr, int L,
@@ -1038,8 +989,8 @@ int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float*
     REQUIRE(h, HCM_ERR_ARG, "null handle");
     REQUIRE(h->kind == 1 || h->kind == 2, HCM_ERR_STATE,
             "hcm_flat_val_step needs a CMANet or Seq2SeqNet handle (hcm_cma_create / hcm_s2s_create): the hierarchical pair is validated by hcm_val_step");
-    REQUIRE(T >= 1 && N >= 1, HCM_ERR_ARG, "T and N must be >= 1");
-    REQUIRE((int64_t)T * N <= h->cfg.max_batch, HCM_ERR_ARG, "T*N must not exceed max_batch");
+    int rc = check_seq(h, T, N);
+    if (rc) return rc;
     REQUIRE(result, HCM_ERR_ARG, "null result");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     const bool monitor = h->kind == 2 && h->s2s_cfg.progress_monitor;
@@ -1052,18 +1003,14 @@ int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float*
             "progress and progress_hat must be NULL: the handle has no progress monitor (hcm_s2s_config.progress_monitor)");
     REQUIRE(!monitor || progress, HCM_ERR_ARG,
             "null progress: the handle was created with PROGRESS_MONITOR.use, the auxiliary loss needs observations[\"progress\"]");
-    int rc = check_fwd(h, T * N);
-    if (rc) return rc;
+    if ((rc = check_fwd(h, T * N))) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(rgb && depth && ids && corrected_actions && oracle_stop && h_in && masks && h_out, HCM_ERR_ARG, "null pointer");
-    h->stream = (hipStream_t)stream;
-    try {
-        run_flat_val_step(h, rgb, rgb_dtype, depth, ids, ids_dtype, T, N, B_instr, corrected_actions, oracle_stop, progress, h_in, masks, result, h_out,
-                          out, stop, progress_hat);
-    } catch (const std::exception& e) {
-        return fail(h, HCM_ERR_HIP, e.what());
-    }
-    return HCM_OK;
+    FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, T * N, L, stream);
+    c.T = T; c.Bi = B_instr;
+    flat_io(h, c, h_in, masks, out, stop, progress_hat, h_out);
+    c.val = FwdCall::kFlatVal; c.corrected = corrected_actions; c.oracle_stop = oracle_stop; c.progress_label = progress; c.result = result;
+    return run_eager(h, c);
 }
 
 int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
@@ -1072,38 +1019,28 @@ int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth,
     int rc = check_fwd(h, B);
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
-    h->cur_lens = lengths;
     REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_act needs both models in the handle");
     REQUIRE(rgb && depth && ids && hi_h_in && lo_h_in && mask && record && hi_h_out && lo_h_out, HCM_ERR_ARG, "null pointer");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     REQUIRE(h->cfg.num_actions + h->cfg.lo_actions + 1 == 7, HCM_ERR_UNSUPPORTED, "record layout assumes 4 + 2 + 1 outputs");
-    const bool reuse = (flags & HCM_ACT_REUSE_INSTRUCTION) != 0;
-    REQUIRE(!reuse || (h->last_hi_batch == B && h->last_hi_L == L), HCM_ERR_STATE,
+    FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, B, L, stream);
+    c.do_hi = c.do_lo = true; c.lens = lengths;
+    c.reuse_instruction = (flags & HCM_ACT_REUSE_INSTRUCTION) != 0;
+    REQUIRE(!c.reuse_instruction || (h->last_hi_batch == B && h->last_hi_L == L), HCM_ERR_STATE,
             "HCM_ACT_REUSE_INSTRUCTION: the previous call on this handle was not an hcm_act step with this batch size and instruction length");
-    h->stream = (hipStream_t)stream;
-    h->reuse_instruction = reuse;
-    const bool host_frames = (flags & HCM_ACT_HOST_FRAMES) != 0;
-    if (host_frames && (!h->stage_rgb || !h->stage_depth)) {           // device staging for the largest call: f32 RGB frames + f32 depth frames
+    c.host_frames = (flags & HCM_ACT_HOST_FRAMES) != 0;
+    if (c.host_frames && (!h->stage_rgb || !h->stage_depth)) {         // device staging for the largest call: f32 RGB frames + f32 depth frames
         const size_t n_rgb = (size_t)h->cfg.max_batch * h->cfg.rgb_h * h->cfg.rgb_w * 3 * 4, n_dep = (size_t)h->cfg.max_batch * h->cfg.depth_h * h->cfg.depth_w * 4;
         if (!h->stage_rgb && hipMalloc(&h->stage_rgb, n_rgb) != hipSuccess) { h->stage_rgb = nullptr; return fail(h, HCM_ERR_NOMEM, "hipMalloc of the RGB frame staging buffer failed"); }
         if (!h->stage_depth && hipMalloc((void**)&h->stage_depth, n_dep) != hipSuccess) { h->stage_depth = nullptr; return fail(h, HCM_ERR_NOMEM, "hipMalloc of the depth frame staging buffer failed"); }
     }
-    h->host_frames = host_frames;
-    const int ld = 7;
-    const std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)L, (uint64_t)rgb_dtype, (uint64_t)ids_dtype, (uint64_t)rgb, (uint64_t)depth, (uint64_t)ids,
-                                       (uint64_t)hi_h_in, (uint64_t)lo_h_in, (uint64_t)mask, (uint64_t)record, (uint64_t)hi_h_out,
-                                       (uint64_t)lo_h_out, (uint64_t)stream, (uint64_t)flags, (uint64_t)lengths};
-    auto body = [&]() {
-        run_step(h, true, true, rgb, rgb_dtype, depth, ids, ids_dtype, B, hi_h_in, lo_h_in, mask, nullptr, record, ld, record + 4, ld,
-                 record + 6, ld, hi_h_out, lo_h_out);
-    };
+    c.hi_h_in = hi_h_in; c.lo_h_in = lo_h_in; c.mask = mask; c.hi_h_out = hi_h_out; c.lo_h_out = lo_h_out;
+    c.logits = record; c.vel = record + 4; c.stop = record + 6; c.ld_logits = c.ld_vel = c.ld_stop = 7;      // the three column blocks of the record
     // HCM_ACT_CHAIN_GRAPHS: one linear graph per chain (the development build's HCM_RGB_SERIAL=0 keeps the single forked graph; HCM_SEG_GRAPH=1 / 0 of that
     // build forces the choice for A/B runs)
     static const bool seg_off = (dev_env("HCM_RGB_SERIAL") && atoi(dev_env("HCM_RGB_SERIAL")) == 0) || (dev_env("HCM_SEG_GRAPH") && atoi(dev_env("HCM_SEG_GRAPH")) == 0);
     static const bool seg_on = dev_env("HCM_SEG_GRAPH") && atoi(dev_env("HCM_SEG_GRAPH")) != 0;
-    rc = run_graphed(h, key, stream, body, !seg_off && (seg_on || (flags & HCM_ACT_CHAIN_GRAPHS) != 0));
-    h->reuse_instruction = false;
-    h->host_frames = false;
+    rc = run_graphed(h, c, !seg_off && (seg_on || (flags & HCM_ACT_CHAIN_GRAPHS) != 0));
     if (rc == HCM_OK) { h->last_hi_batch = B; h->last_hi_L = L; } else drop_instruction_cache(h);
     return rc;
 }
@@ -1120,10 +1057,10 @@ int hcm_refresh_instruction(hcm_handle h, const void* ids, int ids_dtype, const 
             "hcm_refresh_instruction: the previous call on this handle was not an hcm_act step with this batch size and instruction length");
     for (int i = 0; i < n; ++i) REQUIRE(env_indices[i] >= 0 && env_indices[i] < B, HCM_ERR_ARG, "environment index out of range");
     if (n == 0) return HCM_OK;
-    h->cur_lens = lengths;
-    h->stream = (hipStream_t)stream;
+    FwdCall c = frames(nullptr, DT_F32, nullptr, ids, ids_dtype, B, L, stream);
+    c.lens = lengths;
     try {
-        run_refresh_instruction(h, ids, ids_dtype, B, env_indices, n);
+        run_refresh_instruction(h, c, env_indices, n);
     } catch (const std::exception& e) {
         return fail(h, HCM_ERR_HIP, e.what());
     }

@@ -9,20 +9,26 @@
 
 namespace hcm {
 
-int depth_final_spatial(const hcm_config& c);
-int depth_compress_channels(const hcm_config& c);
-
 struct Act { void* p = nullptr; int B = 0, H = 0, W = 0, C = 0; };
 
 struct Fwd {
     hcm_ctx* ctx;
+    const FwdCall& call;    // the call being enqueued: L, lens, the caller's stream, the per-call flags (model.h)
     Arena& ar;
     hipStream_t s;
     int dt;
     size_t esz;
     bool dry;
 
-    explicit Fwd(hcm_ctx* c) : ctx(c), ar(c->arena), s(c->stream), dt(c->dt_vla), esz(dt_size(c->dt_vla)), dry(c->arena.dry) {}
+    Fwd(hcm_ctx* c, const FwdCall& k) : ctx(c), call(k), ar(c->arena), s(k.stream), dt(c->dt_vla), esz(dt_size(c->dt_vla)), dry(c->arena.dry), T(k.T) {
+        val.on = k.val == FwdCall::kVal;
+        fval.on = k.val == FwdCall::kFlatVal;
+        val.oracle = k.oracle;
+        val.corrected = fval.corrected = k.corrected;
+        val.oracle_stop = fval.oracle_stop = k.oracle_stop;
+        fval.progress = k.progress_label;
+        val.result = fval.result = k.result;
+    }
 
     // switch the storage type of the sub-network being enqueued
     void use(int d) { dt = d; esz = dt_size(d); }
@@ -689,9 +695,9 @@ struct Fwd {
     // ---------------------------------------------------------------- BERT encoder
     void bert(const BertW& w, const void* ids, int ids_dt, int B, void* x, const int* lens) {
         const hcm_config& c = ctx->cfg;
-        // L is per call (ctx->cur_L <= cfg.instr_len); buffers are carved at the maximum length so that the workspace layout -- and with
+        // L is per call (call.L <= cfg.instr_len); buffers are carved at the maximum length so that the workspace layout -- and with
         // it the cached instruction stream of HCM_ACT_REUSE_INSTRUCTION -- does not move when L changes
-        const int L = ctx->cur_L, D = c.bert_hidden, rows = B * L;
+        const int L = call.L, D = c.bert_hidden, rows = B * L;
         const size_t rmax = (size_t)B * c.instr_len;
         void* qkv = alloc_t(rmax * 3 * D);
         void* ctxb = alloc_t(rmax * D);
@@ -938,7 +944,7 @@ struct Fwd {
         (void)hipFree(tmp);
     }
 
-    int T = 1;      // time steps packed in the batch (training / validation path); 1 = the per-step rollout call
+    const int T;    // time steps packed in the batch (training / validation path); 1 = the per-step rollout call (FwdCall::T)
 
     // ---------------------------------------------------------------- stages of Seq2Seq_HighLevel_CMA.forward
     struct HiBufs {
@@ -1042,7 +1048,7 @@ struct Fwd {
     void hi_ins_pre(int B, HiBufs& hb) {
         const hcm_config& c = ctx->cfg;
         const VlaW& v = ctx->hi.vla;
-        const int L = ctx->cur_L, d = c.d_model, rows = B * L;
+        const int L = call.L, d = c.d_model, rows = B * L;
         const size_t rmax = (size_t)B * c.instr_len;
         use(ctx->dt_vla);
         calib_slot = 3;
@@ -1201,9 +1207,9 @@ struct Fwd {
     void hi_bert(const void* ids, int ids_dt, int B, HiBufs& hb) {
         use(ctx->dt_bert);
         calib_slot = 0;
-        bert(ctx->hi.bert, ids, ids_dt, B, hb.emb, ctx->cur_lens);
+        bert(ctx->hi.bert, ids, ids_dt, B, hb.emb, call.lens);
         calib_slot = -1;
-        tap("hi.bert", hb.emb, true, {B, ctx->cur_L, ctx->cfg.bert_hidden});
+        tap("hi.bert", hb.emb, true, {B, call.L, ctx->cfg.bert_hidden});
         mark("bert.end");
         hi_ins_pre(B, hb);
         mark("bert.ins_pre_end");
@@ -1212,7 +1218,7 @@ struct Fwd {
     void hi_tail(int B, HiBufs& hb, const float* h_in, const float* mask, float* logits, int ld_logits, float* h_out) {
         const hcm_config& c = ctx->cfg;
         const HighW& w = ctx->hi;
-        const int L = ctx->cur_L, Lm = c.instr_len, d = c.d_model;
+        const int L = call.L, Lm = c.instr_len, d = c.d_model;
         const int dS = w.depth_S;
         const int ldx = hb.ldx;
         float* xh = hb.xh;
@@ -1245,7 +1251,7 @@ struct Fwd {
                 const VlaLayerW& ly = v.layers[l];
                 const bool last = l + 1 == v.layers.size();
                 VlaPost q;
-                q.q = hb.Q[l]; q.I = I; q.B = B; q.L = L; q.d_ff = c.d_ff; q.lens = ctx->cur_lens;
+                q.q = hb.Q[l]; q.I = I; q.B = B; q.L = L; q.d_ff = c.d_ff; q.lens = call.lens;
                 q.wo = ly.o.w; q.bo = ly.o.bias; q.w1 = ly.ff1.w; q.b1 = ly.ff1.bias; q.w2 = ly.ff2.w; q.b2 = ly.ff2.bias;
                 q.g1 = ly.ln_att.gamma; q.be1 = ly.ln_att.beta; q.g2 = ly.ln_ff.gamma; q.be2 = ly.ln_ff.beta;
                 // round 6: the layer's weights in fragment order, read straight into registers (bit-identical; HCM_NO_VLA_WFRAG=1 of the development
@@ -1260,7 +1266,7 @@ struct Fwd {
                     if (!q.fuse_att) {
                         void* att = attb[st] ? attb[st] : (attb[st] = alloc_t((size_t)B * Lm * d));
                         if (!dry) ck(launch_attention(hb.Q[l], kvl, (const char*)kvl + (size_t)d * esz, att, dt, B, c.vla_heads, L, Lk, d, 2 * d, 2 * d, d, B, s,
-                                                      l > 0 ? ctx->cur_lens : nullptr), "vla attention");
+                                                      l > 0 ? call.lens : nullptr), "vla attention");
                         q.att[st] = att;
                     }
                     q.kv[st] = kvl; q.Lk[st] = Lk;
@@ -1274,7 +1280,7 @@ struct Fwd {
             for (int st = 0; st < 2; ++st) {
                 tap(st == 0 ? "hi.vla_rgb" : "hi.vla_depth", outb[st][lastl], true, {B, L, d});
                 if (!pool_in_kernel && !dry)
-                    ck(launch_mean_rows(outb[st][lastl], xh + w.rnn.xcol(c.rgb_out + c.depth_out + st * d), dt, B, L, d, d, ldx, 1, s, ctx->cur_lens), "cross_pooler");
+                    ck(launch_mean_rows(outb[st][lastl], xh + w.rnn.xcol(c.rgb_out + c.depth_out + st * d), dt, B, L, d, d, ldx, 1, s, call.lens), "cross_pooler");
             }
         } else {
         // the two Visual_Ling_Attn calls (rgb, depth) are independent until the recurrent input: run them on two streams
@@ -1296,7 +1302,7 @@ struct Fwd {
                 // layer 0 attends over the visual tokens; deeper layers over the previous layer's (B, L, d) output, of which a ragged
                 // batch's sample owns the first lengths[b] rows only
                 if (!dry) ck(launch_attention(hb.Q[l], kvl, (const char*)kvl + (size_t)d * esz, att, dt, B, c.vla_heads, L, Lk, d, 2 * d, 2 * d, d, B, s,
-                                              l > 0 ? ctx->cur_lens : nullptr), "vla attention");
+                                              l > 0 ? call.lens : nullptr), "vla attention");
                 linear(ly.o, att, rows, d, t2, d, ACT_NONE, false, I, d);                 // queries + att
                 ln(t2, nullptr, ly.ln_att, nullptr, 0, att, rows, d, 1e-5f);             // MultiHeadAttention.layer_norm
                 linear(ly.ff1, att, rows, d, ffh, c.d_ff, ACT_RELU, false);
@@ -1310,7 +1316,7 @@ struct Fwd {
             }
             tap(stream == 0 ? "hi.vla_rgb" : "hi.vla_depth", out, true, {B, L, d});
             // cross_pooler: mean over all L tokens (:209-210) -> xh columns
-            if (!dry) ck(launch_mean_rows(out, xh + w.rnn.xcol(c.rgb_out + c.depth_out + stream * d), dt, B, L, d, d, ldx, 1, s, ctx->cur_lens), "cross_pooler");
+            if (!dry) ck(launch_mean_rows(out, xh + w.rnn.xcol(c.rgb_out + c.depth_out + stream * d), dt, B, L, d, d, ldx, 1, s, call.lens), "cross_pooler");
         }
         }
         // meanwhile (third stream): the early halves of both recurrent steps
@@ -1385,14 +1391,16 @@ struct Fwd {
 
     // hcm_refresh_instruction: recompute the cached instruction stream (hb.I, hb.Q of the last B-sized step) for the listed
     // environments only -- BERT + ins_fc/LN/PE + fc_q at batch n, rows copied into place
-    void refresh_instruction(const void* ids, int ids_dt, int B, const int32_t* idx, int n) {
+    void refresh_instruction(const int32_t* idx, int n) {
         const hcm_config& c = ctx->cfg;
+        const void* ids = call.ids;
+        const int ids_dt = call.ids_dt, B = call.rows;
         ar.reset();
         HiBufs hb = hi_alloc(B);                                  // same offsets as in step(): the persistent tensors
-        const int L = ctx->cur_L, d = c.d_model;
+        const int L = call.L, d = c.d_model;
         const size_t idsz = ids_dt == DT_I64 ? 8 : 4;
         char* sub_ids = (char*)ar.alloc((size_t)n * c.instr_len * idsz);
-        int* sub_lens = (ctx->cur_lens || dry) ? (int*)ar.alloc((size_t)n * sizeof(int)) : nullptr;
+        int* sub_lens = (call.lens || dry) ? (int*)ar.alloc((size_t)n * sizeof(int)) : nullptr;
         HiBufs hn;
         use(ctx->dt_bert);
         hn.emb = alloc_t((size_t)n * c.instr_len * c.bert_hidden);
@@ -1403,12 +1411,12 @@ struct Fwd {
         if (!dry) {
             for (int i = 0; i < n; ++i)
                 ck(hipMemcpyAsync(sub_ids + (size_t)i * L * idsz, (const char*)ids + (size_t)idx[i] * L * idsz, (size_t)L * idsz, hipMemcpyDeviceToDevice, s), "ids gather");
-            if (ctx->cur_lens)
+            if (call.lens)
                 for (int i = 0; i < n; ++i)
-                    ck(hipMemcpyAsync(sub_lens + i, ctx->cur_lens + idx[i], sizeof(int), hipMemcpyDeviceToDevice, s), "lengths gather");
+                    ck(hipMemcpyAsync(sub_lens + i, call.lens + idx[i], sizeof(int), hipMemcpyDeviceToDevice, s), "lengths gather");
         }
         use(ctx->dt_bert);
-        bert(ctx->hi.bert, sub_ids, ids_dt, n, hn.emb, ctx->cur_lens ? sub_lens : nullptr);
+        bert(ctx->hi.bert, sub_ids, ids_dt, n, hn.emb, call.lens ? sub_lens : nullptr);
         hi_ins_pre(n, hn);
         use(ctx->dt_vla);
         if (dry) return;                                          // (hcm_finalize's sizing pass: allocations only)
@@ -1427,11 +1435,11 @@ struct Fwd {
         const hcm_config& c = ctx->cfg;
         const hcm_cma_config& m = ctx->cma_cfg;
         const CmaW& w = ctx->cma;
-        const int L = ctx->cur_L, Lm = c.instr_len, Hi = m.instr_hidden, C = Hi * w.dirs, E = m.embedding_size;
+        const int L = call.L, Lm = c.instr_len, Hi = m.instr_hidden, C = Hi * w.dirs, E = m.embedding_size;
         const int H = c.hidden, hh = H / 2, rC = 2048 + 64, dS = w.depth_S, dC = w.depth_C;
         const int R = c.rnn_type == HCM_LSTM ? 2 : 1;
         const bool multi = ctx->concurrent && !ctx->taps_on;
-        hipStream_t main_s = ctx->stream;
+        hipStream_t main_s = call.stream;
         hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s;
         if (fval.on) {                                            // outputs the caller did not ask for still feed the criteria: workspace rows
             if (!out) out = alloc_f((size_t)B * c.num_actions);
@@ -1601,9 +1609,9 @@ struct Fwd {
         const hcm_s2s_config& m = ctx->s2s_cfg;
         const S2sW& w = ctx->s2s;
         const LowW& lw = ctx->lo;
-        const int L = ctx->cur_L, Lm = c.instr_len, Hi = m.instr_hidden, E = m.embedding_size;
+        const int L = call.L, Lm = c.instr_len, Hi = m.instr_hidden, E = m.embedding_size;
         const bool multi = ctx->concurrent && !ctx->taps_on;
-        hipStream_t main_s = ctx->stream;
+        hipStream_t main_s = call.stream;
         hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s;
         const int ldx = lw.rnn.in + c.hidden;
         if (fval.on) {                                            // outputs the caller did not ask for still feed the criteria: workspace rows
@@ -1693,7 +1701,7 @@ struct Fwd {
     void fork_join_begin(int n_aux) {
         if (dry || n_aux == 0) return;
         if (ctx->seg_mode && !ctx->seg_open) { hcm_ctx::SegOp op; op.kind = 0; op.n = n_aux; ctx->seg_prog.push_back(op); return; }
-        ck(hipEventRecord(ctx->ev_fork, ctx->stream), "fork record");
+        ck(hipEventRecord(ctx->ev_fork, call.stream), "fork record");
         for (int i = 0; i < n_aux; ++i) ck(hipStreamWaitEvent(ctx->aux[i], ctx->ev_fork, 0), "fork wait");
     }
     void fork_join_end(int n_aux) {
@@ -1701,7 +1709,7 @@ struct Fwd {
         if (ctx->seg_mode && !ctx->seg_open) { hcm_ctx::SegOp op; op.kind = 2; op.n = n_aux; ctx->seg_prog.push_back(op); return; }
         for (int i = 0; i < n_aux; ++i) {
             ck(hipEventRecord(ctx->ev_join[i], ctx->aux[i]), "join record");
-            ck(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0), "join wait");
+            ck(hipStreamWaitEvent(call.stream, ctx->ev_join[i], 0), "join wait");
         }
     }
     void on(hipStream_t st) { s = st; }
@@ -1749,7 +1757,7 @@ struct Fwd {
         if (do_hi) hb = hi_alloc(B);
         if (do_lo) lb = lo_alloc(B);
         const bool multi = ctx->concurrent && !ctx->taps_on;    // taps allocate/synchronise: keep them single-stream
-        hipStream_t main_s = ctx->stream;
+        hipStream_t main_s = call.stream;
         int64_t* val_subtask = nullptr;
         if (val.on) {
             // outputs the caller did not ask for still feed the criteria: workspace rows
@@ -1775,7 +1783,7 @@ struct Fwd {
         constexpr int skip = 0;
 #endif
         if (multi) fork_join_begin(n_fork);
-        if (ctx->host_frames && !dry) {
+        if (call.host_frames && !dry) {
             // HCM_ACT_HOST_FRAMES: each chain's frames come up from the pinned host buffers on that chain's own stream, so BERT and the other
             // chain's compute run beside the copies.  The RGB frames go FIRST: the copy engine works in submission order and the RGB trunks are
             // the long chain (the depth chain's kernels fill gaps, they can start 0.3 ms later)
@@ -1804,7 +1812,7 @@ struct Fwd {
         mark("bert.start");
         // (the workspace layout is identical from step to step, so hb.I / hb.Q of the previous step are still in place when the
         //  caller declares the instructions unchanged)
-        if (do_hi && !(skip & 8) && !(ctx->reuse_instruction && !dry)) hi_bert(ids, ids_dt, B, hb);
+        if (do_hi && !(skip & 8) && !(call.reuse_instruction && !dry)) hi_bert(ids, ids_dt, B, hb);
         chain_end();
         // chains 2 and 4: the two depth trunks (small, latency-bound kernels that fill the gaps of the RGB chains)
         on(a1);
@@ -1841,7 +1849,7 @@ struct Fwd {
         // chain 1: the low-level RGB trunk
         static const int rgb_serial = dev_env("HCM_RGB_SERIAL") ? atoi(dev_env("HCM_RGB_SERIAL")) : 1;
         if (val.on) { mark("rgb.hi_end"); on(a0); mark("lorgb.start"); }
-        else on((rgb_serial || ctx->host_frames) ? main_s : a0);        // (staged frames: behind their copy)
+        else on((rgb_serial || call.host_frames) ? main_s : a0);        // (staged frames: behind their copy)
         if (do_hi && do_lo && !rpair && !rshare && !ctx->cfg.ablate_rgb && !(skip & 2)) lo_rgb(rgb, rgb_dt, B, lb);
         if (val.on) mark("lorgb.end");
         on(main_s);
@@ -1892,56 +1900,18 @@ struct Fwd {
     }
 };
 
-// entry point used by api.cpp
-void run_step(hcm_ctx* ctx, bool do_hi, bool do_lo, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt,
-              int B, const float* hi_h_in, const float* lo_h_in, const float* mask, const int64_t* subtask, float* logits,
-              int ld_logits, float* vel, int ld_vel, float* stop, int ld_stop, float* hi_h_out, float* lo_h_out, int T) {
-    Fwd f(ctx);
-    f.T = T;
-    f.step(do_hi, do_lo, rgb, rgb_dt, depth, ids, ids_dt, B, hi_h_in, lo_h_in, mask, subtask, logits, ld_logits, vel, ld_vel,
-           stop, ld_stop, hi_h_out, lo_h_out);
+// entry points used by api.cpp (model.h)
+void run_forward(hcm_ctx* ctx, const FwdCall& c) {
+    Fwd f(ctx, c);
+    if (ctx->kind == 1) f.cma_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.lo_h_in, c.mask, c.vel, c.stop, c.lo_h_out);
+    else if (ctx->kind == 2) f.s2s_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.Bi, c.lo_h_in, c.mask, c.vel, c.stop, c.progress, c.lo_h_out);
+    else f.step(c.do_hi, c.do_lo, c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.hi_h_in, c.lo_h_in, c.mask, c.subtask, c.logits, c.ld_logits,
+                c.vel, c.ld_vel, c.stop, c.ld_stop, c.hi_h_out, c.lo_h_out);
 }
 
-// hcm_val_step; null label pointers = the sizing pass
-void run_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, const int64_t* oracle,
-                  const float* corrected, const float* oracle_stop, const float* hi_h_in, const float* lo_h_in, const float* mask, float* result,
-                  float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop) {
-    Fwd f(ctx);
-    f.T = T;
-    f.val.on = true;
-    f.val.oracle = oracle; f.val.corrected = corrected; f.val.oracle_stop = oracle_stop; f.val.result = result;
-    f.step(true, true, rgb, rgb_dt, depth, ids, ids_dt, T * N, hi_h_in, lo_h_in, mask, nullptr, logits, ctx->cfg.num_actions, vel,
-           ctx->cfg.lo_actions, stop, 1, hi_h_out, lo_h_out);
+void run_refresh_instruction(hcm_ctx* ctx, const FwdCall& c, const int32_t* idx, int n) {
+    Fwd f(ctx, c);
+    f.refresh_instruction(idx, n);
 }
 
-}  // namespace hcm
-
-namespace hcm {
-void run_refresh_instruction(hcm_ctx* ctx, const void* ids, int ids_dt, int B, const int32_t* idx, int n) {
-    Fwd f(ctx);
-    f.refresh_instruction(ids, ids_dt, B, idx, n);
-}
-void run_cma(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, const float* h_in,
-             const float* mask, float* out, float* stop, float* h_out, int T) {
-    Fwd f(ctx);
-    f.T = T;
-    f.cma_step(rgb, rgb_dt, depth, ids, ids_dt, B, h_in, mask, out, stop, h_out);
-}
-void run_s2s(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B, int Bi, const float* h_in,
-             const float* mask, float* out, float* stop, float* progress, float* h_out, int T) {
-    Fwd f(ctx);
-    f.T = T;
-    f.s2s_step(rgb, rgb_dt, depth, ids, ids_dt, B, Bi, h_in, mask, out, stop, progress, h_out);
-}
-// hcm_flat_val_step on a CMANet (Bi unused, progress pointers null) or Seq2SeqNet handle; null label pointers = the sizing pass
-void run_flat_val_step(hcm_ctx* ctx, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int T, int N, int Bi,
-                       const float* corrected, const float* oracle_stop, const float* progress, const float* h_in, const float* mask, float* result,
-                       float* h_out, float* out, float* stop, float* progress_hat) {
-    Fwd f(ctx);
-    f.T = T;
-    f.fval.on = true;
-    f.fval.corrected = corrected; f.fval.oracle_stop = oracle_stop; f.fval.progress = progress; f.fval.result = result;
-    if (ctx->kind == 1) f.cma_step(rgb, rgb_dt, depth, ids, ids_dt, T * N, h_in, mask, out, stop, h_out);
-    else f.s2s_step(rgb, rgb_dt, depth, ids, ids_dt, T * N, Bi, h_in, mask, out, stop, progress_hat, h_out);
-}
 }  // namespace hcm

@@ -181,6 +181,39 @@ struct Arena {
 
 struct Tap { float* dev = nullptr; size_t cap = 0; size_t n = 0; Shape shape; };
 
+// One forward call, completely: an entry point of api.cpp names the fields it sets and hands the descriptor to run_forward() (forward.cpp); the
+// sizing passes of hcm_finalize leave every pointer null.  Nothing about a call travels through hcm_ctx.
+struct FwdCall {
+    bool do_hi = false, do_lo = false;        // HCM handle: the models that run; a CMANet / Seq2SeqNet handle (hcm_ctx::kind) runs its one model
+    const void* rgb = nullptr; int rgb_dt = DT_F32;
+    const float* depth = nullptr;
+    const void* ids = nullptr; int ids_dt = DT_I64;
+    const int* lens = nullptr;                // optional per-row instruction lengths (device, [rows]); null = all L
+    int rows = 0;                             // frames: B of a step, T * N of a sequence call (time-major)
+    int T = 1;                                // time steps packed in the rows; 1 = the per-step call
+    int Bi = 0;                               // Seq2SeqNet: instruction rows, `rows` or 1
+    int L = 0;                                // instruction length (<= cfg.instr_len); unused by the low-level model alone
+    hipStream_t stream = nullptr;             // the caller's stream
+    bool reuse_instruction = false;           // HCM_ACT_REUSE_INSTRUCTION: skip BERT + the instruction stream, reuse what the previous step left in the workspace
+    bool host_frames = false;                 // HCM_ACT_HOST_FRAMES: rgb / depth are pinned host pointers, staged per chain into hcm_ctx::stage_*
+    // recurrent state in / out per model; the one model of a flat handle uses the lo_ pair
+    const float* hi_h_in = nullptr; const float* lo_h_in = nullptr;
+    float* hi_h_out = nullptr; float* lo_h_out = nullptr;
+    const float* mask = nullptr;
+    const int64_t* subtask = nullptr;         // the low-level model alone: the caller's sub-task per row
+    // outputs with their leading dimensions (hcm_act_ex: the three column blocks of the record); a flat handle writes `out` through vel
+    float* logits = nullptr; int ld_logits = 0;
+    float* vel = nullptr; int ld_vel = 0;
+    float* stop = nullptr; int ld_stop = 0;
+    float* progress = nullptr;                // Seq2SeqNet with the progress monitor: progress_hat (rows, 1) or null
+    // the two validation forms: labels and the (8,) result row.  Outputs left null then live in the workspace; null labels = a sizing pass
+    enum Val { kNoVal, kVal, kFlatVal } val = kNoVal;      // hcm_val_step / hcm_flat_val_step
+    const int64_t* oracle = nullptr;          // kVal: vln_oracle_action_sensor
+    const float* corrected = nullptr; const float* oracle_stop = nullptr;
+    const float* progress_label = nullptr;    // kFlatVal with the progress monitor: observations["progress"]
+    float* result = nullptr;
+};
+
 }  // namespace hcm
 
 struct hcm_ctx {
@@ -217,11 +250,10 @@ struct hcm_ctx {
     unsigned long long* marks_dev = nullptr;
     std::vector<std::string> mark_names;
     std::map<std::string, hcm::Tap> taps;
-    hipStream_t stream = nullptr;   // the caller's stream of the current call
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};   // side streams of the encoder chains (forward.cpp step())
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
     bool concurrent = true;
-    // hipGraph cache of the fused step (hcm_act): keyed by (B, dtypes, every pointer argument).  A key is run eagerly the
+    // hipGraph cache of the fused step (hcm_act): keyed by every field of the call's FwdCall (api.cpp call_key).  A key is run eagerly the
     // first time it is seen and captured (all forked streams included) the second time; replays cost one graph launch.
     // Round 4: the fused step is replayed as LINEAR graphs, one per chain, stitched by events outside the graphs.  hipGraphLaunch of a graph
     // captured with forked streams costs the host ~2.1 us per node (0.7-0.8 ms for the step's ~240 nodes: at B = 1 the step was bounded by
@@ -245,14 +277,8 @@ struct hcm_ctx {
     bool use_graph = true;
     int64_t graph_launches = 0, eager_launches = 0;
     bool failed = false;            // a launch failed during the current forward
-    // hcm_act_ex(HCM_ACT_REUSE_INSTRUCTION): skip BERT + the instruction stream of Visual_Ling_Attn and reuse the tensors the
-    // previous step left in the workspace (same batch size required); set per call
-    bool reuse_instruction = false;
-    // HCM_ACT_HOST_FRAMES: rgb / depth of the current hcm_act_ex call are host pointers; staged per chain into these device buffers
-    bool host_frames = false;
-    void* stage_rgb = nullptr; float* stage_depth = nullptr;
+    void* stage_rgb = nullptr; float* stage_depth = nullptr;      // HCM_ACT_HOST_FRAMES: device staging of the caller's pinned host frames (FwdCall::host_frames)
     int last_hi_batch = -1, last_hi_L = -1;   // shape of the cached instruction stream; -1 = none (invalidated by every other entry point)
-    int cur_L = 0;                  // instruction length of the current call (<= cfg.instr_len)
     // fp16 range calibration (hcm_finalize's synthetic batch, hcm_calibrate's caller batch): while `calib` is set the forward code
     // reduces max |x| / non-finite counts of every GEMM output of the fp16 sub-networks into calib_buf[2 * slot] (0 BERT, 1 depth trunks)
     bool calib = false;
@@ -274,5 +300,24 @@ struct hcm_ctx {
     float depth_fold[kDepthPos];
     float rgb_fold = 1.f;
     int range_fold = 0;                  // hcm_query(HCM_RANGE_FOLD): bit 1 depth, bit 2 RGB
-    const int* cur_lens = nullptr;  // optional per-environment instruction lengths of the current call (device, [B]); null = all L
 };
+
+namespace hcm {
+// weights.cpp: expected state_dict keys / shapes per model (create), device weights in the plan's storage types (finalize, re-builds)
+void build_spec_high(hcm_ctx* ctx);
+void build_spec_low(hcm_ctx* ctx);
+void build_spec_cma(hcm_ctx* ctx);
+void build_spec_s2s(hcm_ctx* ctx);
+void prepare_high(hcm_ctx* ctx);
+void prepare_low(hcm_ctx* ctx);
+void prepare_cma(hcm_ctx* ctx);
+void prepare_s2s(hcm_ctx* ctx);
+int depth_final_spatial(const hcm_config& c);
+int depth_compress_channels(const hcm_config& c);
+// forward.cpp: enqueue one call on its stream (dry arena: allocations only); throws std::runtime_error when a launch fails
+void run_forward(hcm_ctx* ctx, const FwdCall& call);
+// hcm_refresh_instruction: ids, ids_dt, rows, L, lens and stream of `call`, for the n environments idx[0..n)
+void run_refresh_instruction(hcm_ctx* ctx, const FwdCall& call, const int32_t* idx, int n);
+// comm.cpp
+void comm_destroy(hcm_ctx* ctx);
+}  // namespace hcm

@@ -13,18 +13,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import _TORCH_DT, _EngineBase, _np32, _ptr       # noqa: F401  (_np32: importable from here as before)
 from .config import HCMConfig
-
-_TORCH_DT = {torch.float32: _lib.HCM_F32, torch.uint8: _lib.HCM_U8, torch.int32: _lib.HCM_I32, torch.int64: _lib.HCM_I64}
-
 
 _SUB_SLOTS = {"depth": 0, "bert": 1, "vla": 2, "rgb": 3}
 _SUB_DT = {"fp32": _lib.HCM_F32, "bf16": _lib.HCM_BF16, "fp16": _lib.HCM_F16}
-
-
-def _ptr(t):
-    """device pointer of an optional tensor (None -> NULL)"""
-    return None if t is None else t.data_ptr()
 
 
 def _to_struct(cfg: HCMConfig, max_batch, precision, build_high, build_low, sub_precision=None, max_instr_len=None, keep_host_weights=False,
@@ -59,16 +52,7 @@ def _to_struct(cfg: HCMConfig, max_batch, precision, build_high, build_low, sub_
     return s
 
 
-def _np32(v):
-    if isinstance(v, torch.Tensor):
-        v = v.detach().cpu().numpy()
-    v = np.asarray(v)
-    if v.dtype == np.int64:
-        return np.require(v, requirements="C"), _lib.HCM_I64          # keeps 0-d (num_batches_tracked) 0-d
-    return np.require(v, dtype=np.float32, requirements="C"), _lib.HCM_F32
-
-
-class HCMEngine:
+class HCMEngine(_EngineBase):
     """Owns one libhcm handle (weights + workspace) on one GPU.  One engine per device per thread."""
 
     def __init__(self, cfg: HCMConfig, high_level_state_dict=None, low_level_state_dict=None, max_batch=64,
@@ -101,7 +85,6 @@ class HCMEngine:
         # fp16 range safety: hcm_finalize checks the fp16 sub-networks on a synthetic batch and repairs what would overflow (`range_fold`,
         # `fp16_fallback`); keep_host_weights=True keeps the f32 host copies so that `calibrate(observations)` can repeat the check -- and
         # the repair -- on real observations
-        self._graph = bool(graph)
         if chain_graphs not in ("auto", True, False):
             raise ValueError('chain_graphs must be "auto", True or False')
         self._chain_graphs = chain_graphs
@@ -112,43 +95,16 @@ class HCMEngine:
         self._gather_B = 0                              # per-rank batch of the library collective (act(gather=True)), 0 before the first such call
         self._gather_called = False
         self.guard_alarm = 0                            # deferred alarms of act(gather=True) steps, see guard_check()
-        self._gstream = None
-        self._static = None
         cfg.validate()
-        self.cfg = cfg
-        self.max_batch = max_batch
         self.precision = precision
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._lib = _lib.lib()
-        self._h = C.c_void_p()
         self.has_high = high_level_state_dict is not None
         self.has_low = low_level_state_dict is not None
-        with torch.cuda.device(self.device):
-            st = _to_struct(cfg, max_batch, precision, self.has_high, self.has_low, sub_precision, self.max_instr_len, keep_host_weights, share_trunks)
-            _lib.check(self._lib.hcm_create(C.byref(st), C.byref(self._h)))
-            try:
-                # load_state_dict(strict=True) semantics (hierarchical_trainer.py:343-345)
-                for model, sd in ((_lib.HCM_HIGH, high_level_state_dict), (_lib.HCM_LOW, low_level_state_dict)):
-                    if sd is None:
-                        continue
-                    for k, v in sd.items():
-                        if k.endswith(("embeddings.position_ids", "embeddings.token_type_ids")):
-                            continue        # BertEmbeddings buffers of some transformers versions, not parameters
-                        a, dt = _np32(v)
-                        shape = (C.c_int64 * max(1, a.ndim))(*a.shape)
-                        _lib.check(self._lib.hcm_load_tensor(self._h, model, k.encode(), a.ctypes.data_as(C.c_void_p), dt,
-                                                             shape, a.ndim), self._h)
-                _lib.check(self._lib.hcm_finalize(self._h), self._h)
-            except Exception:
-                self._lib.hcm_destroy(self._h)
-                self._h = C.c_void_p()
-                raise
-
-    def query(self, what):
-        out = C.c_int64()
-        with torch.cuda.device(self.device):       # (HCM_STEP_NONFINITE waits for the handle's device)
-            _lib.check(self._lib.hcm_query(self._h, what, C.byref(out)), self._h)
-        return out.value
+        st = _to_struct(cfg, max_batch, precision, self.has_high, self.has_low, sub_precision, self.max_instr_len, keep_host_weights, share_trunks)
+        # load_state_dict(strict=True) semantics (hierarchical_trainer.py:343-345); BertEmbeddings' position_ids / token_type_ids are buffers of
+        # some transformers versions, not parameters
+        self._open(cfg, max_batch, device, graph, "hcm_create", st,
+                   ((model, k, v) for model, sd in ((_lib.HCM_HIGH, high_level_state_dict), (_lib.HCM_LOW, low_level_state_dict)) if sd is not None
+                    for k, v in sd.items() if not k.endswith(("embeddings.position_ids", "embeddings.token_type_ids"))))
 
     def _guard_poll(self, stream, defer=False):
         """Every `guard_every` act() calls: non-blocking read of the overflow guard (the value is the one an EARLIER poll enqueued).
@@ -191,10 +147,6 @@ class HCMEngine:
         self._gather_B = 0
 
     @property
-    def num_recurrent_layers(self):
-        return self.query(_lib.HCM_NUM_RECURRENT_LAYERS)
-
-    @property
     def fp16_fallback(self):
         """Sub-networks the range calibration moved from fp16 to bf16 storage: subset of {"bert", "depth", "rgb", "vla"}."""
         bits = self.query(_lib.HCM_FP16_FALLBACK)
@@ -211,13 +163,6 @@ class HCMEngine:
                 "rgb_max_abs": self.query(_lib.HCM_CALIB_MAX_RGB), "vla_max_abs": self.query(_lib.HCM_CALIB_MAX_VLA),
                 "non_finite": self.query(_lib.HCM_CALIB_NONFINITE), "fp16_fallback": sorted(self.fp16_fallback),
                 "range_fold": sorted(self.range_fold)}
-
-    def nonfinite_steps(self):
-        """Overflow guard (hcm_query(HCM_STEP_NONFINITE)): number of (sample, recurrent step) pairs since construction whose gate
-        pre-activations were not all finite -- an fp16 overflow or a NaN anywhere upstream of the state encoders ends up there, and the
-        squashing cell would otherwise turn it into finite garbage.  0 on a healthy engine.  Synchronises the device: call it per episode
-        or per evaluation, not per step."""
-        return self.query(_lib.HCM_STEP_NONFINITE)
 
     def comm_init(self, group=None):
         """Create the library's own RCCL communicator over the ranks of a torch.distributed process group (one process per GPU): rank 0 draws the
@@ -266,25 +211,7 @@ class HCMEngine:
         self._guard_tick = 0
         return self.calibration_report()
 
-    def close(self):
-        if self._h:
-            self._lib.hcm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # ---- helpers
-    def _dev(self, t, dtypes):
-        if not isinstance(t, torch.Tensor):
-            t = torch.as_tensor(np.asarray(t))
-        if t.dtype not in dtypes:
-            t = t.to(dtypes[0])
-        return t.to(self.device, non_blocking=True).contiguous()
-
     def _host_frame(self, t, dtypes, name):
         # HCM_ACT_HOST_FRAMES: the library copies the frames itself, chain by chain -- they must be page-locked host tensors as they are
         if not isinstance(t, torch.Tensor) or t.device.type != "cpu" or not t.is_pinned() or not t.is_contiguous() or t.dtype not in dtypes:
@@ -330,10 +257,6 @@ class HCMEngine:
         if h.dim() != 3 or h.shape[0] != R or h.shape[2] != self.cfg.hidden or (B is not None and h.shape[1] != B):
             raise ValueError(f"hidden state must be ({R},{B if B is not None else 'N'},{self.cfg.hidden}), got {tuple(h.shape)}")
         return h
-
-    @staticmethod
-    def _stream():
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     # ---- the three calls
     def high_forward(self, observations, hidden, masks):
@@ -486,11 +409,7 @@ class HCMEngine:
             os_ = self._dev(oracle_stop, (torch.float32,))
             if tuple(ca.shape) != (TN, self.cfg.lo_actions) or os_.numel() != TN:
                 raise ValueError(f"corrected_actions must be ({TN},{self.cfg.lo_actions}) and oracle_stop ({TN},1), got {tuple(ca.shape)} and {tuple(os_.shape)}")
-            if result is None:
-                result = torch.empty(8, device=self.device, dtype=torch.float32)
-            elif (not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.numel() != 8 or not result.is_contiguous()
-                  or result.device.type != self.device.type or (self.device.index is not None and result.device.index != self.device.index)):
-                raise ValueError("result must be a contiguous (8,) float32 tensor on the engine's device")
+            result = self._result(result)
             hh2, lh2 = torch.empty_like(hh), torch.empty_like(lh)
             logits = vel = stop = None
             if return_outputs:
@@ -509,7 +428,7 @@ class HCMEngine:
     def check_val_result(result):
         """Host-side check of one or more val_step results ((8,) or (n,8), any device; synchronises if on the GPU): raises ValueError when a call
         saw vln_oracle_action_sensor values outside [0, num_sub_tasks] (result[6]).  Returns the results as a CPU tensor."""
-        r = torch.as_tensor(result).detach().to("cpu", torch.float32).reshape(-1, 8)
+        r = _EngineBase.check_val_result(result)
         bad = r[:, 6]
         if bool((bad != 0).any()):
             where = [int(i) for i in torch.nonzero(bad).reshape(-1)]
@@ -616,19 +535,6 @@ class HCMEngine:
             else:
                 _lib.check(self._lib.hcm_refresh_instruction(self._h, ids.data_ptr(), _TORCH_DT[ids.dtype], _ptr(lens), B, L,
                                                              idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size, self._stream()), self._h)
-
-    # ---- debug taps
-    def enable_taps(self, on=True):
-        _lib.check(self._lib.hcm_debug_enable_taps(self._h, int(on)), self._h)
-
-    def get_tap(self, name):
-        n = C.c_int64()
-        shape = (C.c_int64 * 4)()
-        _lib.check(self._lib.hcm_debug_get_tap(self._h, name.encode(), None, 0, C.byref(n), shape), self._h)
-        buf = np.empty(n.value, dtype=np.float32)
-        _lib.check(self._lib.hcm_debug_get_tap(self._h, name.encode(), buf.ctypes.data_as(C.c_void_p), n.value,
-                                               C.byref(n), shape), self._h)
-        return buf.reshape([d for d in shape if d > 0])
 
 
 class _ModelBase:

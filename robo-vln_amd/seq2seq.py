@@ -9,15 +9,12 @@ The reference's GRU instruction encoder raises IndexError at batch 1 (`final_sta
 seq2seq.py:163 indexes shape[1]); the library serves batch 1 with the value a larger batch gives for that row.
 """
 import ctypes as C
-import os
 
-import numpy as np
 import torch
 
 from . import _lib
-from .cma import _val_labels
+from ._engine import _TORCH_DT, _FlatEngine, _ptr, _val_labels
 from .config import S2SConfig
-from .policy import _TORCH_DT, _np32, _ptr
 
 
 def _to_struct(cfg: S2SConfig, max_batch, precision):
@@ -42,66 +39,15 @@ def _to_struct(cfg: S2SConfig, max_batch, precision):
     return s
 
 
-class S2SEngine:
+class S2SEngine(_FlatEngine):
     """Owns one libhcm Seq2SeqNet handle (weights + workspace) on one GPU."""
 
     def __init__(self, cfg: S2SConfig, state_dict, max_batch=64, precision="fp16", device=None, graph=False):
         """graph=True: forward() runs on an engine-owned stream with engine-owned static I/O buffers so that libhcm replays one
         captured hipGraph per step; the returned tensors then alias those buffers and stay valid until the second-next call."""
-        self._graph = bool(graph)
-        self._gstream = None
-        self._static = None
         cfg.validate()
-        self.cfg = cfg
-        self.max_batch = max_batch
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._lib = _lib.lib()
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            st = _to_struct(cfg, max_batch, precision)
-            _lib.check(self._lib.hcm_s2s_create(C.byref(st), C.byref(self._h)))
-            try:
-                for k, v in state_dict.items():          # load_state_dict(strict=True) semantics
-                    a, dt = _np32(v)
-                    shape = (C.c_int64 * max(1, a.ndim))(*a.shape)
-                    _lib.check(self._lib.hcm_load_tensor(self._h, _lib.HCM_S2S, k.encode(), a.ctypes.data_as(C.c_void_p), dt, shape, a.ndim), self._h)
-                _lib.check(self._lib.hcm_finalize(self._h), self._h)
-            except Exception:
-                self._lib.hcm_destroy(self._h)
-                self._h = C.c_void_p()
-                raise
-
-    def query(self, what):
-        out = C.c_int64()
-        with torch.cuda.device(self.device):       # (HCM_STEP_NONFINITE waits for the handle's device)
-            _lib.check(self._lib.hcm_query(self._h, what, C.byref(out)), self._h)
-        return out.value
-
-    def nonfinite_steps(self):
-        """Overflow guard, as HCMEngine.nonfinite_steps (hcm_query(HCM_STEP_NONFINITE)); synchronises the device."""
-        return self.query(_lib.HCM_STEP_NONFINITE)
-
-    @property
-    def num_recurrent_layers(self):
-        return self.query(_lib.HCM_NUM_RECURRENT_LAYERS)
-
-    def close(self):
-        if self._h:
-            self._lib.hcm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _dev(self, t, dtypes):
-        if not isinstance(t, torch.Tensor):
-            t = torch.as_tensor(np.asarray(t))
-        if t.dtype not in dtypes:
-            t = t.to(dtypes[0])
-        return t.to(self.device, non_blocking=True).contiguous()
+        self._open(cfg, max_batch, device, graph, "hcm_s2s_create", _to_struct(cfg, max_batch, precision),
+                   ((_lib.HCM_S2S, k, v) for k, v in state_dict.items()))
 
     def _inputs(self, observations, rows):
         c = self.cfg
@@ -130,40 +76,31 @@ class S2SEngine:
 
     def forward(self, observations, hidden, masks):
         """-> (output (B,num_actions), stop_out (B,1), progress_hat (B,1) or None, rnn_hidden_states)"""
-        c = self.cfg
         with torch.cuda.device(self.device):
             rgb, depth, ids, B = self._inputs(observations, None)
-            h_in = self._dev(hidden, (torch.float32,))
-            R = self.num_recurrent_layers
-            if tuple(h_in.shape) != (R, B, c.hidden):
-                raise ValueError(f"rnn_hidden_states must be ({R},{B},{c.hidden}), got {tuple(h_in.shape)}")
-            m = self._dev(masks, (torch.float32,)).reshape(B, -1)[:, 0].contiguous()   # masks[:,0] (seq2seq.py:172)
+            h_in, m = self._state_mask(hidden, masks, B, B)
+
+            def call(rgb_, depth_, ids_, h_in_, m_, out, stop, prog, h_out, st):
+                _lib.check(self._lib.hcm_s2s_forward(self._h, rgb_.data_ptr(), _TORCH_DT[rgb.dtype], depth_.data_ptr(), ids_.data_ptr(),
+                                                     _TORCH_DT[ids.dtype], B, ids.shape[0], ids.shape[1], h_in_.data_ptr(), m_.data_ptr(),
+                                                     out.data_ptr(), stop.data_ptr(), _ptr(prog), h_out.data_ptr(), st), self._h)
             if self._graph:
-                return self._forward_graph(rgb, depth, ids, h_in, m, B)
+                return self._forward_graph(call, rgb, depth, ids, h_in, m, B, progress=self.cfg.progress_monitor)
             out, stop, prog = self._outputs(B)
             h_out = torch.empty_like(h_in)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(self._lib.hcm_s2s_forward(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(),
-                                                 _TORCH_DT[ids.dtype], B, ids.shape[0], ids.shape[1], h_in.data_ptr(), m.data_ptr(),
-                                                 out.data_ptr(), stop.data_ptr(), _ptr(prog), h_out.data_ptr(), st), self._h)
+            call(rgb, depth, ids, h_in, m, out, stop, prog, h_out, self._stream())
         return out, stop, prog, h_out
 
     def forward_seq(self, observations, hidden, masks, T, N):
         """Training / validation path (RNNStateEncoder.seq_forward): observations hold T*N rows, time-major; hidden (R,N,hidden); masks (T*N,)."""
-        c = self.cfg
         with torch.cuda.device(self.device):
             rgb, depth, ids, B = self._inputs(observations, T * N)
-            h_in = self._dev(hidden, (torch.float32,))
-            R = self.num_recurrent_layers
-            if tuple(h_in.shape) != (R, N, c.hidden):
-                raise ValueError(f"rnn_hidden_states must be ({R},{N},{c.hidden}), got {tuple(h_in.shape)}")
-            m = self._dev(masks, (torch.float32,)).reshape(B, -1)[:, 0].contiguous()
+            h_in, m = self._state_mask(hidden, masks, B, N)
             out, stop, prog = self._outputs(B)
             h_out = torch.empty_like(h_in)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             _lib.check(self._lib.hcm_s2s_forward_seq(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(),
                                                      _TORCH_DT[ids.dtype], T, N, ids.shape[0], ids.shape[1], h_in.data_ptr(), m.data_ptr(),
-                                                     out.data_ptr(), stop.data_ptr(), _ptr(prog), h_out.data_ptr(), st), self._h)
+                                                     out.data_ptr(), stop.data_ptr(), _ptr(prog), h_out.data_ptr(), self._stream()), self._h)
         return out, stop, prog, h_out
 
     def val_step(self, observations, corrected_actions, oracle_stop, hidden, masks, result=None, return_outputs=False):
@@ -186,69 +123,13 @@ class S2SEngine:
                     raise ValueError(f"observations['progress'] must be ({B},) or ({B},1), got {tuple(prog.shape)}")
             h_out = torch.empty_like(h_in)
             out, stop, prog_hat = self._outputs(B) if return_outputs else (None, None, None)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            st = self._stream()
             _lib.check(self._lib.hcm_flat_val_step(self._h, rgb.data_ptr(), _TORCH_DT[rgb.dtype], depth.data_ptr(), ids.data_ptr(), _TORCH_DT[ids.dtype],
                                                    B // N, N, ids.shape[0], ids.shape[1], ca.data_ptr(), os_.data_ptr(), _ptr(prog), h_in.data_ptr(),
                                                    m.data_ptr(), result.data_ptr(), h_out.data_ptr(), _ptr(out), _ptr(stop), _ptr(prog_hat), st), self._h)
         if return_outputs:
             return result, h_out, (out, stop, prog_hat)
         return result, h_out
-
-    @staticmethod
-    def check_val_result(result):
-        """One or more val_step results ((8,) or (n,8), any device; synchronises if on the GPU) as a CPU tensor: the one read of an epoch."""
-        return torch.as_tensor(result).detach().to("cpu", torch.float32).reshape(-1, 8)
-
-    def _forward_graph(self, rgb, depth, ids, h_in, m, B):
-        c = self.cfg
-        if self._gstream is None:
-            self._gstream = torch.cuda.Stream(device=self.device)
-        st = self._static
-        Bi, L = ids.shape
-        if st is None or st["B"] != B or st["Bi"] != Bi or st["rgb"].dtype != rgb.dtype or st["ids"].dtype != ids.dtype:
-            st = {"B": B, "Bi": Bi, "tick": 0, "rgb": torch.empty_like(rgb), "depth": torch.empty_like(depth),
-                  "ids": torch.empty(Bi * c.instr_len, device=self.device, dtype=ids.dtype),
-                  "mask": torch.empty_like(m), "h": [torch.zeros_like(h_in) for _ in range(2)],
-                  "out": [torch.empty(B, c.num_actions, device=self.device) for _ in range(2)],
-                  "stop": [torch.empty(B, 1, device=self.device) for _ in range(2)],
-                  "prog": [torch.empty(B, 1, device=self.device) if c.progress_monitor else None for _ in range(2)]}
-            self._static = st
-        cur, gs = torch.cuda.current_stream(), self._gstream
-        gs.wait_stream(cur)
-        # observation buffers whose addresses repeat from the previous call are read in place (see HCMEngine._act_graph)
-        ptrs = (rgb.data_ptr(), depth.data_ptr(), ids.data_ptr())
-        seen = st.setdefault("seen_ptrs", [])
-        direct = ptrs in seen and not os.environ.get("HCM_NO_DIRECT_OBS")
-        if ptrs in seen:
-            seen.remove(ptrs)
-        seen.append(ptrs)
-        del seen[:-4]
-        st["hold"] = (rgb, depth, ids)
-        g_rgb, g_depth, g_ids = (rgb, depth, ids) if direct else (st["rgb"], st["depth"], st["ids"][:Bi * L].view(Bi, L))
-        with torch.cuda.stream(gs):
-            i = st["tick"] & 1
-            for dst, src in ((g_rgb, rgb), (g_depth, depth), (g_ids, ids), (st["mask"], m), (st["h"][1 - i], h_in)):
-                if dst.data_ptr() != src.data_ptr():
-                    dst.copy_(src, non_blocking=True)
-            _lib.check(self._lib.hcm_s2s_forward(self._h, g_rgb.data_ptr(), _TORCH_DT[rgb.dtype], g_depth.data_ptr(),
-                                                 g_ids.data_ptr(), _TORCH_DT[ids.dtype], B, Bi, L, st["h"][1 - i].data_ptr(),
-                                                 st["mask"].data_ptr(), st["out"][i].data_ptr(), st["stop"][i].data_ptr(),
-                                                 _ptr(st["prog"][i]), st["h"][i].data_ptr(), C.c_void_p(gs.cuda_stream)), self._h)
-            st["tick"] += 1
-        cur.wait_stream(gs)
-        return st["out"][i], st["stop"][i], st["prog"][i], st["h"][i]
-
-    # debug taps (tests)
-    def enable_taps(self, on=True):
-        _lib.check(self._lib.hcm_debug_enable_taps(self._h, int(on)), self._h)
-
-    def get_tap(self, name):
-        n = C.c_int64()
-        shape = (C.c_int64 * 4)()
-        _lib.check(self._lib.hcm_debug_get_tap(self._h, name.encode(), None, 0, C.byref(n), shape), self._h)
-        buf = np.empty(n.value, dtype=np.float32)
-        _lib.check(self._lib.hcm_debug_get_tap(self._h, name.encode(), buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n), shape), self._h)
-        return buf.reshape([d for d in shape if d > 0])
 
 
 class Seq2SeqNet:

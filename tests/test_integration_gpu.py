@@ -94,6 +94,27 @@ def test_c_abi_error_codes():
     eng.close()
 
 
+def test_sequence_calls_refuse_a_product_beyond_max_batch():
+    """hcm_high_forward_seq / hcm_low_forward_seq: T*N beyond max_batch = 4 is HCM_ERR_ARG before anything is launched, the product taken in 64
+    bits (2^16 * 2^16 wraps to 0 in 32)."""
+    import ctypes as C
+    from robo_vln_amd import _lib
+    from robo_vln_amd.policy import HCMEngine
+    lib = _lib.lib()
+    cfg = HCMConfig(rgb_hw=128, depth_hw=128, instr_len=12, vla_layers=1, bert_layers=1).validate()
+    eng = HCMEngine(cfg, *synth.make_weights(cfg, seed=0), max_batch=4, precision="fp16")
+    buf = torch.full((64,), 7.0, device="cuda")
+    p = C.c_void_p(buf.data_ptr())
+    for T, N in ((3, 2), (1 << 16, 1 << 16)):
+        assert lib.hcm_high_forward_seq(eng._h, p, _lib.HCM_F32, p, p, _lib.HCM_I64, None, T, N, 12, p, p, p, p, None) == -1, (T, N)
+        assert b"max_batch" in lib.hcm_last_error(eng._h), (T, N)
+        assert lib.hcm_low_forward_seq(eng._h, p, _lib.HCM_F32, p, T, N, p, p, p, p, p, p, None) == -1, (T, N)
+        assert b"max_batch" in lib.hcm_last_error(eng._h), (T, N)
+    torch.cuda.synchronize()
+    assert bool((buf == 7.0).all())
+    eng.close()
+
+
 def test_rollout_with_cached_instructions_equals_recomputing():
     """rollout(cache_instruction=True): BERT only for the environments whose episode just ended -- same records, bit for bit."""
     from robo_vln_amd.policy import HCMEngine, Policy

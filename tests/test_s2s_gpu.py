@@ -242,4 +242,15 @@ def test_s2s_rejects_bad_input():
         eng.forward(obs, torch.zeros(1, 4, cfg.hidden), torch.zeros(4))                   # LSTM: R = 2
     with pytest.raises(ValueError):
         eng.forward(dict(obs, instruction=obs["instruction"][:2]), torch.zeros(2, 4, cfg.hidden), torch.zeros(4))     # 2 instructions, 4 frames
+    # hcm_s2s_forward_seq: T*N beyond max_batch = 4 is refused before anything is launched, the product taken in 64 bits (2^16 * 2^16 wraps to 0 in 32)
+    import ctypes as C
+    from robo_vln_amd import _lib
+    lib = _lib.lib()
+    buf = torch.full((64,), 7.0, device="cuda")
+    p = C.c_void_p(buf.data_ptr())
+    for T, N in ((3, 2), (1 << 16, 1 << 16)):
+        assert lib.hcm_s2s_forward_seq(eng._h, p, _lib.HCM_F32, p, p, _lib.HCM_I64, T, N, 1, 12, p, p, p, p, None, p, None) == -1, (T, N)
+        assert b"max_batch" in lib.hcm_last_error(eng._h), (T, N)
+    torch.cuda.synchronize()
+    assert bool((buf == 7.0).all())
     eng.close()
