@@ -34,7 +34,8 @@ enum hcm_status {
     HCM_ERR_NOMEM = -7
 };
 
-enum hcm_dtype { HCM_F32 = 0, HCM_BF16 = 1, HCM_I32 = 2, HCM_I64 = 3, HCM_U8 = 4, HCM_F16 = 5 };
+enum hcm_dtype { HCM_F32 = 0, HCM_BF16 = 1, HCM_I32 = 2, HCM_I64 = 3, HCM_U8 = 4, HCM_F16 = 5,
+                 HCM_FEATURES = 6 /* as `rgb_dtype` only: the `rgb` argument is a host `const hcm_features*` (below) */ };
 enum hcm_model { HCM_HIGH = 0, HCM_LOW = 1, HCM_CMA = 2 /* CMANet flat baseline: hcm_cma_create handles only */,
                  HCM_S2S = 3 /* Seq2SeqNet flat baseline: hcm_s2s_create handles only */ };
 enum hcm_encoder { HCM_ENC_RESNET = 0, HCM_ENC_SIMPLECNN = 1 };
@@ -64,6 +65,10 @@ enum hcm_query_what {
     HCM_GATHER_JOINED = 17,        /* 1 when the handle's LAST hcm_act_gather / hcm_gather_poison call enqueued its ncclAllGather, 0 when it returned in
                                       front of the collective (argument error, no communicator): a caller whose peers are about to enter the step's
                                       all-gather must then join it itself (hcm_gather_poison) -- robo-vln_amd/policy.py act(gather=True) */
+    /* hcm_features: f32 elements PER ROW of the feature tensor a (model, modality) takes; 0 = it takes none (SimpleCNN encoder, ablated modality,
+       model not held).  HI = the high-level model, or the one model of a CMANet / Seq2SeqNet handle; LO = the low-level model */
+    HCM_FEAT_RGB_HI = 18, HCM_FEAT_RGB_LO = 19, HCM_FEAT_DEPTH_HI = 20, HCM_FEAT_DEPTH_LO = 21,
+    HCM_FEAT_SHARED = 22,          /* bit 0: the two models' RGB trunks are one (bit-identical weights, hcm_config.reserved[5] clear), bit 1: the depth trunks */
     HCM_RANGE_FOLD = 16            /* bit 1: a power-of-two scale was folded into convs of the GroupNorm depth trunks, bit 2: into the RGB trunks
                                       (the exact alternative to a bf16 fall-back where the network is scale-invariant; hcm_calibrate below) */
 };
@@ -104,6 +109,33 @@ typedef struct hcm_config {
                                            [5]: 1 = do not share a trunk between the two models when their trunk weights are bit-identical
                                            (the default runs it once per step and feeds both heads: same values, half the work) */
 } hcm_config;
+
+/* Precomputed trunk features: the `rgb_features` / `depth_features` observation keys of the reference's ResNet encoders.
+ * VlnResnetDepthEncoder.forward takes observations["depth_features"] instead of running visual_encoder (models/encoders/resnet_encoders.py:83-86),
+ * TorchVisionResNet50.forward takes observations["rgb_features"] instead of running the hooked cnn (:207-214); both trunks are frozen
+ * (:35-36, :146-149), so a caller that walks the same recorded frames again (val_epoch) can compute them once.
+ * Every entry point that takes `rgb, rgb_dtype, depth` accepts rgb_dtype == HCM_FEATURES: `rgb` is then a HOST pointer to this struct and `depth`
+ * must be NULL.  The members are DEVICE pointers; the struct itself is consumed during the call.
+ *   rgb / rgb_dtype / depth   the frames, as the entry point documents them, for every (model, modality) whose feature pointer is NULL;
+ *                             may be NULL when no trunk of the call needs them
+ *   rgb_feat[m], depth_feat[m]  m = 0: the high-level model, or the one model of a CMANet / Seq2SeqNet handle; m = 1: the low-level model.
+ *                             Non-NULL replaces that model's trunk; given together with a frame the feature wins, as in the reference.
+ * Layouts (the reference's, f32, contiguous; element counts per row from hcm_query(HCM_FEAT_*)):
+ *   rgb_feat of a spatial encoder (high-level model, CMANet)   (rows, 2048, 4, 4): the hooked avgpool output behind adaptive_avg_pool2d((4,4)) (:225-230)
+ *   rgb_feat of a flat encoder (low-level model, Seq2SeqNet)   (rows, 2048, 1, 1)  (:234-236)
+ *   depth_feat                                                 (rows, C, s, s), C = round(2048 / s^2), s = depth_h / 64: the ResNetEncoder output (:87-88)
+ * The values are the reference's: a range fold of the RGB trunk (HCM_RANGE_FOLD) is multiplied in on the way in and divided out by
+ * hcm_encode_features, both exactly.  Non-finite values propagate and end up in the overflow guard (HCM_STEP_NONFINITE) like a broken frame's.
+ * Refused with a message, never a GPU fault: a feature for a SimpleCNN encoder (simple_cnns.py has no such key) or an ablated modality
+ * (HCM_ERR_UNSUPPORTED); a feature in a slot the handle has no model for, HCM_ACT_HOST_FRAMES together with HCM_FEATURES, hcm_calibrate with
+ * HCM_FEATURES (calibration needs the trunks to run), a NULL frame that some trunk of the call still needs (HCM_ERR_ARG).
+ * A captured hcm_act graph is keyed by the four feature pointers like by every other argument. */
+typedef struct hcm_features {
+    const void*  rgb;  int32_t rgb_dtype;
+    const float* depth;
+    const float* rgb_feat[2];
+    const float* depth_feat[2];
+} hcm_features;
 
 /* Replaces model construction, hierarchical_trainer.py:315-328 (Seq2Seq_HighLevel_CMA.__init__
  * models/seq2seq_highlevel_cma.py:33-141, Seq2Seq_LowLevel.__init__ models/seq2seq_lowlevel.py:32-98).
@@ -273,6 +305,19 @@ int hcm_gather_poison(hcm_handle h, int B, float* record, float* gathered, void*
 int hcm_act_gather(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, const int32_t* lengths,
                    int B, int L, const float* hi_h_in, const float* lo_h_in, const float* mask, float* record, float* hi_h_out, float* lo_h_out,
                    int flags, float* gathered, void* stream);
+
+/* The trunks alone: runs, for any handle kind, each ResNet trunk and its pool on `rows` frames (rgb / rgb_dtype / depth as for the forward calls,
+ * rows <= max_batch) and writes the hcm_features layouts above into the four pointers of `out` (device, f32; NULL = that feature is not wanted and its
+ * trunk is not run; a frame may be NULL when no wanted trunk reads it).  Independent trunks run concurrently on the handle's side streams, as in
+ * the step; two models whose trunk is one (HCM_FEAT_SHARED) get it run once.  Fed back through HCM_FEATURES the features reproduce the stored
+ * bits of the frame call exactly, in every precision mode: the fold is a power of two and f32 holds every fp16 / bf16 value.
+ * flags = 0: each model's trunk runs with the launches of its own forward / sequence call -- the bits of hcm_high_forward, hcm_low_forward, the
+ * sequence calls, hcm_val_step and the flat handles' calls.  HCM_ENCODE_ACT: the launches of hcm_act, which runs two models' unequal trunks as
+ * one channel-paired network (equal to the own-model launches to round-off only); the same as 0 where the handle shares or has one model.
+ * No synchronisation, no allocation.  HCM_ERR_UNSUPPORTED: a wanted feature of a SimpleCNN encoder or an ablated modality. */
+enum hcm_encode_flags { HCM_ENCODE_ACT = 1 };
+int hcm_encode_features(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int rows, const hcm_features* out, void* stream);
+int hcm_encode_features_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int rows, const hcm_features* out, int flags, void* stream);
 
 /* fp16 range safety (no reference counterpart: the reference is fp32).  Sub-networks that store fp16 (all four in HCM_F16 mode, the depth
  * trunks in HCM_BF16 mode) have a range that ends at 65504.  hcm_finalize runs one forward on a synthetic batch with range hooks on every GEMM
@@ -615,6 +660,11 @@ int hcm_op_flat_val_loss(const float* out, const float* stop, const float* progr
  * hidden must be 512 (HCM_ERR_ARG otherwise); any T, N >= 1.  Synchronises the stream (it owns temporary buffers). */
 int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,
                       int T, int N, int hidden, int rnn_type, void* stream);
+
+/* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
+ * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
+int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);
+int hcm_op_feat_export(const void* y, int dtype, float* x, int rows, int C, int S, int ld, float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,12 +8,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhcm_dev.so" if os.environ.get("HCM_DEV_LIB", "0") not in ("", "0") else "libhcm.so")
 
 HCM_F32, HCM_BF16, HCM_I32, HCM_I64, HCM_U8, HCM_F16 = 0, 1, 2, 3, 4, 5
+HCM_FEATURES = 6            # as rgb_dtype: `rgb` is a host hcm_features* (HcmFeaturesStruct)
 HCM_HIGH, HCM_LOW, HCM_CMA, HCM_S2S = 0, 1, 2, 3
 HCM_ENC_RESNET, HCM_ENC_SIMPLECNN = 0, 1
 HCM_LSTM, HCM_GRU = 0, 1
 (HCM_NUM_RECURRENT_LAYERS, HCM_HIDDEN_SIZE, HCM_NUM_ACTIONS, HCM_RECORD_WIDTH, HCM_WORKSPACE_BYTES,
  HCM_WEIGHT_BYTES, HCM_MAX_BATCH, HCM_GRAPH_LAUNCHES, HCM_EAGER_LAUNCHES, HCM_FP16_FALLBACK, HCM_CALIB_MAX_BERT, HCM_CALIB_MAX_DEPTH,
  HCM_CALIB_NONFINITE, HCM_CALIB_MAX_RGB, HCM_CALIB_MAX_VLA, HCM_STEP_NONFINITE, HCM_RANGE_FOLD, HCM_GATHER_JOINED) = range(18)
+HCM_FEAT_RGB_HI, HCM_FEAT_RGB_LO, HCM_FEAT_DEPTH_HI, HCM_FEAT_DEPTH_LO, HCM_FEAT_SHARED = 18, 19, 20, 21, 22
+HCM_ENCODE_ACT = 1
 # `precision` of HCMEngine / CMAEngine -> hcm_config.precision (include/hcm.h): "fp16" is the measured 16-bit mode
 PRECISIONS = {"fp32": HCM_F32, "fp16": HCM_F16, "bf16": HCM_BF16}
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -51,7 +54,14 @@ class HcmS2sConfigStruct(C.Structure):
         "use_prev_action", "is_bert", "progress_monitor", "ablate_instruction", "ablate_depth", "ablate_rgb")] + [("reserved", C.c_int32 * 6)]
 
 
+class HcmFeaturesStruct(C.Structure):
+    """hcm_features (include/hcm.h): frames for the trunks that still run, and the precomputed trunk outputs per (model, modality)"""
+    _fields_ = [("rgb", C.c_void_p), ("rgb_dtype", C.c_int32), ("depth", C.c_void_p), ("rgb_feat", C.c_void_p * 2), ("depth_feat", C.c_void_p * 2)]
+
+
 EXPORTS = {
+    "hcm_encode_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(HcmFeaturesStruct), C.c_void_p]),
+    "hcm_encode_features_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(HcmFeaturesStruct), C.c_int, C.c_void_p]),
     "hcm_s2s_create": (C.c_int, [C.POINTER(HcmS2sConfigStruct), C.POINTER(C.c_void_p)]),
     "hcm_s2s_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -129,6 +139,8 @@ EXPORTS = {
     "hcm_op_val_loss": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
     "hcm_op_flat_val_loss": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_void_p]),
     "hcm_op_state_scan": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_feat_ingest": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
 }
 

@@ -25,6 +25,7 @@ static FwdCall frames(const void* rgb, int rgb_dt, const float* depth, const voi
 static void drop_instruction_cache(hcm_ctx* h);
 static bool rgb_dt_ok(int d);
 static bool ids_dt_ok(int d);
+static int check_obs(hcm_ctx* h, const FwdCall& c, const float* depth_arg, int rgb_dtype_arg);
 
 static void destroy_entry(hcm_ctx::GraphEntry& g) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -111,7 +112,8 @@ static std::vector<uint64_t> call_key(const FwdCall& c, bool segmented) {
             (uint64_t)c.val, (uint64_t)c.rgb_dt, (uint64_t)c.ids_dt, (uint64_t)c.rows, (uint64_t)c.T, (uint64_t)c.Bi, (uint64_t)c.L,
             (uint64_t)c.ld_logits, (uint64_t)c.ld_vel, (uint64_t)c.ld_stop, p(c.stream), p(c.rgb), p(c.depth), p(c.ids), p(c.lens),
             p(c.hi_h_in), p(c.lo_h_in), p(c.hi_h_out), p(c.lo_h_out), p(c.mask), p(c.subtask), p(c.logits), p(c.vel), p(c.stop), p(c.progress),
-            p(c.oracle), p(c.corrected), p(c.oracle_stop), p(c.progress_label), p(c.result)};
+            p(c.oracle), p(c.corrected), p(c.oracle_stop), p(c.progress_label), p(c.result),
+            p(c.rgb_feat[0]), p(c.rgb_feat[1]), p(c.depth_feat[0]), p(c.depth_feat[1])};
 }
 
 // hipGraph cache shared by the fused entry points, keyed by call_key().  A key is run eagerly the first time it is seen (that also
@@ -427,7 +429,22 @@ static void dry_run(hcm_ctx* h, int B) {
     h->arena.peak = 0;
     FwdCall c;                                             // every pointer null: allocations only
     c.L = h->cfg.instr_len;
-    auto run = [&](int rows, int T, FwdCall::Val val = FwdCall::kNoVal) { c.rows = c.Bi = rows; c.T = T; c.val = val; run_forward(h, c); };
+    // Every shape is sized in its frame form and in its hcm_features form (a stand-in address, never read in a dry pass, in every slot a ResNet
+    // trunk can take a feature for: the ingest buffers instead of the trunks').  hcm_encode_features: below, once at B rows.
+    const float* const stand_in = (const float*)0x1000;
+    auto run = [&](int rows, int T, FwdCall::Val val = FwdCall::kNoVal) {
+        c.rows = c.Bi = rows; c.T = T; c.val = val;
+        for (const float* f : {(const float*)nullptr, stand_in}) {
+            c.rgb_feat[0] = c.rgb_feat[1] = c.depth_feat[0] = c.depth_feat[1] = f;
+            run_forward(h, c);
+        }
+        c.rgb_feat[0] = c.rgb_feat[1] = c.depth_feat[0] = c.depth_feat[1] = nullptr;
+    };
+    {
+        FwdCall e;
+        e.encode = true; e.rows = B;
+        for (bool act : {false, true}) { e.enc_act = act; run_forward(h, e); }
+    }
     if (h->kind == 1) {
         run(B, 1);
         // hcm_cma_forward_seq: the scans' buffers on top of the step's.  What they hold grows with the rows (the projections, both sequence
@@ -774,6 +791,9 @@ int hcm_calibrate(hcm_handle h, const void* rgb, int rgb_dtype, const float* dep
     int rc = check_fwd(h, B);
     if (rc) return rc;
     const bool needs_ids = h->kind == 1 || h->kind == 2 || h->cfg.build_high;
+    REQUIRE(rgb_dtype != HCM_FEATURES, HCM_ERR_ARG,
+            "hcm_calibrate with HCM_FEATURES: the calibration measures the ranges inside the trunks and needs them to run -- pass the frames (the reference "
+            "has no counterpart: resnet_encoders.py:83-86, :207-214 skip the trunk when the feature key is there)");
     REQUIRE(rgb && depth && (ids || !needs_ids), HCM_ERR_ARG, "null pointer");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     if (needs_ids && (rc = check_len(h, L))) return rc;
@@ -828,9 +848,80 @@ static bool ids_dt_ok(int d) { return d == HCM_F32 || d == HCM_I32 || d == HCM_I
 // the observation part of a descriptor
 static FwdCall frames(const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int rows, int L, void* stream) {
     FwdCall c;
-    c.rgb = rgb; c.rgb_dt = rgb_dt; c.depth = depth; c.ids = ids; c.ids_dt = ids_dt;
+    if (rgb_dt == HCM_FEATURES && rgb) {                   // `rgb` is a host hcm_features: frames and features travel in it (check_obs judges them)
+        const hcm_features* f = (const hcm_features*)rgb;
+        c.rgb = f->rgb; c.rgb_dt = f->rgb_dtype; c.depth = f->depth;
+        for (int m = 0; m < 2; ++m) { c.rgb_feat[m] = f->rgb_feat[m]; c.depth_feat[m] = f->depth_feat[m]; }
+    } else { c.rgb = rgb; c.rgb_dt = rgb_dt; c.depth = depth; }
+    c.ids = ids; c.ids_dt = ids_dt;
     c.rows = c.Bi = rows; c.L = L; c.stream = (hipStream_t)stream;
     return c;
+}
+// Which (model, modality) pairs of this handle have a ResNet trunk that runs (no SimpleCNN, not ablated): [slot][0 rgb, 1 depth]; slot 0 = the
+// high-level model or a flat handle's model, slot 1 = the low-level model.  `why` gets the reason a pair takes no feature.
+static bool feat_slot(const hcm_ctx* h, int m, int mod, const char** why) {
+    const char* none = "the handle holds no model for that slot";
+    const char* simple = mod == 0 ? "that model's RGB encoder is a SimpleRGBCNN, which reads observations[\"rgb\"] only (models/encoders/simple_cnns.py:144-147; "
+                                    "rgb_features is a key of TorchVisionResNet50, resnet_encoders.py:207-214)"
+                                  : "that model's depth encoder is a SimpleDepthCNN, which reads observations[\"depth\"] only (models/encoders/simple_cnns.py:122-125; "
+                                    "depth_features is a key of VlnResnetDepthEncoder, resnet_encoders.py:83-86)";
+    const char* ablated = mod == 0 ? "the RGB modality is ablated: the encoder output is multiplied by 0 (seq2seq_highlevel_cma.py:187-188, seq2seq_lowlevel.py:134-135, "
+                                     "cma.py:240-241, seq2seq.py:160-161) and nothing would read the feature"
+                                   : "the depth modality is ablated: the encoder output is multiplied by 0 (seq2seq_highlevel_cma.py:185-186, seq2seq_lowlevel.py:132-133, "
+                                     "cma.py:238-239, seq2seq.py:158-159) and nothing would read the feature";
+    const char* dummy;
+    if (!why) why = &dummy;
+    if (h->kind == 1) {
+        if (m != 0) { *why = none; return false; }
+        if (mod == 0 ? h->cma_cfg.ablate_rgb : h->cma_cfg.ablate_depth) { *why = ablated; return false; }
+        return true;
+    }
+    const bool lo = h->kind == 2 || m == 1;                // Seq2SeqNet runs the low-level model's encoder paths
+    if (h->kind == 2 ? m != 0 : (m == 0 ? !h->cfg.build_high : !h->cfg.build_low)) { *why = none; return false; }
+    if (lo && (mod == 0 ? h->lo.rgb_simple : h->lo.depth_simple)) { *why = simple; return false; }
+    const bool abl = h->kind == 2 ? (mod == 0 ? h->s2s_cfg.ablate_rgb : h->s2s_cfg.ablate_depth) : (mod == 0 ? h->cfg.ablate_rgb : h->cfg.ablate_depth);
+    if (abl) { *why = ablated; return false; }
+    return true;
+}
+// f32 elements per row of the feature (slot m, modality mod) takes; 0 = none
+static int64_t feat_elems(const hcm_ctx* h, int m, int mod) {
+    if (!feat_slot(h, m, mod, nullptr)) return 0;
+    if (mod == 0) return (h->kind == 2 || (h->kind == 0 && m == 1)) ? 2048 : 2048 * 16;
+    const int fs = hcm::depth_final_spatial(h->cfg);
+    return (int64_t)hcm::depth_compress_channels(h->cfg) * fs * fs;
+}
+// The observation part of a call, after frames(): features only where a ResNet trunk would run, and a frame for every trunk that still runs.
+// depth_arg: the entry point's own `depth` argument -- NULL with HCM_FEATURES.  The models of the call: do_hi / do_lo on an HCM handle.
+static int check_obs(hcm_ctx* h, const FwdCall& c, const float* depth_arg, int rgb_dtype_arg) {
+    const bool feats = rgb_dtype_arg == HCM_FEATURES;
+    if (feats) {
+        REQUIRE(c.rgb || c.depth || c.rgb_feat[0] || c.rgb_feat[1] || c.depth_feat[0] || c.depth_feat[1], HCM_ERR_ARG,
+                "HCM_FEATURES: `rgb` must point to an hcm_features holding at least one pointer");
+        REQUIRE(!depth_arg, HCM_ERR_ARG, "HCM_FEATURES: `depth` must be NULL, the depth frames travel in hcm_features.depth");
+        REQUIRE(!c.host_frames, HCM_ERR_ARG, "HCM_ACT_HOST_FRAMES together with HCM_FEATURES: the members of hcm_features are device pointers");
+    }
+    bool need[2] = {false, false};                         // a trunk of the call still reads the RGB / depth frames
+    for (int m = 0; m < 2; ++m) {
+        const bool runs = h->kind != 0 ? m == 0 : (m == 0 ? c.do_hi : c.do_lo);
+        for (int mod = 0; mod < 2; ++mod) {
+            const float* f = mod == 0 ? c.rgb_feat[m] : c.depth_feat[m];
+            const char* why = "";
+            const bool slot = feat_slot(h, m, mod, &why);
+            if (f && !slot)
+                return fail(h, h->kind != 0 && m == 1 ? HCM_ERR_ARG : HCM_ERR_UNSUPPORTED,
+                            std::string(mod == 0 ? "rgb_feat[" : "depth_feat[") + std::to_string(m) + "] given, but " + why);
+            if (!runs || f) continue;
+            // no feature: the frame is read unless the modality is ablated (the encoder is then not run at all)
+            const bool abl = h->kind == 1 ? (mod == 0 ? h->cma_cfg.ablate_rgb : h->cma_cfg.ablate_depth)
+                           : h->kind == 2 ? (mod == 0 ? h->s2s_cfg.ablate_rgb : h->s2s_cfg.ablate_depth) : (mod == 0 ? h->cfg.ablate_rgb : h->cfg.ablate_depth);
+            const bool held = h->kind != 0 || (m == 0 ? h->cfg.build_high : h->cfg.build_low);
+            if (held && !(feats && abl)) need[mod] = true;
+        }
+    }
+    REQUIRE(!need[0] || c.rgb, HCM_ERR_ARG, feats ? "hcm_features.rgb is NULL, but a model of this call has no rgb_feat and still runs its RGB encoder" : "null pointer");
+    REQUIRE(!need[1] || c.depth, HCM_ERR_ARG, feats ? "hcm_features.depth is NULL, but a model of this call has no depth_feat and still runs its depth encoder" : "null pointer");
+    REQUIRE(!c.rgb || rgb_dt_ok(c.rgb_dt), HCM_ERR_ARG, "unsupported rgb dtype");
+    return HCM_OK;
 }
 // state, mask and outputs of a flat handle's one model
 static void flat_io(hcm_ctx* h, FwdCall& c, const float* h_in, const float* mask, float* out, float* stop, float* progress, float* h_out) {
@@ -850,10 +941,11 @@ static int high_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float*
     if ((rc = check_len(h, L))) return rc;
     drop_instruction_cache(h);
     REQUIRE(h->cfg.build_high, HCM_ERR_STATE, "handle holds no high-level model");
-    REQUIRE(rgb && depth && ids && h_in && mask && logits && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE(ids && h_in && mask && logits && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
     c.do_hi = true; c.T = T; c.lens = lengths;
+    if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     c.hi_h_in = h_in; c.mask = mask; c.logits = logits; c.ld_logits = h->cfg.num_actions; c.hi_h_out = h_out;
     return run_eager(h, c);
 }
@@ -876,10 +968,10 @@ static int low_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* 
     if (rc) return rc;
     drop_instruction_cache(h);
     REQUIRE(h->cfg.build_low, HCM_ERR_STATE, "handle holds no low-level model");
-    REQUIRE(rgb && depth && h_in && mask && subtask && vel && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype), HCM_ERR_ARG, "unsupported rgb dtype");
+    REQUIRE(h_in && mask && subtask && vel && stop && h_out, HCM_ERR_ARG, "null pointer");
     FwdCall c = frames(rgb, rgb_dtype, depth, nullptr, DT_I64, rows, 0, stream);
     c.do_lo = true; c.T = T;
+    if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     c.lo_h_in = h_in; c.mask = mask; c.subtask = subtask; c.lo_h_out = h_out;
     c.vel = vel; c.ld_vel = h->cfg.lo_actions; c.stop = stop; c.ld_stop = 1;
     return run_eager(h, c);
@@ -899,10 +991,11 @@ int hcm_low_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const floa
 // hcm_cma_forward (T = 1: through the graph cache) and hcm_cma_forward_seq at T > 1; the caller has checked the handle's kind, rows and L
 static int cma_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int rows, int T, int L,
                        const float* h_in, const float* mask, float* out, float* stop, float* h_out, void* stream) {
-    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE(ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
     c.T = T;
+    if (const int rc = check_obs(h, c, depth, rgb_dtype)) return rc;
     flat_io(h, c, h_in, mask, out, stop, nullptr, h_out);
     return T == 1 ? run_graphed(h, c) : run_eager(h, c);
 }
@@ -940,10 +1033,11 @@ static int s2s_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* 
     int rc = check_fwd(h, rows);
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
-    REQUIRE(rgb && depth && ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE(ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
     c.T = T; c.Bi = B_instr;
+    if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     flat_io(h, c, h_in, mask, out, stop, progress, h_out);
     return graphed ? run_graphed(h, c) : run_eager(h, c);
 }
@@ -968,15 +1062,16 @@ int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* dept
     int rc = check_seq(h, T, N);
     if (rc) return rc;
     REQUIRE(result, HCM_ERR_ARG, "null result");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE((rgb_dt_ok(rgb_dtype) || rgb_dtype == HCM_FEATURES) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     if ((rc = check_fwd(h, T * N))) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_val_step needs both models in the handle");
-    REQUIRE(rgb && depth && ids && oracle_subtask && corrected_actions && oracle_stop && hi_h_in && lo_h_in && masks && hi_h_out && lo_h_out,
+    REQUIRE(ids && oracle_subtask && corrected_actions && oracle_stop && hi_h_in && lo_h_in && masks && hi_h_out && lo_h_out,
             HCM_ERR_ARG, "null pointer");
     drop_instruction_cache(h);
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, T * N, L, stream);
     c.do_hi = c.do_lo = true; c.T = T; c.lens = lengths;
+    if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     c.hi_h_in = hi_h_in; c.lo_h_in = lo_h_in; c.mask = masks; c.hi_h_out = hi_h_out; c.lo_h_out = lo_h_out;
     c.logits = logits; c.ld_logits = h->cfg.num_actions; c.vel = vel; c.ld_vel = h->cfg.lo_actions; c.stop = stop; c.ld_stop = 1;
     c.val = FwdCall::kVal; c.oracle = oracle_subtask; c.corrected = corrected_actions; c.oracle_stop = oracle_stop; c.result = result;
@@ -992,7 +1087,7 @@ int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float*
     int rc = check_seq(h, T, N);
     if (rc) return rc;
     REQUIRE(result, HCM_ERR_ARG, "null result");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE((rgb_dt_ok(rgb_dtype) || rgb_dtype == HCM_FEATURES) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     const bool monitor = h->kind == 2 && h->s2s_cfg.progress_monitor;
     if (h->kind == 1)
         REQUIRE(B_instr == T * N, HCM_ERR_ARG, "B_instr must be T*N on a CMANet handle: one instruction row per frame (hcm_cma_forward_seq)");
@@ -1005,12 +1100,43 @@ int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float*
             "null progress: the handle was created with PROGRESS_MONITOR.use, the auxiliary loss needs observations[\"progress\"]");
     if ((rc = check_fwd(h, T * N))) return rc;
     if ((rc = check_len(h, L))) return rc;
-    REQUIRE(rgb && depth && ids && corrected_actions && oracle_stop && h_in && masks && h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(ids && corrected_actions && oracle_stop && h_in && masks && h_out, HCM_ERR_ARG, "null pointer");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, T * N, L, stream);
     c.T = T; c.Bi = B_instr;
+    if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     flat_io(h, c, h_in, masks, out, stop, progress_hat, h_out);
     c.val = FwdCall::kFlatVal; c.corrected = corrected_actions; c.oracle_stop = oracle_stop; c.progress_label = progress; c.result = result;
     return run_eager(h, c);
+}
+
+int hcm_encode_features_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int rows, const hcm_features* out, int flags, void* stream) {
+    int rc = check_fwd(h, rows);
+    if (rc) return rc;
+    REQUIRE(out, HCM_ERR_ARG, "null `out`");
+    REQUIRE(rgb_dtype != HCM_FEATURES, HCM_ERR_ARG, "hcm_encode_features reads frames: rgb_dtype must be HCM_F32 or HCM_U8");
+    REQUIRE((flags & ~HCM_ENCODE_ACT) == 0, HCM_ERR_ARG, "unknown flag");
+    drop_instruction_cache(h);
+    FwdCall c = frames(rgb, rgb_dtype, depth, nullptr, DT_I64, rows, 0, stream);
+    c.encode = true; c.enc_act = (flags & HCM_ENCODE_ACT) != 0;
+    bool any = false, need[2] = {false, false};
+    for (int m = 0; m < 2; ++m)
+        for (int mod = 0; mod < 2; ++mod) {
+            float* o = const_cast<float*>(mod == 0 ? out->rgb_feat[m] : out->depth_feat[m]);
+            if (!o) continue;
+            const char* why = "";
+            if (!feat_slot(h, m, mod, &why))
+                return fail(h, h->kind != 0 && m == 1 ? HCM_ERR_ARG : HCM_ERR_UNSUPPORTED,
+                            std::string(mod == 0 ? "rgb_feat[" : "depth_feat[") + std::to_string(m) + "] wanted, but " + why);
+            (mod == 0 ? c.enc_rgb[m] : c.enc_depth[m]) = o;
+            any = need[mod] = true;
+        }
+    REQUIRE(any, HCM_ERR_ARG, "no feature wanted: every pointer of `out` is NULL");
+    REQUIRE(!need[0] || (rgb && rgb_dt_ok(rgb_dtype)), HCM_ERR_ARG, "an RGB feature is wanted: `rgb` must be frames of dtype HCM_F32 or HCM_U8");
+    REQUIRE(!need[1] || depth, HCM_ERR_ARG, "a depth feature is wanted: `depth` is NULL");
+    return run_eager(h, c);
+}
+int hcm_encode_features(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int rows, const hcm_features* out, void* stream) {
+    return hcm_encode_features_ex(h, rgb, rgb_dtype, depth, rows, out, 0, stream);
 }
 
 int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
@@ -1020,8 +1146,8 @@ int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth,
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_act needs both models in the handle");
-    REQUIRE(rgb && depth && ids && hi_h_in && lo_h_in && mask && record && hi_h_out && lo_h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE(ids && hi_h_in && lo_h_in && mask && record && hi_h_out && lo_h_out, HCM_ERR_ARG, "null pointer");
+    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     REQUIRE(h->cfg.num_actions + h->cfg.lo_actions + 1 == 7, HCM_ERR_UNSUPPORTED, "record layout assumes 4 + 2 + 1 outputs");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, B, L, stream);
     c.do_hi = c.do_lo = true; c.lens = lengths;
@@ -1029,6 +1155,7 @@ int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth,
     REQUIRE(!c.reuse_instruction || (h->last_hi_batch == B && h->last_hi_L == L), HCM_ERR_STATE,
             "HCM_ACT_REUSE_INSTRUCTION: the previous call on this handle was not an hcm_act step with this batch size and instruction length");
     c.host_frames = (flags & HCM_ACT_HOST_FRAMES) != 0;
+    if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     if (c.host_frames && (!h->stage_rgb || !h->stage_depth)) {         // device staging for the largest call: f32 RGB frames + f32 depth frames
         const size_t n_rgb = (size_t)h->cfg.max_batch * h->cfg.rgb_h * h->cfg.rgb_w * 3 * 4, n_dep = (size_t)h->cfg.max_batch * h->cfg.depth_h * h->cfg.depth_w * 4;
         if (!h->stage_rgb && hipMalloc(&h->stage_rgb, n_rgb) != hipSuccess) { h->stage_rgb = nullptr; return fail(h, HCM_ERR_NOMEM, "hipMalloc of the RGB frame staging buffer failed"); }
@@ -1088,6 +1215,14 @@ int hcm_query(hcm_handle h, int what, int64_t* out) {
         case HCM_FP16_FALLBACK: *out = h->fp16_fallback; break;
         case HCM_RANGE_FOLD: *out = h->range_fold; break;
         case HCM_GATHER_JOINED: *out = h->gather_joined; break;
+        case HCM_FEAT_RGB_HI: *out = feat_elems(h, 0, 0); break;
+        case HCM_FEAT_RGB_LO: *out = feat_elems(h, 1, 0); break;
+        case HCM_FEAT_DEPTH_HI: *out = feat_elems(h, 0, 1); break;
+        case HCM_FEAT_DEPTH_LO: *out = feat_elems(h, 1, 1); break;
+        case HCM_FEAT_SHARED:
+            *out = h->kind == 0 && h->cfg.build_high && h->cfg.build_low
+                       ? (int64_t)(h->hi.rgb_shared && !h->lo.rgb_simple) | (int64_t)(h->hi.depth_shared && !h->lo.depth_simple) << 1 : 0;
+            break;
         case HCM_CALIB_MAX_BERT: *out = (int64_t)h->calib_max[0]; break;
         case HCM_CALIB_MAX_DEPTH: *out = (int64_t)h->calib_max[1]; break;
         case HCM_CALIB_NONFINITE: *out = (int64_t)h->calib_bad[0] + (int64_t)h->calib_bad[1] + (int64_t)h->calib_bad[2] + (int64_t)h->calib_bad[3]; break;
@@ -1591,6 +1726,13 @@ int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, co
     const hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(ws);
     return op_rc(e != hipSuccess ? e : e2);
+}
+
+int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
+    return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
+}
+int hcm_op_feat_export(const void* y, int dtype, float* x, int rows, int C, int S, int ld, float scale, void* stream) {
+    return op_rc(hcm::launch_feat_export(y, op_dt(dtype), x, rows, C, S, ld, scale, (hipStream_t)stream));
 }
 
 int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, int C, void* stream) {

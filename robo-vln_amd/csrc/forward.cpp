@@ -1071,16 +1071,41 @@ struct Fwd {
         return b;
     }
 
+    // ---------------------------------------------------------------- precomputed trunk features (hcm_features, include/hcm.h)
+    // The reference's encoders take their trunk output from observations["rgb_features"] / ["depth_features"] when it is there
+    // (resnet_encoders.py:83-86, :207-214).  A feature replaces the trunk AND its pooling launch: it is written, in the current storage type, into the
+    // very buffer that launch fills -- columns [0, C) of [B][S][ld] -- and everything behind it runs unchanged.  Cp > C: the depth compression conv
+    // runs padded to a power of two (weights.cpp) and its padding channels are exact zeros.
+    // The RGB trunk's activations carry hcm_ctx::rgb_fold (fp16 storage only, weights.cpp bn_fold) and the consumers' weights its inverse: features
+    // at the ABI are the reference's unscaled values, so the fold is multiplied in here and divided out in feat_out -- a power of two, exact.
+    // The depth trunk ends in its compression conv's GroupNorm + ReLU (trunk(), conv_gn(t.compress ...)), which removes every depth_fold: no scale.
+    float rgb_scale() const { return ctx->dt_rgb == DT_F16 ? ctx->rgb_fold : 1.f; }
+    void feat_in(const float* feat, void* y, int B, int C, int Cp, int S, int ld, float scale) {
+        if (dry) return;
+        ck(launch_feat_ingest(feat, y, dt, B, C, S, ld, scale, s), "feature ingest");
+        if (Cp > C) ck(hipMemset2DAsync((char*)y + (size_t)C * esz, (size_t)ld * esz, 0, (size_t)(Cp - C) * esz, (size_t)B * S, s), "feature padding");
+    }
+    void feat_out(const void* y, float* feat, int B, int C, int S, int ld, float scale) {
+        if (!dry && feat) ck(launch_feat_export(y, dt, feat, B, C, S, ld, scale, s), "feature export");
+    }
+    static int depth_true_c(const TrunkW& t) { return t.compress_true ? t.compress_true : t.compress.Cout; }
+
     // depth_encoder (seq2seq_highlevel_cma.py:178-179): GN-ResNet50 + pos-emb channels -> dep_tok
-    void hi_depth(const float* depth, int B, HiBufs& hb) {
+    void hi_depth(const float* depth, int B, HiBufs& hb, const float* feat = nullptr) {
         const HighW& w = ctx->hi;
-        const int dS = w.depth_S, dC = w.depth_C;
+        const int dS = w.depth_S, dC = w.depth_C, Cp = w.depth.compress.Cout;
         use(ctx->dt_depth);
-        Act o = depth_trunk(w.depth, depth, B, "hi.depth");
-        void* tok = ctx->dt_depth == ctx->dt_vla ? hb.dep_tok : alloc_t((size_t)B * dS * dC);
+        void* tok = nullptr;
+        if (feat) {
+            tok = ctx->dt_depth == ctx->dt_vla ? hb.dep_tok : alloc_t((size_t)B * dS * dC);
+            feat_in(feat, tok, B, depth_true_c(w.depth), Cp, dS, dC, 1.f);
+        } else {
+            Act o = depth_trunk(w.depth, depth, B, "hi.depth");
+            tok = ctx->dt_depth == ctx->dt_vla ? hb.dep_tok : alloc_t((size_t)B * dS * dC);
+            if (!dry) ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, o.H, o.W, dC, s), "depth tokens");
+        }
         if (!dry) {
-            ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, o.H, o.W, dC, s), "depth tokens");
-            ck(launch_fill_cols(w.depth_pe, (char*)tok + (size_t)o.C * esz, dt, B, dS, 64, dC, s), "depth pe");
+            ck(launch_fill_cols(w.depth_pe, (char*)tok + (size_t)Cp * esz, dt, B, dS, 64, dC, s), "depth pe");
             if (tok != hb.dep_tok) ck(launch_convert(tok, ctx->dt_depth, hb.dep_tok, ctx->dt_vla, (size_t)B * dS * dC, s), "depth tokens convert");
         }
         use(ctx->dt_vla);
@@ -1166,14 +1191,20 @@ struct Fwd {
         hi_vis_pre(1, B, hb);
     }
     // rgb_encoder (:180-181): ResNet50 trunk, adaptive_avg_pool2d(4,4), pos-emb channels -> rgb_tok
-    void hi_rgb(const void* rgb, int rgb_dt, int B, HiBufs& hb) {
+    void hi_rgb(const void* rgb, int rgb_dt, int B, HiBufs& hb, const float* feat = nullptr) {
         const HighW& w = ctx->hi;
         const int rC = 2048 + 64;
         use(ctx->dt_rgb);
-        Act o = rgb_trunk(w.rgb, rgb, rgb_dt, B, "hi.rgb");
-        void* tok = ctx->dt_rgb == ctx->dt_vla ? hb.rgb_tok : alloc_t((size_t)B * 16 * rC);
+        void* tok = nullptr;
+        if (feat) {
+            tok = ctx->dt_rgb == ctx->dt_vla ? hb.rgb_tok : alloc_t((size_t)B * 16 * rC);
+            feat_in(feat, tok, B, 2048, 2048, 16, rC, rgb_scale());
+        } else {
+            Act o = rgb_trunk(w.rgb, rgb, rgb_dt, B, "hi.rgb");
+            tok = ctx->dt_rgb == ctx->dt_vla ? hb.rgb_tok : alloc_t((size_t)B * 16 * rC);
+            if (!dry) ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, 4, 4, rC, s), "rgb tokens");
+        }
         if (!dry) {
-            ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, 4, 4, rC, s), "rgb tokens");
             ck(launch_fill_cols(w.rgb_pe, (char*)tok + (size_t)2048 * esz, dt, B, 16, 64, rC, s), "rgb pe");
             if (tok != hb.rgb_tok) ck(launch_convert(tok, ctx->dt_rgb, hb.rgb_tok, ctx->dt_vla, (size_t)B * 16 * rC, s), "rgb tokens convert");
         }
@@ -1347,19 +1378,25 @@ struct Fwd {
     }
 
     // ---------------------------------------------------------------- stages of Seq2Seq_LowLevel.forward
-    void lo_depth(const float* depth, int B, LoBufs& lb) {
+    void lo_depth(const float* depth, int B, LoBufs& lb, const float* feat = nullptr) {
         const LowW& w = ctx->lo;
         use(ctx->dt_depth);
         if (w.depth_simple) {
             calib_slot = 1;
             simple_cnn(w.depth_s, depth, DT_F32, 1.0f, B, lb.xh, lb.ldx);
             calib_slot = -1;
+        } else if (feat) {
+            // depth_features (resnet_encoders.py:83-86) -> the NHWC-flattened row visual_fc reads from the trunk's last activation
+            const int S = depth_final_spatial(ctx->cfg) * depth_final_spatial(ctx->cfg), Cp = w.depth.compress.Cout;
+            void* flat = alloc_t((size_t)B * S * Cp);
+            feat_in(feat, flat, B, depth_true_c(w.depth), Cp, S, Cp, 1.f);
+            linear(w.depth_fc, flat, B, S * Cp, lb.xh, lb.ldx, ACT_RELU, true);          // visual_fc
         } else {
             Act o = depth_trunk(w.depth, depth, B, "lo.depth");
             linear(w.depth_fc, o.p, B, o.H * o.W * o.C, lb.xh, lb.ldx, ACT_RELU, true);     // visual_fc
         }
     }
-    void lo_rgb(const void* rgb, int rgb_dt, int B, LoBufs& lb) {
+    void lo_rgb(const void* rgb, int rgb_dt, int B, LoBufs& lb, const float* feat = nullptr) {
         const LowW& w = ctx->lo;
         const hcm_config& c = ctx->cfg;
         use(ctx->dt_rgb);
@@ -1367,6 +1404,11 @@ struct Fwd {
             calib_slot = 2;
             simple_cnn(w.rgb_s, rgb, rgb_dt, 1.0f / 255.0f, B, lb.xh + c.depth_out, lb.ldx);
             calib_slot = -1;
+        } else if (feat) {
+            // rgb_features (resnet_encoders.py:207-214), (B,2048,1,1) -> the pooled row fc reads
+            void* pooled = alloc_t((size_t)B * 2048);
+            feat_in(feat, pooled, B, 2048, 2048, 1, 2048, rgb_scale());
+            linear(w.rgb_fc, pooled, B, 2048, lb.xh + c.depth_out, lb.ldx, ACT_RELU, true);
         } else {
             Act o = rgb_trunk(w.rgb, rgb, rgb_dt, B, "lo.rgb");
             void* pooled = alloc_t((size_t)B * o.C);
@@ -1506,11 +1548,18 @@ struct Fwd {
             tap("cma.depth_spatial", dep_tok, true, {B, dS, dC});
         } else {
             use(ctx->dt_depth);
-            Act o = depth_trunk(w.depth, depth, B, "cma.depth");
-            void* tok = ctx->dt_depth == ctx->dt_vla ? dep_tok : alloc_t((size_t)B * dS * dC);
+            const int Cp = w.depth.compress.Cout;
+            void* tok = nullptr;
+            if (call.depth_feat[0]) {                             // depth_features (resnet_encoders.py:83-86)
+                tok = ctx->dt_depth == ctx->dt_vla ? dep_tok : alloc_t((size_t)B * dS * dC);
+                feat_in(call.depth_feat[0], tok, B, depth_true_c(w.depth), Cp, dS, dC, 1.f);
+            } else {
+                Act o = depth_trunk(w.depth, depth, B, "cma.depth");
+                tok = ctx->dt_depth == ctx->dt_vla ? dep_tok : alloc_t((size_t)B * dS * dC);
+                if (!dry) ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, o.H, o.W, dC, s), "depth tokens");
+            }
             if (!dry) {
-                ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, o.H, o.W, dC, s), "depth tokens");
-                ck(launch_fill_cols(w.depth_pe, (char*)tok + (size_t)o.C * esz, dt, B, dS, 64, dC, s), "depth pe");
+                ck(launch_fill_cols(w.depth_pe, (char*)tok + (size_t)Cp * esz, dt, B, dS, 64, dC, s), "depth pe");
                 if (tok != dep_tok) ck(launch_convert(tok, ctx->dt_depth, dep_tok, ctx->dt_vla, (size_t)B * dS * dC, s), "depth tokens convert");
             }
             use(ctx->dt_vla);
@@ -1524,10 +1573,16 @@ struct Fwd {
             tap("cma.rgb_spatial", rgb_tok, true, {B, 16, rC});
         } else {
             use(ctx->dt_rgb);
-            Act o = rgb_trunk(w.rgb, rgb, rgb_dt, B, "cma.rgb");
-            void* tok = ctx->dt_rgb == ctx->dt_vla ? rgb_tok : alloc_t((size_t)B * 16 * rC);
+            void* tok = nullptr;
+            if (call.rgb_feat[0]) {                               // rgb_features (resnet_encoders.py:207-214)
+                tok = ctx->dt_rgb == ctx->dt_vla ? rgb_tok : alloc_t((size_t)B * 16 * rC);
+                feat_in(call.rgb_feat[0], tok, B, 2048, 2048, 16, rC, rgb_scale());
+            } else {
+                Act o = rgb_trunk(w.rgb, rgb, rgb_dt, B, "cma.rgb");
+                tok = ctx->dt_rgb == ctx->dt_vla ? rgb_tok : alloc_t((size_t)B * 16 * rC);
+                if (!dry) ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, 4, 4, rC, s), "rgb tokens");
+            }
             if (!dry) {
-                ck(launch_adaptive_avgpool(o.p, tok, dt, B, o.H, o.W, o.C, 4, 4, rC, s), "rgb tokens");
                 ck(launch_fill_cols(w.rgb_pe, (char*)tok + (size_t)2048 * esz, dt, B, 16, 64, rC, s), "rgb pe");
                 if (tok != rgb_tok) ck(launch_convert(tok, ctx->dt_rgb, rgb_tok, ctx->dt_vla, (size_t)B * 16 * rC, s), "rgb tokens convert");
             }
@@ -1670,13 +1725,13 @@ struct Fwd {
         on(a1);
         if (m.ablate_depth) {
             if (!dry) ck(hipMemset2DAsync(xh + Hi, (size_t)ldx * 4, 0, (size_t)c.depth_out * 4, B, s), "ablate: zero depth features");      // seq2seq.py:158-159
-        } else lo_depth(depth, B, lb);
+        } else lo_depth(depth, B, lb, call.depth_feat[0]);
         tap_cols("s2s.depth_flat", xh + Hi, ldx, B, c.depth_out);
         // chain C (caller's stream): RGB encoder, flat mode (seq2seq.py:155)
         on(main_s);
         if (m.ablate_rgb) {
             if (!dry) ck(hipMemset2DAsync(xh + Hi + c.depth_out, (size_t)ldx * 4, 0, (size_t)c.rgb_out * 4, B, s), "ablate: zero rgb features");   // seq2seq.py:160-161
-        } else lo_rgb(rgb, rgb_dt, B, lb);
+        } else lo_rgb(rgb, rgb_dt, B, lb, call.rgb_feat[0]);
         tap_cols("s2s.rgb_flat", xh + Hi + c.depth_out, ldx, B, c.rgb_out);
         if (multi) fork_join_end(2);
 
@@ -1746,6 +1801,82 @@ struct Fwd {
         for (; i < ctx->mark_names.size(); ++i) if (ctx->mark_names[i] == name) break;
         if (i == ctx->mark_names.size()) { if (i >= 256) return; ctx->mark_names.push_back(name); }
         ck(launch_mark(ctx->marks_dev + i, s), "mark");
+    }
+
+    // ---------------------------------------------------------------- hcm_encode_features: the trunks and their pools alone, written out as hcm_features.
+    // One RGB trunk pass -> up to two features: the (4,4) token pool of a spatial encoder from channels [c_sp, c_sp + 2048) of the trunk output and
+    // the global pool of a flat encoder from [c_fl, c_fl + 2048) -- the pooling launches of hi_rgb / lo_rgb / rgb_shared / rgb_pair, then the export
+    void enc_rgb(const TrunkW& t, int B, float* sp, int c_sp, float* fl, int c_fl, const std::string& name) {
+        use(ctx->dt_rgb);
+        Act o = rgb_trunk(t, call.rgb, call.rgb_dt, B, name);
+        const int C1 = 2048;
+        if (sp || dry) {                                          // (the sizing pass of hcm_finalize: both pools)
+            void* tok = alloc_t((size_t)B * 16 * C1);
+            if (!dry) ck(launch_adaptive_avgpool((char*)o.p + (size_t)c_sp * esz, tok, dt, B, o.H, o.W, C1, 4, 4, C1, s, o.C), "rgb tokens (export)");
+            feat_out(tok, sp, B, C1, 16, C1, 1.f / rgb_scale());
+        }
+        if (fl || dry) {
+            void* pooled = alloc_t((size_t)B * C1);
+            if (!dry) ck(launch_adaptive_avgpool((char*)o.p + (size_t)c_fl * esz, pooled, dt, B, o.H, o.W, C1, 1, 1, C1, s, o.C), "global avgpool (export)");
+            feat_out(pooled, fl, B, C1, 1, C1, 1.f / rgb_scale());
+        }
+    }
+    // One depth trunk pass -> up to two features, straight from its last activation [B][S][o.C] (the token pool is the identity on that map and
+    // visual_fc reads the activation itself): channels [c0, c0 + C) and [c1, c1 + C)
+    void enc_depth(const TrunkW& t, int B, float* f0, int c0, float* f1, int c1, const std::string& name) {
+        use(ctx->dt_depth);
+        Act o = depth_trunk(t, call.depth, B, name);
+        const int C = depth_true_c(t);
+        feat_out((char*)o.p + (size_t)c0 * esz, f0, B, C, o.H * o.W, o.C, 1.f);
+        feat_out((char*)o.p + (size_t)c1 * esz, f1, B, C, o.H * o.W, o.C, 1.f);
+    }
+    void encode(int B) {
+        ar.reset();
+        const bool multi = ctx->concurrent && !ctx->taps_on;
+        hipStream_t main_s = call.stream;
+        hipStream_t a0 = multi ? ctx->aux[0] : main_s, a1 = multi ? ctx->aux[1] : main_s;
+        // (null everywhere in the sizing pass of hcm_finalize, which then takes every trunk the handle has: `|| dry` below)
+        float* const r0 = call.enc_rgb[0]; float* const r1 = call.enc_rgb[1]; float* const d0 = call.enc_depth[0]; float* const d1 = call.enc_depth[1];
+        if (multi) fork_join_begin(2);
+        if (ctx->kind != 0) {
+            // CMANet: both encoders spatial; Seq2SeqNet: both flat (the low-level model's paths)
+            const bool flat = ctx->kind == 2;
+            on(a1);
+            const bool dep_ok = flat ? !ctx->lo.depth_simple && !ctx->s2s_cfg.ablate_depth : !ctx->cma_cfg.ablate_depth;
+            if (dep_ok && (d0 || dry)) enc_depth(flat ? ctx->lo.depth : ctx->cma.depth, B, d0, 0, nullptr, 0, flat ? "lo.depth" : "cma.depth");
+            on(main_s);
+            const bool rgb_ok = flat ? !ctx->lo.rgb_simple && !ctx->s2s_cfg.ablate_rgb : !ctx->cma_cfg.ablate_rgb;
+            if (rgb_ok && (r0 || dry)) enc_rgb(flat ? ctx->lo.rgb : ctx->cma.rgb, B, flat ? nullptr : r0, 0, flat ? r0 : nullptr, 0, flat ? "lo.rgb" : "cma.rgb");
+            if (multi) fork_join_end(2);
+            return;
+        }
+        const hcm_config& c = ctx->cfg;
+        const bool hi = c.build_high != 0, lo = c.build_low != 0;
+        // depth trunks on aux 1, one behind the other (as in hcm_val_step)
+        on(a1);
+        if (!c.ablate_depth) {
+            const bool w0 = hi && (d0 || dry), w1 = lo && !ctx->lo.depth_simple && (d1 || dry);
+            if (w0 && w1 && ctx->hi.depth_shared) enc_depth(ctx->hi.depth, B, d0, 0, d1, 0, "hi.depth");
+            else if (w0 && w1 && call.enc_act && ctx->hi.has_depth_pair) enc_depth(ctx->hi.depth_pair, B, d0, 0, d1, ctx->hi.depth_pair.compress.Cout, "pair.depth");
+            else {
+                if (w0) enc_depth(ctx->hi.depth, B, d0, 0, nullptr, 0, "hi.depth");
+                if (w1) enc_depth(ctx->lo.depth, B, nullptr, 0, d1, 0, "lo.depth");
+            }
+        }
+        // the high-level RGB trunk on the caller's stream, the low-level one beside it on aux 0
+        on(main_s);
+        if (!c.ablate_rgb) {
+            const bool w0 = hi && (r0 || dry), w1 = lo && !ctx->lo.rgb_simple && (r1 || dry);
+            if (w0 && w1 && ctx->hi.rgb_shared) enc_rgb(ctx->hi.rgb, B, r0, 0, r1, 0, "hi.rgb");
+            else if (w0 && w1 && call.enc_act && ctx->hi.has_rgb_pair) enc_rgb(ctx->hi.rgb_pair, B, r0, 0, r1, 2048, "pair.rgb");
+            else {
+                if (w0) enc_rgb(ctx->hi.rgb, B, r0, 0, nullptr, 0, "hi.rgb");
+                on(w0 ? a0 : main_s);
+                if (w1) enc_rgb(ctx->lo.rgb, B, nullptr, 0, r1, 0, "lo.rgb");
+                on(main_s);
+            }
+        }
+        if (multi) fork_join_end(2);
     }
 
     void step(bool do_hi, bool do_lo, const void* rgb, int rgb_dt, const float* depth, const void* ids, int ids_dt, int B,
@@ -1818,20 +1949,23 @@ struct Fwd {
         on(a1);
         chain_begin();
         mark("depth.start");
-        const bool dshare = do_hi && do_lo && !val.on && ctx->hi.depth_shared && !ctx->lo.depth_simple;
+        // (a model whose feature the caller passes -- hcm_features -- has no trunk to run: the shared / paired forms serve calls without any)
+        const float* const rf_hi = call.rgb_feat[0]; const float* const rf_lo = call.rgb_feat[1];
+        const float* const df_hi = call.depth_feat[0]; const float* const df_lo = call.depth_feat[1];
+        const bool dshare = do_hi && do_lo && !val.on && ctx->hi.depth_shared && !ctx->lo.depth_simple && !df_hi && !df_lo;
         // (hcm_val_step promises the bits of the single-model sequence calls: it runs each model's trunks with those calls' own launches, side by
         //  side on the chains' streams, not as shared trunks or hi|lo pairs, whose grouped launches agree with them to round-off only)
-        const bool pair = do_hi && do_lo && !val.on && ctx->hi.has_depth_pair && !ctx->lo.depth_simple;
+        const bool pair = do_hi && do_lo && !val.on && ctx->hi.has_depth_pair && !ctx->lo.depth_simple && !df_hi && !df_lo;
         if (ctx->cfg.ablate_depth) {
             if (!(skip & 4)) ablated_encoder(1, B, do_hi ? &hb : nullptr, do_lo ? &lb : nullptr);
         } else if (dshare) {
             if (!(skip & 4)) depth_shared(depth, B, hb, lb);
         } else if (pair) {
             if (!(skip & 4)) depth_pair(depth, B, hb, lb);
-        } else if (do_hi && !(skip & 4)) hi_depth(depth, B, hb);
+        } else if (do_hi && !(skip & 4)) hi_depth(depth, B, hb, df_hi);
         on(a3);
         if (val.on) mark("lodepth.start");
-        if (do_lo && !pair && !dshare && !ctx->cfg.ablate_depth && !(skip & 4)) lo_depth(depth, B, lb);
+        if (do_lo && !pair && !dshare && !ctx->cfg.ablate_depth && !(skip & 4)) lo_depth(depth, B, lb, df_lo);
         if (val.on) mark("lodepth.end");
         on(a1);
         mark("depth.end");
@@ -1840,17 +1974,17 @@ struct Fwd {
         on(main_s);
         chain_begin();
         mark("rgb.start");
-        const bool rshare = do_hi && do_lo && !val.on && ctx->hi.rgb_shared && !ctx->lo.rgb_simple;
-        const bool rpair = do_hi && do_lo && !val.on && ctx->hi.has_rgb_pair && !ctx->lo.rgb_simple;
+        const bool rshare = do_hi && do_lo && !val.on && ctx->hi.rgb_shared && !ctx->lo.rgb_simple && !rf_hi && !rf_lo;
+        const bool rpair = do_hi && do_lo && !val.on && ctx->hi.has_rgb_pair && !ctx->lo.rgb_simple && !rf_hi && !rf_lo;
         if (ctx->cfg.ablate_rgb) { if (!(skip & 1)) ablated_encoder(0, B, do_hi ? &hb : nullptr, do_lo ? &lb : nullptr); }
         else if (rshare) { if (!(skip & 1)) rgb_shared(rgb, rgb_dt, B, hb, lb); }
         else if (rpair) { if (!(skip & 1)) rgb_pair(rgb, rgb_dt, B, hb, lb); }
-        else if (!(skip & 1)) { if (do_hi) hi_rgb(rgb, rgb_dt, B, hb); else lo_rgb(rgb, rgb_dt, B, lb); }
+        else if (!(skip & 1)) { if (do_hi) hi_rgb(rgb, rgb_dt, B, hb, rf_hi); else lo_rgb(rgb, rgb_dt, B, lb, rf_lo); }
         // chain 1: the low-level RGB trunk
         static const int rgb_serial = dev_env("HCM_RGB_SERIAL") ? atoi(dev_env("HCM_RGB_SERIAL")) : 1;
         if (val.on) { mark("rgb.hi_end"); on(a0); mark("lorgb.start"); }
         else on((rgb_serial || call.host_frames) ? main_s : a0);        // (staged frames: behind their copy)
-        if (do_hi && do_lo && !rpair && !rshare && !ctx->cfg.ablate_rgb && !(skip & 2)) lo_rgb(rgb, rgb_dt, B, lb);
+        if (do_hi && do_lo && !rpair && !rshare && !ctx->cfg.ablate_rgb && !(skip & 2)) lo_rgb(rgb, rgb_dt, B, lb, rf_lo);
         if (val.on) mark("lorgb.end");
         on(main_s);
         mark("rgb.end");
@@ -1903,7 +2037,8 @@ struct Fwd {
 // entry points used by api.cpp (model.h)
 void run_forward(hcm_ctx* ctx, const FwdCall& c) {
     Fwd f(ctx, c);
-    if (ctx->kind == 1) f.cma_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.lo_h_in, c.mask, c.vel, c.stop, c.lo_h_out);
+    if (c.encode) f.encode(c.rows);
+    else if (ctx->kind == 1) f.cma_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.lo_h_in, c.mask, c.vel, c.stop, c.lo_h_out);
     else if (ctx->kind == 2) f.s2s_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.Bi, c.lo_h_in, c.mask, c.vel, c.stop, c.progress, c.lo_h_out);
     else f.step(c.do_hi, c.do_lo, c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.hi_h_in, c.lo_h_in, c.mask, c.subtask, c.logits, c.ld_logits,
                 c.vel, c.ld_vel, c.stop, c.ld_stop, c.hi_h_out, c.lo_h_out);

@@ -354,5 +354,11 @@ bool depth_conv8x8s4_ok(int dt, int H, int act);
 hipError_t launch_depth_conv8x8s4(const float* x, const void* w, const float* bias, void* y, int dt, int B, int H, int act, hipStream_t s);
 // storage-type conversion between sub-networks (e.g. fp16 depth tokens -> bf16 cross-modal block)
 hipError_t launch_convert(const void* x, int dt_in, void* y, int dt_out, size_t n, hipStream_t s);
+// features.hip: precomputed trunk features at the ABI (hcm_features: the reference's NCHW f32 `rgb_features` / `depth_features`) <-> the buffer a
+// trunk's pooling launch writes.  x (rows, C, S) f32 contiguous; y [rows][S][ld] in storage type dt, columns [0, C): the token rows of a spatial
+// encoder (ld = C + 64), the pooled row of flat RGB (S = 1, ld = C), the NHWC-flattened row visual_fc reads (ld = C).  The value is multiplied by
+// `scale`, a power of two (the RGB trunk's range fold, or its inverse on the way out): exact in every storage type.  Any rows, C, S >= 1.
+hipError_t launch_feat_ingest(const float* x, void* y, int dt, int rows, int C, int S, int ld, float scale, hipStream_t s);
+hipError_t launch_feat_export(const void* y, int dt, float* x, int rows, int C, int S, int ld, float scale, hipStream_t s);
 
 }  // namespace hcm

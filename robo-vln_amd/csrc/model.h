@@ -187,6 +187,13 @@ struct FwdCall {
     bool do_hi = false, do_lo = false;        // HCM handle: the models that run; a CMANet / Seq2SeqNet handle (hcm_ctx::kind) runs its one model
     const void* rgb = nullptr; int rgb_dt = DT_F32;
     const float* depth = nullptr;
+    // hcm_features: precomputed trunk outputs, [0] the high-level model / a flat handle's model, [1] the low-level model; non-null replaces that trunk
+    const float* rgb_feat[2] = {nullptr, nullptr};
+    const float* depth_feat[2] = {nullptr, nullptr};
+    // hcm_encode_features: trunks and pools only, written out in the hcm_features layouts (null = not wanted); enc_act: hcm_act's trunk launches
+    bool encode = false, enc_act = false;
+    float* enc_rgb[2] = {nullptr, nullptr};
+    float* enc_depth[2] = {nullptr, nullptr};
     const void* ids = nullptr; int ids_dt = DT_I64;
     const int* lens = nullptr;                // optional per-row instruction lengths (device, [rows]); null = all L
     int rows = 0;                             // frames: B of a step, T * N of a sequence call (time-major)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import _TORCH_DT, _EngineBase, _np32, _ptr       # noqa: F401  (_np32: importable from here as before)
+from ._engine import _TORCH_DT, _EngineBase, _FeatureFrames, _np32, _ptr, obs_rows       # noqa: F401  (_np32: importable from here as before)
 from .config import HCMConfig
 
 _SUB_SLOTS = {"depth": 0, "bert": 1, "vla": 2, "rgb": 3}
@@ -218,19 +218,31 @@ class HCMEngine(_EngineBase):
             raise ValueError(f"host_frames=True: {name} must be a contiguous pinned CPU tensor of dtype {' / '.join(str(d) for d in dtypes)}")
         return t
 
-    def _obs(self, observations, need_ids, host_frames=False):
+    def _has_slot(self, slot):
+        return self.has_high if slot == 0 else self.has_low
+
+    def _frame_check(self, rgb, depth, host_frames=False):
         if host_frames:
-            rgb = self._host_frame(observations["rgb"], (torch.float32, torch.uint8), "rgb")
-            depth = self._host_frame(observations["depth"], (torch.float32,), "depth")
+            rgb = self._host_frame(rgb, (torch.float32, torch.uint8), "rgb")
+            depth = self._host_frame(depth, (torch.float32,), "depth")
         else:
-            rgb = self._dev(observations["rgb"], (torch.float32, torch.uint8))
-            depth = self._dev(observations["depth"], (torch.float32,))
+            rgb = self._dev(rgb, (torch.float32, torch.uint8))
+            depth = self._dev(depth, (torch.float32,))
         B = rgb.shape[0]
         c = self.cfg
         if tuple(rgb.shape[1:]) != (*c.rgb_shape, 3):
             raise ValueError(f"rgb must be (B,{c.rgb_shape[0]},{c.rgb_shape[1]},3), got {tuple(rgb.shape)}")
         if tuple(depth.shape) != (B, *c.depth_shape, 1):
             raise ValueError(f"depth must be (B,{c.depth_shape[0]},{c.depth_shape[1]},1), got {tuple(depth.shape)}")
+        return rgb, depth
+
+    def _enc_frames(self, observations):
+        return self._frame_check(observations["rgb"], observations["depth"])
+
+    def _obs(self, observations, need_ids, host_frames=False, slots=(0, 1)):
+        """slots: the models the call runs (0 high-level, 1 low-level) -- whose rgb_features / depth_features it takes (_EngineBase._frames)"""
+        rgb, depth, B = self._frames(observations, tuple(s for s in slots if self._has_slot(s)) or slots,
+                                     lambda r, d: self._frame_check(r, d, host_frames), host_frames)
         ids = lens = None
         if need_ids:
             ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
@@ -261,7 +273,7 @@ class HCMEngine(_EngineBase):
     # ---- the three calls
     def high_forward(self, observations, hidden, masks):
         with torch.cuda.device(self.device):
-            rgb, depth, ids, lens, B = self._obs(observations, True)
+            rgb, depth, ids, lens, B = self._obs(observations, True, slots=(0,))
             h_in, m = self._hidden(hidden, B), self._mask(masks, B)
             logits = torch.empty(B, self.cfg.num_actions, device=self.device, dtype=torch.float32)
             h_out = torch.empty_like(h_in)
@@ -272,7 +284,7 @@ class HCMEngine(_EngineBase):
 
     def low_forward(self, observations, hidden, masks, subtask):
         with torch.cuda.device(self.device):
-            rgb, depth, _, _, B = self._obs(observations, False)
+            rgb, depth, _, _, B = self._obs(observations, False, slots=(1,))
             h_in, m = self._hidden(hidden, B), self._mask(masks, B)
             st = self._dev(subtask, (torch.int64,)).reshape(B)
             vel = torch.empty(B, self.cfg.lo_actions, device=self.device, dtype=torch.float32)
@@ -294,10 +306,11 @@ class HCMEngine(_EngineBase):
             if self._gstream is None:
                 self._gstream = torch.cuda.Stream(device=self.device)
             st = self._static
+            feat = isinstance(rgb, _FeatureFrames)      # features are read in place: the graph is keyed by the pointers in the struct
             if st is None or st["B"] != B or st["rgb"].dtype != rgb.dtype or st["ids"].dtype != ids.dtype or st["rgb"].device != rgb.device:
                 # the static ids buffer holds the longest instruction; a call uses its first B*L elements, so the graph of a new L
                 # differs by its key only, not by the buffer address
-                st = {"B": B, "tick": 0, "rgb": torch.empty_like(rgb), "depth": torch.empty_like(depth),
+                st = {"B": B, "tick": 0, "rgb": rgb if feat else torch.empty_like(rgb), "depth": depth if feat else torch.empty_like(depth),
                       "ids": torch.empty(B * self.max_instr_len, device=self.device, dtype=ids.dtype),
                       "lens": torch.empty(B, device=self.device, dtype=torch.int32),
                       "mask": torch.empty_like(m), "rec": [torch.empty(B, 7, device=self.device) for _ in range(2)],
@@ -310,7 +323,7 @@ class HCMEngine(_EngineBase):
             # output buffers) are read in place: the captured graph is keyed by their addresses like by any other argument.
             # Tensors seen for the first time go through the engine's static copies, so that fresh allocations every step
             # do not force a new capture every step.
-            ptrs = (rgb.data_ptr(), depth.data_ptr(), ids.data_ptr(), m.data_ptr(), L, lens.data_ptr() if lens is not None else 0)
+            ptrs = (rgb.pointers() if feat else (rgb.data_ptr(), depth.data_ptr())) + (ids.data_ptr(), m.data_ptr(), L, lens.data_ptr() if lens is not None else 0)
             # (a caller that rotates a few buffer sets -- double-buffered staging -- is recognised as well: the last four sets)
             seen = st.setdefault("seen_ptrs", [])
             direct = ptrs in seen and not os.environ.get("HCM_NO_DIRECT_OBS")
@@ -321,7 +334,7 @@ class HCMEngine(_EngineBase):
             st["hold"] = (rgb, depth, ids, m, lens)        # keep the caller's tensors alive while the graph may read them
             s_ids = st["ids"][:B * L].view(B, L)
             g_rgb, g_depth, g_ids, g_m = (rgb, depth, ids, m) if direct else (st["rgb"], st["depth"], s_ids, st["mask"])
-            if host_frames:                                # pinned host frames are always read in place (the library stages them)
+            if host_frames or feat:                        # pinned host frames are always read in place (the library stages them); so are features
                 g_rgb, g_depth = rgb, depth
             g_lens = None if lens is None else lens if direct else st["lens"]
             with torch.cuda.stream(gs):
@@ -353,7 +366,7 @@ class HCMEngine(_EngineBase):
     # ---- training / validation path: T*N frames per call, RNNStateEncoder.seq_forward (state_encoder.py:83-133)
     def high_forward_seq(self, observations, hidden, masks):
         with torch.cuda.device(self.device):
-            rgb, depth, ids, lens, TN = self._obs(observations, True)
+            rgb, depth, ids, lens, TN = self._obs(observations, True, slots=(0,))
             h_in = self._hidden(hidden)
             N = h_in.shape[1]
             if TN % N:
@@ -368,7 +381,7 @@ class HCMEngine(_EngineBase):
 
     def low_forward_seq(self, observations, hidden, masks, subtask):
         with torch.cuda.device(self.device):
-            rgb, depth, _, _, TN = self._obs(observations, False)
+            rgb, depth, _, _, TN = self._obs(observations, False, slots=(1,))
             h_in = self._hidden(hidden)
             N = h_in.shape[1]
             if TN % N:
@@ -481,7 +494,7 @@ class HCMEngine(_EngineBase):
                     cg = min(observations["rgb"].numel() * observations["rgb"].element_size(),
                              observations["depth"].numel() * observations["depth"].element_size()) >= (4 << 20)
                 else:
-                    cg = int(observations["rgb"].shape[0]) <= 2
+                    cg = obs_rows(observations) <= 2
             if cg:
                 flags |= _lib.HCM_ACT_CHAIN_GRAPHS
         if self._graph:
@@ -570,7 +583,7 @@ class Seq2Seq_HighLevel_CMA(_ModelBase):
     def forward(self, batch):
         observations, rnn_hidden_states, prev_actions, masks = batch   # prev_actions unused (use_prev_action=False)
         # RNNStateEncoder.forward dispatch (state_encoder.py:135-137): frames == hidden batch -> single step, else sequence
-        if observations["rgb"].shape[0] == rnn_hidden_states.shape[1]:
+        if obs_rows(observations) == rnn_hidden_states.shape[1]:
             logits, hidden = self.engine.high_forward(observations, rnn_hidden_states, masks)
         else:
             logits, hidden = self.engine.high_forward_seq(observations, rnn_hidden_states, masks)
@@ -585,7 +598,7 @@ class Seq2Seq_LowLevel(_ModelBase):
 
     def forward(self, batch):
         observations, rnn_hidden_states, prev_actions, masks, discrete_actions = batch
-        if observations["rgb"].shape[0] == rnn_hidden_states.shape[1]:
+        if obs_rows(observations) == rnn_hidden_states.shape[1]:
             return self.engine.low_forward(observations, rnn_hidden_states, masks, discrete_actions)
         return self.engine.low_forward_seq(observations, rnn_hidden_states, masks, discrete_actions)
 

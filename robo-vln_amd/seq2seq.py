@@ -51,21 +51,28 @@ class S2SEngine(_FlatEngine):
 
     def _inputs(self, observations, rows):
         c = self.cfg
-        rgb = self._dev(observations["rgb"], (torch.float32, torch.uint8))
-        depth = self._dev(observations["depth"], (torch.float32,))
-        B = rgb.shape[0]
+        rgb, depth, B = self._frames(observations, (0,), self._frame_check)      # (or rgb_features / depth_features)
         if rows is not None and B != rows:
             raise ValueError(f"expected {rows} frames, got {B}")
-        if tuple(rgb.shape[1:]) != (*c.rgb_shape, 3):
-            raise ValueError(f"rgb must be (B,{c.rgb_shape[0]},{c.rgb_shape[1]},3), got {tuple(rgb.shape)}")
-        if tuple(depth.shape) != (B, *c.depth_shape, 1):
-            raise ValueError(f"depth must be (B,{c.depth_shape[0]},{c.depth_shape[1]},1), got {tuple(depth.shape)}")
         ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
         # cfg.instr_len is the longest padded instruction the workspace is sized for; every call brings its own L.  A (1, L) instruction is NOT
         # expanded here: the library encodes it once and writes the vector to all B rows (seq2seq.py:163)
         if ids.dim() != 2 or ids.shape[0] not in (1, B) or not 1 <= ids.shape[1] <= c.instr_len:
             raise ValueError(f"instruction must be (B or 1, L <= {c.instr_len}), got {tuple(ids.shape)}")
         return rgb, depth, ids, B
+
+    def _frame_check(self, rgb, depth):
+        c = self.cfg
+        rgb = self._dev(rgb, (torch.float32, torch.uint8))
+        depth = self._dev(depth, (torch.float32,))
+        if tuple(rgb.shape[1:]) != (*c.rgb_shape, 3):
+            raise ValueError(f"rgb must be (B,{c.rgb_shape[0]},{c.rgb_shape[1]},3), got {tuple(rgb.shape)}")
+        if tuple(depth.shape) != (rgb.shape[0], *c.depth_shape, 1):
+            raise ValueError(f"depth must be (B,{c.depth_shape[0]},{c.depth_shape[1]},1), got {tuple(depth.shape)}")
+        return rgb, depth
+
+    def _enc_frames(self, observations):
+        return self._frame_check(observations["rgb"], observations["depth"])
 
     def _outputs(self, B):
         c = self.cfg

@@ -15,7 +15,64 @@ def split_rows(t, steps):
     return t.split(steps, dim=0)
 
 
-class HCMValidator:
+def _map_feats(feats, fn):
+    """fn over the tensors of an encode_features() dict (a value is one tensor, or a (high, low) pair with None where an encoder takes none)"""
+    return {k: (tuple(None if t is None else fn(t) for t in v) if isinstance(v, (tuple, list)) else fn(v)) for k, v in feats.items()}
+
+
+class _FeatureCache:
+    """cache_features=True for the two validators.  Both trunks are frozen in the reference (resnet_encoders.py:35-36, :146-149) and val_epoch
+    walks the same recorded frames every epoch, so every epoch after the first recomputes the same trunk outputs.  With the cache the first run()
+    over a list of batches encodes each chunk once (engine.encode_features) and keeps the result per (batch, chunk); that run and every later one
+    hand the chunk to val_step under the reference's feature keys (`rgb_features`, `depth_features`) with no `rgb` / `depth` -- the same bits as
+    from the frames.  cache_device "cuda" keeps the features on the engine's device, "cpu" in pinned host memory.  A later run() must bring the
+    same batches: the same number of chunks with the same row counts (ValueError otherwise); clear_cache() forgets them."""
+
+    def _init_cache(self, cache_features, cache_device):
+        if cache_device not in ("cuda", "cpu"):
+            raise ValueError('cache_device must be "cuda" or "cpu"')
+        self.cache_features = bool(cache_features)
+        self.cache_device = cache_device
+        self.clear_cache()
+
+    def clear_cache(self):
+        self._cache = {}
+        self._cache_full = False        # a run() has completed: the set of (batch, chunk) keys is closed
+
+    def _keep(self, t):
+        if self.cache_device == "cuda":
+            return t
+        host = torch.empty(t.shape, dtype=t.dtype, pin_memory=torch.cuda.is_available())
+        host.copy_(t)
+        return host
+
+    def _chunk_obs(self, batch_idx, chunk_idx, obs, rows):
+        """the chunk's observations as val_step gets them: unchanged without the cache, else the feature keys in place of the frames"""
+        if not self.cache_features:
+            return obs
+        key = (batch_idx, chunk_idx)
+        hit = self._cache.get(key)
+        if hit is None:
+            if self._cache_full:
+                raise ValueError(f"cache_features: batch {batch_idx} chunk {chunk_idx} was not part of the cached run (clear_cache() first)")
+            feats = self.engine.encode_features(obs)
+            hit = self._cache[key] = (rows, _map_feats(feats, self._keep))
+        elif hit[0] != rows:
+            raise ValueError(f"cache_features: batch {batch_idx} chunk {chunk_idx} has {rows} rows, the cached features {hit[0]} "
+                             "(clear_cache() before validating other batches)")
+        out = {k: v for k, v in obs.items() if k not in ("rgb", "depth")}
+        out.update(hit[1])
+        return out
+
+    def _close_cache(self, n_keys):
+        if not self.cache_features:
+            return
+        if self._cache_full and n_keys != len(self._cache):
+            raise ValueError(f"cache_features: this run had {n_keys} chunks, the cached one {len(self._cache)} (clear_cache() first)")
+        self._cache_full = True
+
+
+class HCMValidator(_FeatureCache):
     """val_epoch over batches shaped as the trainer's `collate_fn` (hierarchical_trainer.py:66-154) returns them:
 
         (observations, prev_actions, not_done_masks, corrected_actions, oracle_stop)
@@ -29,14 +86,16 @@ class HCMValidator:
     (one per trajectory) is repeated for every time step of the chunk.
 
     `engine` needs `val_step`, `num_recurrent_layers`, `cfg.hidden`, `device` and `check_val_result` -- HCMEngine, or a stand-in in tests.
+    cache_features / cache_device: see _FeatureCache (off by default; the engine then needs `encode_features` too).
     """
 
-    def __init__(self, engine, tbptt_steps, batch_size):
+    def __init__(self, engine, tbptt_steps, batch_size, cache_features=False, cache_device="cuda"):
         if tbptt_steps < 1 or batch_size < 1:
             raise ValueError("tbptt_steps and batch_size must be >= 1")
         self.engine = engine
         self.tbptt_steps = int(tbptt_steps)
         self.batch_size = int(batch_size)
+        self._init_cache(cache_features, cache_device)
 
     def _instruction(self, ids, rows):
         N = self.batch_size
@@ -58,7 +117,8 @@ class HCMValidator:
         eng, N, S = self.engine, self.batch_size, self.tbptt_steps
         R, H, dev = eng.num_recurrent_layers, eng.cfg.hidden, eng.device
         tables = []
-        for batch in batches:
+        n_keys = 0
+        for bi, batch in enumerate(batches):
             observations, _prev_actions, not_done_masks, corrected_actions, oracle_stop = batch
             rows_total = corrected_actions.shape[0]
             per_key = {k: (None if k == "instruction" else split_rows(torch.as_tensor(v), S)) for k, v in observations.items()}
@@ -79,10 +139,13 @@ class HCMValidator:
                 rows = c_split[i].shape[0]
                 obs = {k: v[i] for k, v in per_key.items() if v is not None}
                 obs["instruction"] = self._instruction(ids, rows)
+                obs = self._chunk_obs(bi, i, obs, rows)
+                n_keys += 1
                 _, hh, lh = eng.val_step(obs, c_split[i], s_split[i], hh, lh, m_split[i], result=table[i])
             tables.append(table)
         if not tables:
             raise ValueError("no batches")
+        self._close_cache(n_keys)
         table = eng.check_val_result(torch.cat(tables, 0))  # the one device-to-host read; raises on out-of-range labels
         total = float(table[:, 4].sum())
         return {
@@ -94,7 +157,7 @@ class HCMValidator:
         }
 
 
-class FlatValidator:
+class FlatValidator(_FeatureCache):
     """val_epoch of the flat trainer (robo_vln_trainer.py:726-813) over batches shaped as its `collate_fn` returns them:
 
         (observations, prev_actions, not_done_masks, corrected_actions, oracle_stop)
@@ -109,14 +172,16 @@ class FlatValidator:
     instruction (one per trajectory) is repeated for every time step of the chunk.
 
     `engine` needs `val_step`, `num_recurrent_layers`, `cfg.hidden` and `device` -- CMAEngine, S2SEngine, or a stand-in in tests.
+    cache_features / cache_device: see _FeatureCache (off by default; the engine then needs `encode_features` too).
     """
 
-    def __init__(self, engine, tbptt_steps, batch_size):
+    def __init__(self, engine, tbptt_steps, batch_size, cache_features=False, cache_device="cuda"):
         if tbptt_steps < 1 or batch_size < 1:
             raise ValueError("tbptt_steps and batch_size must be >= 1")
         self.engine = engine
         self.tbptt_steps = int(tbptt_steps)
         self.batch_size = int(batch_size)
+        self._init_cache(cache_features, cache_device)
 
     def _instruction(self, ids, rows):
         N = self.batch_size
@@ -134,7 +199,8 @@ class FlatValidator:
         eng, N, S = self.engine, self.batch_size, self.tbptt_steps
         R, H, dev = eng.num_recurrent_layers, eng.cfg.hidden, eng.device
         tables = []
-        for batch in batches:
+        n_keys = 0
+        for bi, batch in enumerate(batches):
             observations, _prev_actions, not_done_masks, corrected_actions, oracle_stop = batch
             rows_total = corrected_actions.shape[0]
             per_key = {k: (None if k == "instruction" else split_rows(torch.as_tensor(v), S)) for k, v in observations.items()}
@@ -154,10 +220,13 @@ class FlatValidator:
                 rows = c_split[i].shape[0]
                 obs = {k: v[i] for k, v in per_key.items() if v is not None}
                 obs["instruction"] = self._instruction(ids, rows)
+                obs = self._chunk_obs(bi, i, obs, rows)
+                n_keys += 1
                 _, h = eng.val_step(obs, c_split[i], s_split[i], h, m_split[i], result=table[i])
             tables.append(table)
         if not tables:
             raise ValueError("no batches")
+        self._close_cache(n_keys)
         table = torch.cat(tables, 0).detach().to("cpu", torch.float32)      # the one device-to-host read
         t = table[:, :3].double()
         return {

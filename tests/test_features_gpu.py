@@ -1,0 +1,485 @@
+"""Precomputed trunk features on the GPU (hcm_features / hcm_encode_features, the `rgb_features` / `depth_features` observation keys of the
+reference's encoders, resnet_encoders.py:83-86, :207-214): the exported features against the CPU oracle's trunks, the oracle's features fed in
+against the oracle's frame forward, the round trip frames -> encode_features -> call against the frame call BIT FOR BIT for every entry point,
+mixed frames / features, the precedence of a feature over a frame, a range-folded RGB trunk, and the refusals.
+
+Engines: bert_layers = 2, vla_layers = 2, L = 12, 128-pixel frames, plus one at depth 192 (3 x 3 map: odd S, 228 channels padded to 256 inside) and
+one at RGB 160 x 224 (a 5 x 7 map: the (4,4) pool in front of the export is not the identity); rows 1 and 3, (T, N) = (4, 2) for the sequence and
+validation calls.  One engine per (kind, variant, precision) for the whole module.
+
+Bars: max-abs error over max |reference|, 1e-3 in fp32 mode and 1e-2 in the 16-bit modes (tests/test_parity_gpu.py's output tolerances).  The
+round trips are torch.equal: the fold is a power of two and f32 holds every fp16 / bf16 value, so ingest restores the stored bits."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import hcm_oracle
+from robo_vln_amd import _lib, synth
+from robo_vln_amd.config import HCMConfig
+from tests import cma_seq_cases, features_ref, s2s_ref
+
+pytestmark = pytest.mark.gpu
+
+TOL = {"fp32": 1e-3, "fp16": 1e-2, "bf16": 1e-2}
+SEED = 5
+T, N = 4, 2
+VARIANTS = {"base": dict(rgb_hw=128, depth_hw=128), "d192": dict(rgb_hw=128, depth_hw=192), "r160": dict(rgb_hw=160, rgb_w=224, depth_hw=128)}
+
+
+def hcm_cfg(variant="base"):
+    return HCMConfig(instr_len=12, vla_layers=2, bert_layers=2, rnn_type="GRU", **VARIANTS[variant]).validate()
+
+
+def cma_cfg():
+    return cma_seq_cases.seq_case("cma_seq_T4_N2_L12")[0]
+
+
+def s2s_cfg():
+    return s2s_ref.seq_case("s2s_seq_T4_N2_gru")[0]
+
+
+def _shared_weights(cfg):
+    """both state_dicts with ONE set of trunk weights, as the reference's frozen pretrained encoders give them"""
+    hi, lo = synth.make_weights(cfg, SEED)
+    lo = dict(lo)
+    for k, v in hi.items():
+        if k.startswith(("rgb_encoder.cnn.", "depth_encoder.visual_encoder.")) and k in lo:
+            lo[k] = v
+    return hi, lo
+
+
+_weights = {}
+
+
+def weights(kind, variant="base"):
+    if (kind, variant) not in _weights:
+        if kind == "hcm":
+            w = synth.make_weights(hcm_cfg(variant), SEED)
+        elif kind == "hcm_shared":
+            w = _shared_weights(hcm_cfg(variant))
+        elif kind == "cma":
+            w = synth.make_cma_weights(cma_cfg(), SEED)
+        else:
+            w = synth.make_s2s_weights(s2s_cfg(), SEED)
+        _weights[(kind, variant)] = w
+    return _weights[(kind, variant)]
+
+
+@pytest.fixture(scope="module")
+def engines():
+    from robo_vln_amd.cma import CMAEngine
+    from robo_vln_amd.policy import HCMEngine
+    from robo_vln_amd.seq2seq import S2SEngine
+    made = {}
+
+    def get(kind, precision, variant="base", graph=False):
+        key = (kind, precision, variant, graph)
+        if key not in made:
+            w = weights(kind, variant)
+            if kind.startswith("hcm"):
+                made[key] = HCMEngine(hcm_cfg(variant), *w, max_batch=T * N, precision=precision, graph=graph, guard_every=0)
+            elif kind == "cma":
+                made[key] = CMAEngine(cma_cfg(), w, max_batch=T * N, precision=precision, graph=graph)
+            else:
+                made[key] = S2SEngine(s2s_cfg(), w, max_batch=T * N, precision=precision, graph=graph)
+        return made[key]
+    yield get
+    for e in made.values():
+        e.close()
+
+
+def observations(kind, rows, variant="base", step=0):
+    if kind.startswith("hcm"):
+        return synth.make_observations(hcm_cfg(variant), rows, step=step, seed=SEED)
+    if kind == "cma":
+        return synth.make_cma_observations(cma_cfg(), rows, step=step, seed=SEED)
+    return synth.make_s2s_observations(s2s_cfg(), rows, step=step, seed=SEED)
+
+
+def cuda(obs):
+    return {k: (tuple(None if t is None else torch.as_tensor(t).cuda() for t in v) if isinstance(v, tuple) else torch.as_tensor(np.asarray(v)).cuda())
+            for k, v in obs.items()}
+
+
+def swap(obs, feats, keys=("rgb", "depth")):
+    """obs with the frames of `keys` replaced by their features"""
+    out = {k: v for k, v in obs.items() if k not in keys}
+    out.update({k + "_features": feats[k + "_features"] for k in keys})
+    return out
+
+
+def rel_err(got, ref):
+    got, ref = torch.as_tensor(got).float().cpu(), torch.as_tensor(ref).float().cpu()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float((got - ref).abs().max() / ref.abs().max())
+
+
+def same(a, b):
+    a = a if isinstance(a, (tuple, list)) else (a,)
+    b = b if isinstance(b, (tuple, list)) else (b,)
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        if isinstance(x, (tuple, list)):
+            same(x, y)
+        elif x is not None or y is not None:
+            assert torch.equal(x, y), float((x.float() - y.float()).abs().max())
+
+
+def state(eng, n):
+    g = torch.Generator().manual_seed(3)
+    return (torch.rand(eng.num_recurrent_layers, n, eng.cfg.hidden, generator=g) - 0.5).cuda()
+
+
+# ---------------------------------------------------------------- 0. the two kernels alone
+@pytest.mark.parametrize("dtype", ["f32", "f16", "bf16"])
+@pytest.mark.parametrize("rows,C,S,ld", [(1, 2048, 16, 2112), (3, 2048, 1, 2048), (3, 128, 16, 192), (2, 228, 9, 320), (3, 130, 9, 131), (2, 57, 36, 64),
+                                         (1, 8, 256, 72)])
+def test_feature_kernels_transpose_convert_and_scale_exactly(rows, C, S, ld, dtype):
+    """(rows, C, S) f32 <-> columns [0, C) of [rows][S][ld]: the 16-byte form (C a multiple of 64, S <= 32), odd S, C and ld, several tiles along
+    S, columns beyond C untouched; values fp16 / bf16 hold exactly and a power-of-two scale, so both directions are exact."""
+    tdt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dtype]
+    code = {"f32": _lib.HCM_F32, "f16": _lib.HCM_F16, "bf16": _lib.HCM_BF16}[dtype]
+    l = _lib.lib()
+    x = (torch.randint(-64, 64, (rows, C, S), generator=torch.Generator().manual_seed(C + S)).float() / 8).cuda()
+    y = torch.full((rows, S, ld), 7.0, dtype=tdt, device="cuda")
+    assert l.hcm_op_feat_ingest(x.data_ptr(), y.data_ptr(), code, rows, C, S, ld, 4.0, None) == 0
+    assert torch.equal(y[:, :, :C].float(), x.transpose(1, 2) * 4) and bool((y[:, :, C:] == 7).all())
+    back = torch.zeros_like(x)
+    assert l.hcm_op_feat_export(y.data_ptr(), code, back.data_ptr(), rows, C, S, ld, 0.25, None) == 0
+    assert torch.equal(back, x)
+    assert l.hcm_op_feat_ingest(x.data_ptr(), y.data_ptr(), code, 0, C, S, ld, 1.0, None) != 0          # rows < 1: refused, nothing launched
+
+
+# ---------------------------------------------------------------- 1. encode against the oracle's trunks
+@pytest.mark.parametrize("variant,rows", [("base", 3), ("d192", 1), ("r160", 3)])
+def test_encode_features_matches_the_oracle_trunks_hcm(variant, rows, engines):
+    eng = engines("hcm", "fp32", variant)
+    cfg = hcm_cfg(variant)
+    obs = observations("hcm", rows, variant)
+    feats = eng.encode_features(cuda(obs))
+    s = cfg.depth_final_spatial()
+    assert tuple(feats["rgb_features"][0].shape) == (rows, 2048, 4, 4) and tuple(feats["rgb_features"][1].shape) == (rows, 2048, 1, 1)
+    assert tuple(feats["depth_features"][0].shape) == tuple(feats["depth_features"][1].shape) == (rows, cfg.depth_compress_channels(), s, s)
+    for slot, sd in enumerate(weights("hcm", variant)):
+        r, d = features_ref.trunk_features(cfg, sd, obs, spatial=slot == 0)
+        er, ed = rel_err(feats["rgb_features"][slot], r), rel_err(feats["depth_features"][slot], d)
+        print(f"encode_features [{variant}, rows {rows}, model {slot}]: rgb {er:.2e} depth {ed:.2e} (<= {TOL['fp32']:.0e})")
+        assert er <= TOL["fp32"] and ed <= TOL["fp32"]
+
+
+@pytest.mark.parametrize("kind", ["cma", "s2s"])
+def test_encode_features_matches_the_oracle_trunks_flat_engines(kind, engines):
+    eng = engines(kind, "fp32")
+    cfg = eng.cfg
+    obs = observations(kind, 3)
+    feats = eng.encode_features(cuda(obs))
+    r, d = features_ref.trunk_features(cfg, weights(kind), obs, spatial=kind == "cma")
+    er, ed = rel_err(feats["rgb_features"], r), rel_err(feats["depth_features"], d)
+    print(f"encode_features [{kind}]: rgb {er:.2e} depth {ed:.2e} (<= {TOL['fp32']:.0e})")
+    assert er <= TOL["fp32"] and ed <= TOL["fp32"]
+
+
+# ---------------------------------------------------------------- 2. ingest alone: the ORACLE's features against the oracle's frame forward
+@pytest.fixture(scope="module")
+def oracle_runs():
+    """per kind: (observations, the oracle's features, the oracle's frame forward) at 3 rows, computed once"""
+    made = {}
+
+    def get(kind):
+        if kind in made:
+            return made[kind]
+        rows = 3
+        obs = observations("hcm" if kind in ("hi", "lo") else kind, rows)
+        h0 = (torch.rand(2, rows, 512, generator=torch.Generator().manual_seed(3)) - 0.5)
+        m = np.array([0.0, 1.0, 1.0], np.float32)
+        if kind in ("hi", "lo"):
+            cfg = hcm_cfg()
+            sd = weights("hcm")[0 if kind == "hi" else 1]
+            R = cfg.num_recurrent_layers
+            feats = features_ref.trunk_features(cfg, sd, obs, spatial=kind == "hi")
+            if kind == "hi":
+                ref = hcm_oracle.HighLevelOracle(cfg, sd).forward(obs, h0[:R], m)
+            else:
+                ref = hcm_oracle.LowLevelOracle(cfg, sd).forward(obs, h0[:R], m, torch.tensor([0, 2, 4]))
+        elif kind == "cma":
+            cfg = cma_cfg()
+            R = cfg.num_recurrent_layers
+            h0 = (torch.rand(R, rows, cfg.hidden, generator=torch.Generator().manual_seed(3)) - 0.5)
+            feats = features_ref.trunk_features(cfg, weights("cma"), obs, spatial=True)
+            ref = hcm_oracle.CMAOracle(cfg, weights("cma")).forward(obs, h0.clone(), m)
+        else:
+            cfg = s2s_cfg()
+            R = cfg.num_recurrent_layers
+            h0 = (torch.rand(R, rows, cfg.hidden, generator=torch.Generator().manual_seed(3)) - 0.5)
+            feats = features_ref.trunk_features(cfg, weights("s2s"), obs, spatial=False)
+            ref = s2s_ref.S2SOracle(cfg, weights("s2s")).forward(obs, h0.clone(), m)
+        made[kind] = (obs, feats, h0[:R].clone(), m, ref)
+        return made[kind]
+    return get
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16"])
+@pytest.mark.parametrize("kind", ["hi", "lo", "cma", "s2s"])
+def test_oracle_features_give_the_oracle_frame_forward(kind, precision, engines, oracle_runs):
+    obs, (rf, df), h0, m, ref = oracle_runs(kind)
+    fobs = {k: v for k, v in obs.items() if k not in ("rgb", "depth")}
+    fobs.update(rgb_features=rf, depth_features=df)
+    fobs = cuda(fobs)
+    mt = torch.from_numpy(m).cuda()
+    if kind == "hi":
+        got = engines("hcm", precision).high_forward(fobs, h0.cuda(), mt)
+    elif kind == "lo":
+        got = engines("hcm", precision).low_forward(fobs, h0.cuda(), mt, torch.tensor([0, 2, 4]).cuda())
+    else:
+        got = engines(kind, precision).forward(fobs, h0.cuda(), mt)
+    assert len(got) == len(ref)
+    for g, r in zip(got, ref):
+        if g is None and r is None:                               # (Seq2SeqNet without the progress monitor: no progress_hat)
+            continue
+        e = float((g.cpu() - r).abs().max())
+        print(f"ingest [{kind}, {precision}]: max-abs {e:.2e} (<= {TOL[precision]:.0e})")
+        assert e <= TOL[precision]
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16"])
+def test_golden_features_give_the_reference_outputs(precision):
+    """tests/golden/features_128_L12.npz: the imported reference models on observations that hold only the feature keys."""
+    import os
+    from robo_vln_amd.cma import CMAEngine
+    from robo_vln_amd.policy import HCMEngine
+    from tests import features_cases as fc
+    gold = np.load(os.path.join(os.path.dirname(__file__), "golden", "features_128_L12.npz"))
+    cfg, ccfg = fc.hcm_cfg(), fc.cma_cfg()
+    t = lambda a: torch.as_tensor(np.asarray(a)).cuda()
+    eng = HCMEngine(cfg, *synth.make_weights(cfg, fc.SEED), max_batch=2, precision=precision)
+    cma = CMAEngine(ccfg, synth.make_cma_weights(ccfg, fc.SEED), max_batch=2, precision=precision)
+    try:
+        ids, h0, m = fc.hi_inputs(cfg)
+        got = eng.high_forward({"rgb_features": t(gold["rgb_spatial"]), "depth_features": t(gold["depth"][:1]), "instruction": t(ids)}, h0.cuda(), t(m))
+        pairs = list(zip(("hi logits", "hi hidden"), got, (gold["hi_logits"], gold["hi_hidden"])))
+        h0, m, sub = fc.lo_inputs(cfg)
+        got = eng.low_forward({"rgb_features": t(gold["rgb_flat"]), "depth_features": t(gold["depth"])}, h0.cuda(), t(m), t(sub))
+        pairs += list(zip(("lo vel", "lo stop", "lo hidden"), got, (gold["lo_vel"], gold["lo_stop"], gold["lo_hidden"])))
+        ids, h0, m = fc.cma_inputs(ccfg)
+        got = cma.forward({"rgb_features": t(gold["rgb_spatial"]), "depth_features": t(gold["depth"][:1]), "instruction": t(ids)}, h0.cuda(), t(m))
+        pairs += list(zip(("cma out", "cma stop", "cma hidden"), got, (gold["cma_out"], gold["cma_stop"], gold["cma_hidden"])))
+        for what, g, r in pairs:
+            e = float(np.abs(g.cpu().numpy() - r).max())
+            print(f"golden [{precision}] {what}: max-abs {e:.2e} (<= {TOL[precision]:.0e})")
+            assert e <= TOL[precision]
+    finally:
+        eng.close()
+        cma.close()
+
+
+# ---------------------------------------------------------------- 3. round trip, bit for bit
+def _hcm_calls(eng, rows_step, variant):
+    """name -> f(observations) for every HCM entry point, states and labels fixed"""
+    R = eng.num_recurrent_layers
+    hs, hq = state(eng, rows_step), state(eng, N)
+    ms = torch.tensor([0.0, 1.0, 1.0][:rows_step]).cuda()
+    mq = torch.from_numpy((np.arange(T * N) % 3 != 0).astype(np.float32)).cuda()
+    sub_s = torch.tensor([0, 2, 4][:rows_step]).cuda()
+    sub_q = torch.arange(T * N).cuda() % 5
+    oracle = (torch.arange(T * N) % 5)
+    corrected = torch.rand(T * N, 2, generator=torch.Generator().manual_seed(1)).cuda()
+    stop = (torch.arange(T * N) % 2).float().view(-1, 1).cuda()
+    return R, {
+        "high_forward": (rows_step, lambda o: eng.high_forward(o, hs, ms)),
+        "low_forward": (rows_step, lambda o: eng.low_forward(o, hs, ms, sub_s)),
+        "high_forward_seq": (T * N, lambda o: eng.high_forward_seq(o, hq, mq)),
+        "low_forward_seq": (T * N, lambda o: eng.low_forward_seq(o, hq, mq, sub_q)),
+        "val_step": (T * N, lambda o: eng.val_step(dict(o, vln_oracle_action_sensor=oracle), corrected, stop, hq, hq, mq, return_outputs=True)),
+    }
+
+
+@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+@pytest.mark.parametrize("variant,rows", [("base", 3), ("d192", 1), ("r160", 3)])
+def test_round_trip_is_bit_identical_hcm(variant, rows, precision, engines):
+    eng = engines("hcm", precision, variant)
+    _, calls = _hcm_calls(eng, rows, variant)
+    for name, (n, f) in calls.items():
+        obs = cuda(observations("hcm", n, variant))
+        feats = eng.encode_features(obs)
+        same(f(swap(obs, feats)), f(obs))
+    assert eng.nonfinite_steps() == 0
+
+
+def test_round_trip_val_step_bf16(engines):
+    eng = engines("hcm", "bf16")
+    _, calls = _hcm_calls(eng, 3, "base")
+    obs = cuda(observations("hcm", T * N))
+    same(calls["val_step"][1](swap(obs, eng.encode_features(obs))), calls["val_step"][1](obs))
+
+
+def _act_two_steps(eng, obs_steps, for_act_feats=None):
+    hh = lh = torch.zeros(eng.num_recurrent_layers, obs_steps[0]["instruction"].shape[0], eng.cfg.hidden).cuda()
+    out = []
+    for t, o in enumerate(obs_steps):
+        m = torch.full((o["instruction"].shape[0],), float(t > 0)).cuda()
+        rec, hh, lh = eng.act(o, hh, lh, m)
+        rec, hh, lh = rec.clone(), hh.clone(), lh.clone()
+        out.append((rec, hh, lh))
+    return out
+
+
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("kind,precision", [("hcm", "fp16"), ("hcm", "fp32"), ("hcm", "bf16"), ("hcm_shared", "fp16")])
+def test_round_trip_is_bit_identical_act(kind, precision, graph, engines):
+    """act() runs two models' unequal trunks as one paired network: encode_features(for_act=True) runs those launches.  With shared trunks
+    (kind hcm_shared: the reference's frozen pretrained encoders) the default features serve act() as well."""
+    eng = engines(kind, precision, "base", graph)
+    for rows in (1, 3):
+        steps = [cuda(observations("hcm", rows, step=t)) for t in range(2)]
+        feats = [eng.encode_features(o, for_act=kind == "hcm") for o in steps]
+        fsteps = [swap(o, f) for o, f in zip(steps, feats)]
+        ref = _act_two_steps(eng, steps)
+        if graph:
+            # the same tensors again: the second pass over fixed addresses is captured, the third replayed
+            for _ in range(2):
+                got = _act_two_steps(eng, fsteps)
+                same(got, ref)
+            assert eng.query(_lib.HCM_GRAPH_LAUNCHES) > 0
+        same(_act_two_steps(eng, fsteps), ref)
+
+
+@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+@pytest.mark.parametrize("kind", ["cma", "s2s"])
+def test_round_trip_is_bit_identical_flat_engines(kind, precision, engines):
+    eng = engines(kind, precision)
+    hq = state(eng, N)
+    mq = torch.from_numpy((np.arange(T * N) % 3 != 0).astype(np.float32)).cuda()
+    corrected = torch.rand(T * N, 2, generator=torch.Generator().manual_seed(1)).cuda()
+    stop = (torch.arange(T * N) % 2).float().view(-1, 1).cuda()
+    for rows in (1, 3):
+        obs = cuda(observations(kind, rows))
+        hs, ms = state(eng, rows), torch.tensor([0.0, 1.0, 1.0][:rows]).cuda()
+        same(eng.forward(swap(obs, eng.encode_features(obs)), hs, ms), eng.forward(obs, hs, ms))
+    obs = cuda(observations(kind, T * N))
+    fobs = swap(obs, eng.encode_features(obs))
+    same(eng.forward_seq(fobs, hq, mq, T, N), eng.forward_seq(obs, hq, mq, T, N))
+    same(eng.val_step(fobs, corrected, stop, hq, mq, return_outputs=True), eng.val_step(obs, corrected, stop, hq, mq, return_outputs=True))
+    assert eng.nonfinite_steps() == 0
+
+
+# ---------------------------------------------------------------- 4. mixed, 5. precedence
+@pytest.mark.parametrize("kind", ["hcm", "cma", "s2s"])
+def test_mixed_and_precedence(kind, engines):
+    eng = engines(kind, "fp16")
+    obs = cuda(observations(kind, 3))
+    feats = eng.encode_features(obs)
+    hs, ms = state(eng, 3), torch.tensor([0.0, 1.0, 1.0]).cuda()
+    if kind == "hcm":
+        hq, mq = state(eng, N), torch.ones(T * N).cuda()
+        f = lambda o: eng.high_forward(o, hs, ms) + eng.low_forward(o, hs, ms, torch.tensor([0, 2, 4]).cuda())
+    else:
+        f = lambda o: eng.forward(o, hs, ms)
+    ref = f(obs)
+    same(f(swap(obs, feats, ("rgb",))), ref)                    # RGB as features, depth as frames
+    same(f(swap(obs, feats, ("depth",))), ref)                  # the reverse
+    nan = {k: (torch.full_like(v.float(), float("nan")) if k in ("rgb", "depth") else v) for k, v in obs.items()}
+    same(f(dict(nan, **feats)), ref)                            # a feature wins over the frame beside it, which is not read
+    assert eng.nonfinite_steps() == 0
+
+
+# ---------------------------------------------------------------- 6. a range-folded RGB trunk
+def _big_rgb_trunk(hi, lo, K=2.0 ** 15):
+    """Every activation of the BatchNorm-folded RGB trunks times K (conv + folded BN + ReLU, the pools and the residual sums are positively
+    homogeneous: the stem's BN gain and every BN's shift and running mean take the factor), the consumers' trunk-feature columns divided by it:
+    the same network function, with a trunk far outside fp16 -- what ImageNet-like BN statistics do to it (tests/test_trained_like_weights_gpu.py),
+    made certain."""
+    out = []
+    for sd in (hi, lo):
+        sd = {k: np.array(v, copy=True) for k, v in sd.items()}
+        pre = "rgb_encoder.cnn."
+        for k in sd:
+            if not k.startswith(pre):
+                continue
+            if k == pre + "bn1.weight" or (k.endswith((".bias", ".running_mean")) and k != pre + "bn1.running_mean" and sd[k].ndim == 1
+                                           and not k.startswith(pre + "fc.")):
+                sd[k] = (sd[k] * np.float32(K)).astype(np.float32)
+        for k in ("rgb_kv.weight", "rgb_linear.2.weight", "rgb_encoder.fc.weight"):
+            if k in sd:
+                sd[k][:, :2048] = sd[k][:, :2048] / np.float32(K)
+        out.append(sd)
+    return out
+
+
+def test_range_folded_rgb_trunk_exports_unscaled_features_and_round_trips():
+    from robo_vln_amd.policy import HCMEngine
+    cfg = hcm_cfg()
+    hi, lo = _big_rgb_trunk(*weights("hcm"))
+    eng = HCMEngine(cfg, hi, lo, max_batch=3, precision="fp16", guard_every=0)
+    try:
+        assert "rgb" in eng.range_fold, eng.calibration_report()
+        obs_np = observations("hcm", 3)
+        obs = cuda(obs_np)
+        feats = eng.encode_features(obs)
+        for slot, sd in enumerate((hi, lo)):
+            r, _ = features_ref.trunk_features(cfg, sd, obs_np, spatial=slot == 0)
+            e = rel_err(feats["rgb_features"][slot], r)
+            print(f"range-folded trunk, model {slot}: exported rgb_features vs the oracle's unscaled ones {e:.2e} (<= {TOL['fp16']:.0e}), max |ref| {float(r.abs().max()):.3e}")
+            assert e <= TOL["fp16"]
+        steps = [cuda(observations("hcm", 3, step=t)) for t in range(2)]
+        fsteps = [swap(o, eng.encode_features(o, for_act=True)) for o in steps]
+        same(_act_two_steps(eng, fsteps), _act_two_steps(eng, steps))
+        assert eng.nonfinite_steps() == 0
+    finally:
+        eng.close()
+
+
+# ---------------------------------------------------------------- 7. refusals
+def test_refusals_and_the_engine_stays_usable(engines):
+    from robo_vln_amd.policy import HCMEngine
+    eng = engines("hcm", "fp16")
+    obs = cuda(observations("hcm", 3))
+    feats = eng.encode_features(obs)
+    hs, ms = state(eng, 3), torch.tensor([0.0, 1.0, 1.0]).cuda()
+    ref = eng.high_forward(obs, hs, ms)
+    with pytest.raises(ValueError, match=r"\(rows,2048,4,4\)"):                     # a wrong feature shape
+        eng.high_forward(dict(swap(obs, feats), rgb_features=feats["rgb_features"][1]), hs, ms)
+    with pytest.raises(ValueError, match="pair"):                                   # one RGB tensor for two models
+        eng.act(dict(swap(obs, feats), rgb_features=feats["rgb_features"][0]), hs, hs, ms)
+    with pytest.raises(ValueError, match="missing"):                                # a frame some trunk still needs
+        eng.high_forward({k: v for k, v in swap(obs, feats, ("rgb",)).items() if k != "depth"}, hs, ms)
+    with pytest.raises(ValueError, match="resnet_encoders.py:83-86"):               # calibration needs the trunks
+        eng.calibrate(swap(obs, feats))
+    pinned = dict(swap(obs, feats))
+    with pytest.raises(ValueError, match="host_frames"):
+        eng.act(pinned, hs, hs, ms, host_frames=True)
+    # the raw C ABI: HCM_ACT_HOST_FRAMES with HCM_FEATURES, and a NULL frame with a NULL feature
+    st = _lib.HcmFeaturesStruct()
+    st.rgb_feat[0], st.depth_feat[0] = feats["rgb_features"][0].data_ptr(), feats["depth_features"][0].data_ptr()
+    st.rgb_feat[1] = feats["rgb_features"][1].data_ptr()                            # depth_feat[1] and depth stay NULL
+    ids = obs["instruction"].long().contiguous()
+    rec, h2 = torch.empty(3, 7).cuda(), torch.empty_like(hs)
+    args = (eng._h, C.addressof(st), _lib.HCM_FEATURES, None, ids.data_ptr(), _lib.HCM_I64, None, 3, ids.shape[1], hs.data_ptr(), hs.data_ptr(),
+            ms.data_ptr(), rec.data_ptr(), h2.data_ptr(), h2.data_ptr())
+    assert eng._lib.hcm_act_ex(*args, 0, None) == -1 and "hcm_features.depth is NULL" in _lib.last_error(eng._h)
+    assert eng._lib.hcm_act_ex(*args, _lib.HCM_ACT_HOST_FRAMES, None) == -1 and "HCM_ACT_HOST_FRAMES" in _lib.last_error(eng._h)
+    same(eng.high_forward(obs, hs, ms), ref)
+    same(eng.high_forward(swap(obs, feats), hs, ms), ref)
+    # a SimpleCNN encoder and an ablated modality take no features: refused by the library with the reference line
+    cfg = HCMConfig(rgb_hw=128, depth_hw=128, instr_len=12, vla_layers=2, bert_layers=2, rgb_encoder="SimpleRGBCNN", depth_encoder="SimpleDepthCNN",
+                    rnn_type="GRU").validate()
+    lo_only = HCMEngine(cfg, None, synth.materialize(synth.low_level_spec(cfg), "lo", SEED), max_batch=3, precision="fp16")
+    try:
+        bad = {"rgb_features": torch.zeros(3, 2048, 1, 1).cuda(), "depth": obs["depth"]}
+        with pytest.raises(ValueError, match=r"simple_cnns.py:144-147"):
+            lo_only.low_forward(bad, hs, ms, torch.tensor([0, 2, 4]).cuda())
+        with pytest.raises(ValueError, match=r"simple_cnns.py:122-125"):
+            lo_only.low_forward({"depth_features": torch.zeros(3, 128, 4, 4).cuda(), "rgb": obs["rgb"]}, hs, ms, torch.tensor([0, 2, 4]).cuda())
+        lo_only.low_forward(obs, hs, ms, torch.tensor([0, 2, 4]).cuda())
+    finally:
+        lo_only.close()
+    cfg = HCMConfig(instr_len=12, vla_layers=2, bert_layers=2, ablate_depth=True, rnn_type="GRU", **VARIANTS["base"]).validate()
+    abl = HCMEngine(cfg, *synth.make_weights(cfg, SEED), max_batch=3, precision="fp16")
+    try:
+        h = torch.zeros(abl.num_recurrent_layers, 3, cfg.hidden).cuda()
+        with pytest.raises(ValueError, match=r"seq2seq_highlevel_cma.py:185-186"):
+            abl.high_forward(dict(obs, depth_features=feats["depth_features"][0]), h, ms)
+        abl.high_forward(obs, h, ms)
+    finally:
+        abl.close()
