@@ -660,6 +660,25 @@ int hcm_op_flat_val_loss(const float* out, const float* stop, const float* progr
  * hidden must be 512 (HCM_ERR_ARG otherwise); any T, N >= 1.  Synchronises the stream (it owns temporary buffers). */
 int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,
                       int T, int N, int hidden, int rnn_type, void* stream);
+/* The training form of hcm_op_state_scan: the same arguments and, bit for bit, the same seq_out / h_out, plus what the reverse scan needs.
+ *   gates (T*N, 4*hidden): the post-activation gates of every row -- LSTM i,f,g,o; GRU r,z,n and hn = W_hn h' + b_hn (h' = h_{t-1} * mask), the
+ *   value r multiplies inside tanh.  c_seq (T*N, hidden): c_t of every row, LSTM only (must be NULL for GRU).
+ *   work: 4*hidden*hidden floats owned by the caller; w_hh (torch layout, on the device) is packed into it by a device kernel on `stream`.
+ * Allocates nothing, copies nothing to the host and does not synchronise the stream: weights change after every optimizer step. */
+int hcm_op_state_scan_train(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,
+                            float* gates, float* c_seq, float* work, int T, int N, int hidden, int rnn_type, void* stream);
+/* Back-propagation through time for hcm_op_state_scan_train (csrc/state_scan_bwd.hip), one launch per step from T-1 down to 0.
+ *   in:  d_seq (T*N, hidden) the cotangent of every h_t; gates, c_seq (LSTM; NULL for GRU), seq_out, h_in, masks, w_hh as the forward had them
+ *   out: d_pre (T*N, G*hidden) the gradient with respect to `pre`; d_gh (T*N, 3*hidden), GRU only (NULL for LSTM): the h-side gate gradients
+ *        [da_r, da_z, da_n * r] (for LSTM they are d_pre); d_h_in (R, N, hidden), the carry behind step 0 -- a buffer of its own
+ *   work: 4*hidden*hidden + 4*N*hidden floats owned by the caller: w_hh in the reverse scan's order (packed on `stream`) and the two ping-pong
+ *        pairs of the (h, c) carry that successive launches alternate between.  No output may overlap it (HCM_ERR_ARG).
+ * No gradient enters through the final state (the reference detaches it, state_encoder.py:131).  With x the input rows and
+ * h' = cat(h_in[0], seq_out[:-N]) * masks: dx = d_pre W_ih, dW_ih = d_pre^T x, db_ih = sum d_pre, dW_hh = d_gh^T h', db_hh = sum d_gh -- dense
+ * GEMMs left to the caller.  Allocates nothing and does not synchronise the stream; fixed summation order, bitwise reproducible. */
+int hcm_op_state_scan_bwd(const float* d_seq, const float* gates, const float* c_seq, const float* seq_out, const float* h_in, const float* masks,
+                          const float* w_hh, float* work, float* d_pre, float* d_gh, float* d_h_in, int T, int N, int hidden, int rnn_type,
+                          void* stream);
 
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */

@@ -1,6 +1,7 @@
 // C ABI of libhcm (include/hcm.h).
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -1726,6 +1727,32 @@ int hcm_op_state_scan(const float* pre, const float* w_hh, const float* b_hh, co
     const hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(ws);
     return op_rc(e != hipSuccess ? e : e2);
+}
+
+int hcm_op_state_scan_train(const float* pre, const float* w_hh, const float* b_hh, const float* h_in, const float* masks, float* seq_out, float* h_out,
+                            float* gates, float* c_seq, float* work, int T, int N, int hidden, int rnn_type, void* stream) {
+    if (!pre || !w_hh || !h_in || !masks || !seq_out || !h_out || !gates || !work || T < 1 || N < 1 || !state_scan_ok(hidden)) return HCM_ERR_ARG;
+    if (rnn_type != HCM_LSTM && rnn_type != HCM_GRU) return HCM_ERR_ARG;
+    if ((c_seq == nullptr) != (rnn_type == HCM_GRU)) return HCM_ERR_ARG;
+    return op_rc(launch_state_scan_train(pre, w_hh, b_hh, h_in, masks, seq_out, h_out, gates, c_seq, work, T, N, hidden, rnn_type == HCM_GRU ? 1 : 0,
+                                         (hipStream_t)stream));
+}
+
+int hcm_op_state_scan_bwd(const float* d_seq, const float* gates, const float* c_seq, const float* seq_out, const float* h_in, const float* masks,
+                          const float* w_hh, float* work, float* d_pre, float* d_gh, float* d_h_in, int T, int N, int hidden, int rnn_type,
+                          void* stream) {
+    if (!d_seq || !gates || !seq_out || !h_in || !masks || !w_hh || !work || !d_pre || !d_h_in || T < 1 || N < 1 || !state_scan_ok(hidden))
+        return HCM_ERR_ARG;
+    if (rnn_type != HCM_LSTM && rnn_type != HCM_GRU) return HCM_ERR_ARG;
+    const bool gru = rnn_type == HCM_GRU;
+    if ((c_seq == nullptr) != gru || (d_gh == nullptr) == gru) return HCM_ERR_ARG;
+    // every workgroup of a step reads the packed weights and both carries in `work` while the outputs are stored: no output may lie inside it
+    const size_t NH = (size_t)N * hidden, rows = (size_t)T * N * (gru ? 3 : 4) * hidden;
+    const uintptr_t w0 = (uintptr_t)work, w1 = w0 + ((size_t)4 * hidden * hidden + 4 * NH) * sizeof(float);
+    const auto in_work = [&](const float* p, size_t n) { return p && (uintptr_t)p < w1 && (uintptr_t)p + n * sizeof(float) > w0; };
+    if (in_work(d_h_in, (gru ? 1 : 2) * NH) || in_work(d_pre, rows) || in_work(d_gh, rows)) return HCM_ERR_ARG;
+    return op_rc(launch_state_scan_bwd(d_seq, gates, c_seq, seq_out, h_in, masks, w_hh, work, d_pre, d_gh, d_h_in, T, N, hidden, gru ? 1 : 0,
+                                       (hipStream_t)stream));
 }
 
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {

@@ -286,6 +286,15 @@ bool state_scan_ok(int H);
 void state_scan_pack(const float* w_hh, float* out, int H, int G);       // host-side re-layout of torch's (G*H, H)
 hipError_t launch_state_scan(const float* pre, const float* ws, const float* bhh, const float* h_in, const float* mask, float* seq, float* h_out,
                              unsigned* flags, unsigned* bad, int T, int N, int H, int gru, hipStream_t s);
+// The training forward: w_hh as torch stores it, packed into `work` (4*H*H floats) by a device kernel on the stream (state_scan_pack on the device);
+// gates [T*N][4H] (LSTM i,f,g,o / GRU r,z,n,hn) and cseq [T*N][H] (LSTM; null for GRU) are what the reverse scan reads.  seq / h_out carry the
+// bits of launch_state_scan.  No allocation, no host copy, no synchronisation.
+hipError_t launch_state_scan_train(const float* pre, const float* w_hh, const float* bhh, const float* h_in, const float* mask, float* seq, float* h_out,
+                                   float* gates, float* cseq, float* work, int T, int N, int H, int gru, hipStream_t s);
+// Reverse scan (state_scan_bwd.hip): d_seq [T*N][H] -> d_pre [T*N][G*H], d_gh [T*N][3H] (GRU; null for LSTM), d_h_in (R,N,H); one launch per step.
+//   work: 4*H*H floats for W_hh in reverse-scan order (packed on the stream) + 4*N*H floats for the two ping-pong carry pairs
+hipError_t launch_state_scan_bwd(const float* d_seq, const float* gates, const float* cseq, const float* seq, const float* h_in, const float* mask,
+                                 const float* w_hh, float* work, float* d_pre, float* d_gh, float* d_h_in, int T, int N, int H, int gru, hipStream_t s);
 // split-K: fixed-order sum of S f32 partial results [S][M][N] + bias + activation (see Fwd::linear)
 // How many K slices a skinny long-K linear layer is cut into (forward.cpp Fwd::linear and hcm_op_linear use the same rule, so an operator call
 // reproduces the model path bit for bit): powers of two while the (64 x 32-tile) grid stays under 256 workgroups and a slice keeps >= 256 columns

@@ -25,10 +25,14 @@ namespace hcm {
 
 constexpr int kScanNB = 8;
 
-template <int H, bool GRU>
+// SAVE (the training forward, hcm_op_state_scan_train): the cell epilogue also stores what the reverse scan (state_scan_bwd.hip) reads -- the
+// post-activation gates of the row (LSTM i,f,g,o; GRU r,z,n and hn = W_hn h' + b_hn, the value r multiplies) into gates_t [N][4H] and, LSTM, c_t
+// into cseq_t [N][H].  Extra stores of values the epilogue has anyway: the arithmetic, and so every bit of h_t / c_t, is that of SAVE = false.
+template <int H, bool GRU, bool SAVE>
 __global__ __launch_bounds__(256) void state_scan_step_kernel(const float* __restrict__ pre, const float4* __restrict__ ws, const float* __restrict__ bhh,
                                                                const float* h_prev, const float* c_prev, const float* __restrict__ mask, float* seq_t,
-                                                               float* h_last, float* c_out, unsigned* __restrict__ flags_t, int N) {
+                                                               float* h_last, float* c_out, unsigned* __restrict__ flags_t, float* __restrict__ gates_t,
+                                                               float* __restrict__ cseq_t, int N) {
     constexpr int NG = GRU ? 3 : 4, U = kScanUnits, KS = H / 16, NB = kScanNB;
     static_assert(H % 64 == 0 && U == 16, "thread mapping: 16 units x 16 k lanes");
     __shared__ float hs[NB * H];
@@ -101,6 +105,10 @@ __global__ __launch_bounds__(256) void state_scan_step_kernel(const float* __res
                     const float z = sigmoidf_(a1 + rs[1]);
                     const float nn = tanhf(a2 + r * rs[2]);
                     h2 = (1.f - z) * nn + z * hs[s_ * H + u];
+                    if (SAVE) {
+                        float* gp = gates_t + (size_t)n * 4 * H + u;
+                        gp[0] = r, gp[H] = z, gp[2 * H] = nn, gp[3 * H] = rs[2];
+                    }
                 } else {
                     const float g0 = p[0] + rs[0], g1 = p[H] + rs[1], g2 = p[2 * H] + rs[2], g3 = p[(NG - 1) * H] + rs[NG - 1];
                     bad = !isfinite(g0 + g1 + g2 + g3);
@@ -109,6 +117,11 @@ __global__ __launch_bounds__(256) void state_scan_step_kernel(const float* __res
                     const float c2 = gf * c + gi * gg;
                     h2 = go * tanhf(c2);
                     c_out[(size_t)n * H + u] = c2;
+                    if (SAVE) {
+                        float* gp = gates_t + (size_t)n * 4 * H + u;
+                        gp[0] = gi, gp[H] = gf, gp[2 * H] = gg, gp[3 * H] = go;
+                        cseq_t[(size_t)n * H + u] = c2;
+                    }
                 }
                 seq_t[(size_t)n * H + u] = h2;
                 if (h_last) h_last[(size_t)n * H + u] = h2;
@@ -148,9 +161,9 @@ void state_scan_pack(const float* w_hh, float* out, int H, int G) {
     }
 }
 
-template <int H>
+template <int H, bool SAVE>
 static hipError_t scan_steps(const float* pre, const float* ws, const float* bhh, const float* h_in, const float* mask, float* seq, float* h_out,
-                             unsigned* flags, int T, int N, int gru, hipStream_t s) {
+                             unsigned* flags, float* gates, float* cseq, int T, int N, int gru, hipStream_t s) {
     const int NG = gru ? 3 : 4, nwg = H / kScanUnits;
     const size_t NH = (size_t)N * H;
     const bool alias1 = T == 1 && h_out == h_in;
@@ -160,12 +173,13 @@ static hipError_t scan_steps(const float* pre, const float* ws, const float* bhh
         float* hl = t == T - 1 && !alias1 ? h_out : nullptr;
         const float* pt = pre + (size_t)t * N * NG * H;
         unsigned* ft = flags ? flags + (size_t)t * N * nwg : nullptr;
+        float* gt = SAVE ? gates + (size_t)t * NH * 4 : nullptr;
         if (gru)
-            hipLaunchKernelGGL((state_scan_step_kernel<H, true>), dim3(nwg), dim3(256), 0, s, pt, (const float4*)ws, bhh, hp, nullptr, mask + (size_t)t * N,
-                               seq + (size_t)t * NH, hl, nullptr, ft, N);
+            hipLaunchKernelGGL((state_scan_step_kernel<H, true, SAVE>), dim3(nwg), dim3(256), 0, s, pt, (const float4*)ws, bhh, hp, nullptr,
+                               mask + (size_t)t * N, seq + (size_t)t * NH, hl, nullptr, ft, gt, nullptr, N);
         else
-            hipLaunchKernelGGL((state_scan_step_kernel<H, false>), dim3(nwg), dim3(256), 0, s, pt, (const float4*)ws, bhh, hp, cp, mask + (size_t)t * N,
-                               seq + (size_t)t * NH, hl, h_out + NH, ft, N);
+            hipLaunchKernelGGL((state_scan_step_kernel<H, false, SAVE>), dim3(nwg), dim3(256), 0, s, pt, (const float4*)ws, bhh, hp, cp,
+                               mask + (size_t)t * N, seq + (size_t)t * NH, hl, h_out + NH, ft, gt, SAVE ? cseq + (size_t)t * NH : nullptr, N);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -180,13 +194,46 @@ hipError_t launch_state_scan(const float* pre, const float* ws, const float* bhh
     // sequence buffer's previous row block; at step 0 it is h_in, and only a one-step scan also stores its h into h_out there -- with h_out
     // aliasing h_in that store goes through the sequence buffer instead (copied behind the launch).
     if (!bad) flags = nullptr;
-    hipError_t e = scan_steps<512>(pre, ws, bhh, h_in, mask, seq, h_out, flags, T, N, gru, s);
+    hipError_t e = scan_steps<512, false>(pre, ws, bhh, h_in, mask, seq, h_out, flags, nullptr, nullptr, T, N, gru, s);
     if (e != hipSuccess) return e;
     if (bad) {
         hipLaunchKernelGGL(state_scan_guard_kernel, dim3(1), dim3(256), 0, s, flags, T * N, H / kScanUnits, bad);
         e = hipGetLastError();
     }
     return e;
+}
+
+// state_scan_pack on the device: a workgroup moves the (4 gates x 16 units) x 64 k tile of slice blockIdx.y through LDS, so that both the reads of
+// torch's (G*H, H) rows (64 consecutive k) and the stores in scan order (4096 consecutive floats) are contiguous.  GRU: the 4th gate slot is 0.
+__global__ __launch_bounds__(256) void state_scan_pack_kernel(const float* __restrict__ w_hh, float* __restrict__ ws, int H, int G) {
+    __shared__ float tile[64][65];
+    constexpr int U = kScanUnits;
+    const int tid = threadIdx.x, k0 = blockIdx.x * 64, b = blockIdx.y;
+    for (int e = tid; e < 64 * 64; e += 256) {
+        const int row = e >> 6, kk = e & 63, g = row >> 4, uu = row & 15;
+        tile[row][kk] = g < G ? w_hh[((size_t)g * H + b * U + uu) * H + k0 + kk] : 0.f;
+    }
+    __syncthreads();
+    float* out = ws + ((size_t)b * H + k0) * U * 4;
+    for (int o = tid; o < 64 * 64; o += 256) {
+        const int g = o & 3, uu = (o >> 2) & 15, kk = o >> 6;
+        out[o] = tile[g * 16 + uu][kk];
+    }
+}
+
+static hipError_t launch_state_scan_pack(const float* w_hh, float* ws, int H, int G, hipStream_t s) {
+    if (!state_scan_ok(H) || !w_hh || !ws || (G != 3 && G != 4)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(state_scan_pack_kernel, dim3(H / 64, H / kScanUnits), dim3(256), 0, s, w_hh, ws, H, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_state_scan_train(const float* pre, const float* w_hh, const float* bhh, const float* h_in, const float* mask, float* seq, float* h_out,
+                                   float* gates, float* cseq, float* work, int T, int N, int H, int gru, hipStream_t s) {
+    if (!state_scan_ok(H) || T < 1 || N < 1 || !pre || !w_hh || !h_in || !mask || !seq || !h_out || !gates || !work || (cseq == nullptr) != (gru != 0))
+        return hipErrorInvalidValue;
+    const hipError_t e = launch_state_scan_pack(w_hh, work, H, gru ? 3 : 4, s);
+    if (e != hipSuccess) return e;
+    return scan_steps<512, true>(pre, work, bhh, h_in, mask, seq, h_out, nullptr, gates, cseq, T, N, gru, s);
 }
 
 }  // namespace hcm
