@@ -680,6 +680,39 @@ int hcm_op_state_scan_bwd(const float* d_seq, const float* gates, const float* c
                           const float* w_hh, float* work, float* d_pre, float* d_gh, float* d_h_in, int T, int N, int hidden, int rnn_type,
                           void* stream);
 
+/* The cross-modal layer (InterModuleAttnLayer, transformer.py:209-221) after its three projections, in float32 and with what a backward pass needs
+ * (csrc/vla_train.hip).  d_model 256, 4 heads of 64; B, L >= 1 with L <= 4194240 and rows = B*L <= 33554431; Lk 1..64; d_ff 256, 512, 768 or 1024; anything else HCM_ERR_ARG.
+ *   a = softmax(q k^T / 8) v;  x1 = LN1(I + keep1 s (a Wo^T + bo));  h = keep2 s relu(x1 W1^T + b1);  out = LN2(x1 + keep3 s (h W2^T + b2))
+ *   q, I (rows, 256); kv (B, Lk, 512) = fc_k | fc_v of the keys; wo (256, 256), w1 (d_ff, 256), w2 (256, d_ff) and the biases / LayerNorm
+ *   parameters as torch stores them, on the device; LayerNorm eps 1e-5.
+ *   keep1 (rows, 256), keep2 (rows, d_ff), keep3 (rows, 256): uint8 keep masks of the three dropouts, s = 1 / (1 - p), 0 <= p < 1.  A NULL mask
+ *   means no dropout at that place (keep everything, no scaling): all three NULL and p = 0 is the eval-mode layer.
+ * Written by the forward, read by the backward (all float32, owned by the caller):
+ *   a (rows, 256), x1 (rows, 256), h (rows, d_ff; post-dropout): the left operands of the three weight gradients, which the caller reduces;
+ *   x1hat, x2hat (rows, 256): the two LayerNorms' normalised rows (y - mean) * rstd; rstd (rows, 2): their reciprocal standard deviations.
+ *   With the normalised rows saved the means are not needed.  The attention probabilities are not saved: the backward recomputes them.
+ * work: hcm_op_vla_train_work_floats(B, L, Lk, d_ff) floats (0 for unsupported sizes) owned by the caller, serving either op: the three weights
+ *   in the kernels' operand order (packed on `stream` in every call: nothing is cached, weights change at every optimizer step), the backward's
+ *   (rows, 256) attention-output gradient and its LayerNorm partial sums.  No output may overlap it (HCM_ERR_ARG).  Row tensors, weights and
+ *   work must be 16-byte aligned, keep masks 4-byte aligned.
+ * Both ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible. */
+int64_t hcm_op_vla_train_work_floats(int B, int L, int Lk, int d_ff);
+int hcm_op_vla_layer_train(const float* q, const float* I, const float* kv, const float* wo, const float* bo, const float* w1, const float* b1,
+                           const float* w2, const float* b2, const float* g1, const float* be1, const float* g2, const float* be2,
+                           const uint8_t* keep1, const uint8_t* keep2, const uint8_t* keep3, float p, float* out, float* a, float* x1, float* x1hat,
+                           float* h, float* x2hat, float* rstd, float* work, int B, int L, int Lk, int d_ff, void* stream);
+/* Backward of hcm_op_vla_layer_train from d_out (rows, 256) and what the forward saved; q, kv, the weights, masks and p as the forward had them.
+ *   out: d_q, d_I (rows, 256); d_kv (B, Lk, 512), summed over a sample's L rows in a fixed order (one workgroup per (sample, head));
+ *        d_u (rows, 256), d_hpre (rows, d_ff), d_z (rows, 256): the row-local gradients of u = a Wo^T + bo, of fc1's pre-activation and of
+ *        z = h W2^T + b2, so that dWo = d_u^T a, dW1 = d_hpre^T x1, dW2 = d_z^T h, d_bo / d_b1 / d_b2 = their column sums -- dense reductions
+ *        over all rows, left to the caller; d_ln (4, 256) = d_g1, d_be1, d_g2, d_be2, reduced here (per-workgroup partials in `work`, summed
+ *        in workgroup order) because the normalised rows never leave the op otherwise.
+ * Four launches on `stream`, no host synchronisation. */
+int hcm_op_vla_layer_bwd(const float* d_out, const float* q, const float* kv, const float* wo, const float* w1, const float* w2, const float* g1,
+                         const float* g2, const uint8_t* keep1, const uint8_t* keep2, const uint8_t* keep3, float p, const float* x1hat, const float* h,
+                         const float* x2hat, const float* rstd, float* work, float* d_q, float* d_I, float* d_kv, float* d_u, float* d_hpre, float* d_z,
+                         float* d_ln, int B, int L, int Lk, int d_ff, void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

@@ -1755,6 +1755,64 @@ int hcm_op_state_scan_bwd(const float* d_seq, const float* gates, const float* c
                                        (hipStream_t)stream));
 }
 
+int64_t hcm_op_vla_train_work_floats(int B, int L, int Lk, int d_ff) {
+    return vla_train_ok(B, L, Lk, d_ff) ? (int64_t)vla_train_work_floats(B, L, Lk, d_ff) : 0;
+}
+
+// the kernels move 16 bytes per lane (4 for the keep masks); no output may lie inside the work buffer, which the launches read while they store
+static bool vla_train_aligned(std::initializer_list<const void*> f32, std::initializer_list<const void*> u8) {
+    for (const void* p : f32) if ((uintptr_t)p % 16) return false;
+    for (const void* p : u8) if ((uintptr_t)p % 4) return false;
+    return true;
+}
+static bool vla_train_in_work(const float* work, size_t work_floats, std::initializer_list<std::pair<const void*, size_t>> outs) {
+    const uintptr_t w0 = (uintptr_t)work, w1 = w0 + work_floats * sizeof(float);
+    for (const auto& o : outs)
+        if (o.first && (uintptr_t)o.first < w1 && (uintptr_t)o.first + o.second * sizeof(float) > w0) return true;
+    return false;
+}
+
+int hcm_op_vla_layer_train(const float* q, const float* I, const float* kv, const float* wo, const float* bo, const float* w1, const float* b1,
+                           const float* w2, const float* b2, const float* g1, const float* be1, const float* g2, const float* be2,
+                           const uint8_t* keep1, const uint8_t* keep2, const uint8_t* keep3, float p, float* out, float* a, float* x1, float* x1hat,
+                           float* h, float* x2hat, float* rstd, float* work, int B, int L, int Lk, int d_ff, void* stream) {
+    if (!q || !I || !kv || !wo || !bo || !w1 || !b1 || !w2 || !b2 || !g1 || !be1 || !g2 || !be2 || !out || !a || !x1 || !x1hat || !h || !x2hat || !rstd ||
+        !work || !(p >= 0.f && p < 1.f) || !vla_train_ok(B, L, Lk, d_ff))
+        return HCM_ERR_ARG;
+    if (!vla_train_aligned({I, wo, w1, w2, g1, be1, g2, be2, out, a, x1, x1hat, x2hat, work}, {keep1, keep2, keep3})) return HCM_ERR_ARG;
+    const size_t rows = (size_t)B * L;
+    if (vla_train_in_work(work, vla_train_work_floats(B, L, Lk, d_ff),
+                          {{out, rows * 256}, {a, rows * 256}, {x1, rows * 256}, {x1hat, rows * 256}, {h, rows * d_ff}, {x2hat, rows * 256}, {rstd, rows * 2}}))
+        return HCM_ERR_ARG;
+    VlaTrainArgs t;
+    t.q = q; t.I = I; t.kv = kv; t.wo = wo; t.bo = bo; t.w1 = w1; t.b1 = b1; t.w2 = w2; t.b2 = b2; t.g1 = g1; t.be1 = be1; t.g2 = g2; t.be2 = be2;
+    t.keep1 = keep1; t.keep2 = keep2; t.keep3 = keep3; t.p = p;
+    t.out = out; t.a = a; t.x1 = x1; t.x1hat = x1hat; t.h = h; t.x2hat = x2hat; t.rstd = rstd; t.work = work;
+    t.B = B; t.L = L; t.Lk = Lk; t.d_ff = d_ff;
+    return op_rc(launch_vla_train_fwd(t, (hipStream_t)stream));
+}
+
+int hcm_op_vla_layer_bwd(const float* d_out, const float* q, const float* kv, const float* wo, const float* w1, const float* w2, const float* g1,
+                         const float* g2, const uint8_t* keep1, const uint8_t* keep2, const uint8_t* keep3, float p, const float* x1hat, const float* h,
+                         const float* x2hat, const float* rstd, float* work, float* d_q, float* d_I, float* d_kv, float* d_u, float* d_hpre, float* d_z,
+                         float* d_ln, int B, int L, int Lk, int d_ff, void* stream) {
+    if (!d_out || !q || !kv || !wo || !w1 || !w2 || !g1 || !g2 || !x1hat || !h || !x2hat || !rstd || !work || !d_q || !d_I || !d_kv || !d_u || !d_hpre ||
+        !d_z || !d_ln || !(p >= 0.f && p < 1.f) || !vla_train_ok(B, L, Lk, d_ff))
+        return HCM_ERR_ARG;
+    if (!vla_train_aligned({d_out, wo, w1, w2, g1, g2, x1hat, x2hat, work, d_I, d_u, d_z}, {keep1, keep2, keep3})) return HCM_ERR_ARG;
+    const size_t rows = (size_t)B * L;
+    if (vla_train_in_work(work, vla_train_work_floats(B, L, Lk, d_ff),
+                          {{d_q, rows * 256}, {d_I, rows * 256}, {d_kv, (size_t)B * Lk * 512}, {d_u, rows * 256}, {d_hpre, rows * d_ff}, {d_z, rows * 256}, {d_ln, 1024}}))
+        return HCM_ERR_ARG;
+    VlaTrainArgs t;
+    t.d_out = d_out; t.q = q; t.kv = kv; t.wo = wo; t.w1 = w1; t.w2 = w2; t.g1 = g1; t.g2 = g2;
+    t.keep1 = keep1; t.keep2 = keep2; t.keep3 = keep3; t.p = p;
+    t.x1hat = const_cast<float*>(x1hat); t.h = const_cast<float*>(h); t.x2hat = const_cast<float*>(x2hat); t.rstd = const_cast<float*>(rstd); t.work = work;
+    t.d_q = d_q; t.d_I = d_I; t.d_kv = d_kv; t.d_u = d_u; t.d_hpre = d_hpre; t.d_z = d_z; t.d_ln = d_ln;
+    t.B = B; t.L = L; t.Lk = Lk; t.d_ff = d_ff;
+    return op_rc(launch_vla_train_bwd(t, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

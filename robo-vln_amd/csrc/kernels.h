@@ -295,6 +295,25 @@ hipError_t launch_state_scan_train(const float* pre, const float* w_hh, const fl
 //   work: 4*H*H floats for W_hh in reverse-scan order (packed on the stream) + 4*N*H floats for the two ping-pong carry pairs
 hipError_t launch_state_scan_bwd(const float* d_seq, const float* gates, const float* cseq, const float* seq, const float* h_in, const float* mask,
                                  const float* w_hh, float* work, float* d_pre, float* d_gh, float* d_h_in, int T, int N, int H, int gru, hipStream_t s);
+// The cross-modal layer in float32 with a backward pass (vla_train.hip): d_model 256, 4 heads of 64, Lk <= 64, d_ff a multiple of 256 up to 1024,
+// any B, L >= 1.  One argument block for both directions; each launcher reads what include/hcm.h lists for its op.  Weights as torch stores them,
+// packed into `work` on the stream in every call.  No allocation, no host copy, no synchronisation, no atomics.
+struct VlaTrainArgs {
+    const float *q = nullptr, *I = nullptr, *kv = nullptr;                     // [B*L][256], [B*L][256], [B][Lk][512]
+    const float *wo = nullptr, *bo = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
+    const float *g1 = nullptr, *be1 = nullptr, *g2 = nullptr, *be2 = nullptr;
+    const uint8_t *keep1 = nullptr, *keep2 = nullptr, *keep3 = nullptr;        // [rows][256], [rows][d_ff], [rows][256] or null
+    float p = 0.f;
+    float *out = nullptr, *a = nullptr, *x1 = nullptr, *x1hat = nullptr, *h = nullptr, *x2hat = nullptr, *rstd = nullptr;   // forward out / backward in
+    const float* d_out = nullptr;
+    float *d_q = nullptr, *d_I = nullptr, *d_kv = nullptr, *d_u = nullptr, *d_hpre = nullptr, *d_z = nullptr, *d_ln = nullptr;
+    float* work = nullptr;                                                     // vla_train_work_floats()
+    int B = 0, L = 0, Lk = 0, d_ff = 0;
+};
+bool vla_train_ok(int B, int L, int Lk, int d_ff);
+size_t vla_train_work_floats(int B, int L, int Lk, int d_ff);
+hipError_t launch_vla_train_fwd(const VlaTrainArgs& t, hipStream_t s);
+hipError_t launch_vla_train_bwd(const VlaTrainArgs& t, hipStream_t s);
 // split-K: fixed-order sum of S f32 partial results [S][M][N] + bias + activation (see Fwd::linear)
 // How many K slices a skinny long-K linear layer is cut into (forward.cpp Fwd::linear and hcm_op_linear use the same rule, so an operator call
 // reproduces the model path bit for bit): powers of two while the (64 x 32-tile) grid stays under 256 workgroups and a slice keeps >= 256 columns

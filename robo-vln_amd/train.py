@@ -4,8 +4,14 @@ backward on the HIP scan kernels (csrc/state_scan.hip, csrc/state_scan_bwd.hip).
 `state_scan` is the autograd function; `RNNStateEncoder` is the drop-in module (same parameters, same state-dict keys, same argument shapes).
 Device tensors go through the kernels -- hidden size 512, one layer, float32, the sizes the kernels are built for -- and anything else on
 the device raises.  CPU tensors go through `cell_loop`, a pure-torch restatement (a per-step cell loop with h * mask in front of every step):
-it is what the GPU tests compare against, not a fallback for a missing kernel."""
+it is what the GPU tests compare against, not a fallback for a missing kernel.
+
+Differentiable cross-modal layer: the reference's InterModuleAttnLayer (models/transformer/transformer.py:209-221) with everything behind the
+three projections -- attention, fc_o, dropout, LayerNorm, the feed-forward block, dropout, LayerNorm -- on the float32 HIP kernels of
+csrc/vla_train.hip, forward and backward.  `vla_layer` is the autograd function, `InterModuleAttnLayer` the drop-in module, `vla_layer_ref` the
+pure-torch restatement (CPU path of the module, and what the tests compare against)."""
 import ctypes as C
+import math
 
 import torch
 from torch import nn
@@ -14,6 +20,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 SCAN_HIDDEN = 512
+VLA_D_MODEL, VLA_HEADS, VLA_MAX_KEYS, VLA_MAX_D_FF = 256, 4, 64, 1024
 
 
 def _ptr(t):
@@ -191,3 +198,179 @@ class RNNStateEncoder(nn.Module):
         if x.size(0) == hidden_states.size(1):
             return self.single_forward(x, hidden_states, masks)
         return self.seq_forward(x, hidden_states, masks)
+
+
+def mask_dropout(x, keep, p):
+    """Dropout with the keep mask given: x * keep / (1 - p); keep None = identity.  keep has x's element count (the kernels take it as (rows, n))."""
+    return x if keep is None else x * keep.reshape(x.shape).to(x.dtype) / (1.0 - p)
+
+
+def vla_attention_ref(q, I, kv, wo, bo, g1, be1, keep1=None, p=0.0, heads=VLA_HEADS):
+    """The first half of vla_layer_ref, MultiHeadAttention behind its projections (transformer.py:111-126): x1 = LN1(I + dropout(fc_o(attention)))"""
+    B, L, _ = q.shape
+    Lk = kv.shape[1]
+    d_k = q.shape[2] // heads
+    qh = q.reshape(B, L, heads, d_k).permute(0, 2, 1, 3)
+    kh = kv[..., :heads * d_k].reshape(B, Lk, heads, d_k).permute(0, 2, 3, 1)
+    vh = kv[..., heads * d_k:].reshape(B, Lk, heads, -1).permute(0, 2, 1, 3)
+    att = torch.softmax(torch.matmul(qh, kh) / math.sqrt(d_k), -1)
+    a = torch.matmul(att, vh).permute(0, 2, 1, 3).reshape(B, L, -1)
+    u = torch.nn.functional.linear(a, wo, bo)
+    return torch.nn.functional.layer_norm(I + mask_dropout(u, keep1, p), I.shape[-1:], g1, be1, 1e-5)
+
+
+def vla_layer_ref(q, I, kv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2, keep=None, p=0.0, heads=VLA_HEADS):
+    """Pure-torch restatement of the layer behind its projections, any dtype, CPU or device: q = fc_q(input_1) (B, L, h*d_k), I = input_1
+    (B, L, d_model), kv = fc_k(input_2) | fc_v(input_2) (B, Lk, h*d_k + h*d_v); keep = None or the three keep masks of the dropouts behind
+    fc_o, behind the ReLU and behind fc2 (element counts B*L*d_model, B*L*d_ff, B*L*d_model), p the dropout probability they were drawn with.
+    MultiHeadAttention (vla_attention_ref) and PositionWiseFeedForward (transformer.py:25-43)."""
+    k1, k2, k3 = keep if keep is not None else (None, None, None)
+    x1 = vla_attention_ref(q, I, kv, wo, bo, g1, be1, k1, p, heads)
+    h = mask_dropout(torch.relu(torch.nn.functional.linear(x1, w1, b1)), k2, p)
+    z = torch.nn.functional.linear(h, w2, b2)
+    return torch.nn.functional.layer_norm(x1 + mask_dropout(z, k3, p), I.shape[-1:], g2, be2, 1e-5)
+
+
+class _VlaLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, I, kv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2, keep1, keep2, keep3, p):
+        if not q.is_cuda:
+            raise ValueError("vla_layer runs on the device; CPU tensors go through vla_layer_ref")
+        named = (("I", I), ("kv", kv), ("wo", wo), ("bo", bo), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("g1", g1), ("be1", be1),
+                 ("g2", g2), ("be2", be2), ("keep[0]", keep1), ("keep[1]", keep2), ("keep[2]", keep3))
+        for name, t in named:
+            if t is not None and t.device != q.device:    # the kernels take raw pointers: a host pointer would fault on the device
+                raise ValueError(f"vla_layer: {name} is on {t.device}, q on {q.device}")
+        D = VLA_D_MODEL
+        if q.dim() != 3 or q.shape[2] != D or I.shape != q.shape or kv.dim() != 3 or kv.shape[0] != q.shape[0] or kv.shape[2] != 2 * D:
+            raise ValueError(f"vla_layer serves q, I (B, L, {D}) and kv (B, Lk, {2 * D}), got {tuple(q.shape)}, {tuple(I.shape)}, {tuple(kv.shape)}")
+        B, L, Lk, d_ff = q.shape[0], q.shape[1], kv.shape[1], w1.shape[0]
+        if B < 1 or L < 1 or not 1 <= Lk <= VLA_MAX_KEYS or d_ff % 256 or not 256 <= d_ff <= VLA_MAX_D_FF:
+            raise ValueError(f"vla_layer serves B, L >= 1, 1..{VLA_MAX_KEYS} keys and d_ff a multiple of 256 up to {VLA_MAX_D_FF}, got B {B}, L {L}, Lk {Lk}, d_ff {d_ff}")
+        for name, t, shape in (("wo", wo, (D, D)), ("bo", bo, (D,)), ("w1", w1, (d_ff, D)), ("b1", b1, (d_ff,)), ("w2", w2, (D, d_ff)), ("b2", b2, (D,)),
+                               ("g1", g1, (D,)), ("be1", be1, (D,)), ("g2", g2, (D,)), ("be2", be2, (D,))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"vla_layer: {name} has shape {tuple(t.shape)}, expected {shape}")
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"vla_layer: p must be in [0, 1), got {p}")
+        rows = B * L
+        keeps = []
+        for name, t, n in (("keep[0]", keep1, D), ("keep[1]", keep2, d_ff), ("keep[2]", keep3, D)):
+            if t is not None and (t.dtype != torch.uint8 or t.numel() != rows * n):
+                raise ValueError(f"vla_layer: {name} must be uint8 with {rows} x {n} elements, got {t.dtype} {tuple(t.shape)}")
+            keeps.append(None if t is None else t.contiguous())
+        q, I, kv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2 = (_f32c(t) for t in (q, I, kv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2))
+        dev = q.device
+        out, a, x1, x1hat, x2hat = (torch.empty(B, L, D, device=dev) for _ in range(5))
+        h = torch.empty(rows, d_ff, device=dev)
+        rstd = torch.empty(rows, 2, device=dev)
+        work = torch.empty(_lib.lib().hcm_op_vla_train_work_floats(B, L, Lk, d_ff), device=dev)
+        _lib.check(_lib.lib().hcm_op_vla_layer_train(_ptr(q), _ptr(I), _ptr(kv), _ptr(wo), _ptr(bo), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(g1),
+                                                     _ptr(be1), _ptr(g2), _ptr(be2), _ptr(keeps[0]), _ptr(keeps[1]), _ptr(keeps[2]), p, _ptr(out), _ptr(a),
+                                                     _ptr(x1), _ptr(x1hat), _ptr(h), _ptr(x2hat), _ptr(rstd), _ptr(work), B, L, Lk, d_ff, _stream()))
+        ctx.save_for_backward(q, kv, wo, w1, w2, g1, g2, a, x1, x1hat, h, x2hat, rstd, *keeps)
+        ctx.dims = (B, L, Lk, d_ff, p)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        q, kv, wo, w1, w2, g1, g2, a, x1, x1hat, h, x2hat, rstd, keep1, keep2, keep3 = ctx.saved_tensors
+        B, L, Lk, d_ff, p = ctx.dims
+        D, rows, dev = VLA_D_MODEL, B * L, q.device
+        d_out = _f32c(d_out)
+        d_q, d_I = torch.empty_like(q), torch.empty_like(q)
+        d_kv = torch.empty_like(kv)
+        d_u, d_z = torch.empty(rows, D, device=dev), torch.empty(rows, D, device=dev)
+        d_hpre = torch.empty(rows, d_ff, device=dev)
+        d_ln = torch.empty(4, D, device=dev)
+        work = torch.empty(_lib.lib().hcm_op_vla_train_work_floats(B, L, Lk, d_ff), device=dev)
+        _lib.check(_lib.lib().hcm_op_vla_layer_bwd(_ptr(d_out), _ptr(q), _ptr(kv), _ptr(wo), _ptr(w1), _ptr(w2), _ptr(g1), _ptr(g2), _ptr(keep1), _ptr(keep2),
+                                                   _ptr(keep3), p, _ptr(x1hat), _ptr(h), _ptr(x2hat), _ptr(rstd), _ptr(work), _ptr(d_q), _ptr(d_I), _ptr(d_kv),
+                                                   _ptr(d_u), _ptr(d_hpre), _ptr(d_z), _ptr(d_ln), B, L, Lk, d_ff, _stream()))
+        need = ctx.needs_input_grad
+        return (d_q if need[0] else None, d_I if need[1] else None, d_kv if need[2] else None,
+                d_u.t() @ a.reshape(rows, D) if need[3] else None, d_u.sum(0) if need[4] else None,
+                d_hpre.t() @ x1.reshape(rows, D) if need[5] else None, d_hpre.sum(0) if need[6] else None,
+                d_z.t() @ h if need[7] else None, d_z.sum(0) if need[8] else None,
+                d_ln[0] if need[9] else None, d_ln[1] if need[10] else None, d_ln[2] if need[11] else None, d_ln[3] if need[12] else None,
+                None, None, None, None)
+
+
+def vla_layer(q, I, kv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2, keep=None, p=0.0):
+    """The cross-modal layer behind its three projections (float32, on the device) with gradients to the first thirteen arguments: arguments as
+    vla_layer_ref; d_model 256, 4 heads of 64, 1..64 keys, d_ff a multiple of 256 up to 1024, any B, L >= 1; keep = None or three uint8 keep masks.
+
+    Forward: hcm_op_vla_layer_train (weight pack, attention, one fused launch for the rest) saves a, x1, h, the two normalised rows and their
+    reciprocal standard deviations.  Backward: hcm_op_vla_layer_bwd gives d_q, d_I, d_kv, the four LayerNorm parameter gradients and the row-local
+    d_u, d_hpre, d_z; the dense reductions over all rows -- dWo = d_u.T @ a, dW1 = d_hpre.T @ x1, dW2 = d_z.T @ h and the three bias column
+    sums -- stay in torch, the split state_scan's backward made.  Nothing is cached between calls: the weights are packed for the kernels on the
+    device in every call."""
+    k1, k2, k3 = keep if keep is not None else (None, None, None)
+    return _VlaLayer.apply(q, I, kv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2, k1, k2, k3, float(p))
+
+
+class _ScaledDotProductAttention(nn.Module):
+    """Parameters and initialisation of the reference's ScaledDotProductAttention (transformer.py:46-79): xavier_normal_ weights, zero biases"""
+
+    def __init__(self, d_model, d_k, d_v, h):
+        super().__init__()
+        self.fc_q = nn.Linear(d_model, h * d_k)
+        self.fc_k = nn.Linear(d_model, h * d_k)
+        self.fc_v = nn.Linear(d_model, h * d_v)
+        self.fc_o = nn.Linear(h * d_v, d_model)
+        for fc in (self.fc_q, self.fc_k, self.fc_v, self.fc_o):
+            nn.init.xavier_normal_(fc.weight, gain=1.0)
+        for fc in (self.fc_q, self.fc_k, self.fc_v, self.fc_o):
+            nn.init.constant_(fc.bias, 0)
+
+
+class _MultiHeadAttention(nn.Module):
+    def __init__(self, d_model, d_k, d_v, h):
+        super().__init__()
+        self.attention = _ScaledDotProductAttention(d_model, d_k, d_v, h)
+        self.layer_norm = nn.LayerNorm(d_model)
+
+
+class _PositionWiseFeedForward(nn.Module):
+    def __init__(self, d_model, d_ff):
+        super().__init__()
+        self.fc1 = nn.Linear(d_model, d_ff)
+        self.fc2 = nn.Linear(d_ff, d_model)
+        self.layer_norm = nn.LayerNorm(d_model)
+
+
+class InterModuleAttnLayer(nn.Module):
+    """Drop-in for the reference's InterModuleAttnLayer (transformer.py:209-221): the same sixteen state-dict keys (enc_att.attention.fc_{q,k,v,o},
+    enc_att.layer_norm, pwff.fc1, pwff.fc2, pwff.layer_norm), the same initialisation and forward signature.  fc_q / fc_k / fc_v are ordinary
+    nn.Linear through torch autograd; everything behind them is vla_layer on the device and vla_layer_ref on the CPU.  In train mode with
+    dropout > 0 the three keep masks are drawn with torch's generator on the input's device (draw_keep), so torch.manual_seed governs them."""
+
+    def __init__(self, d_model=256, d_k=64, d_v=64, h=4, d_ff=1024, dropout=.1):
+        super().__init__()
+        self.enc_att = _MultiHeadAttention(d_model, d_k, d_v, h)
+        self.pwff = _PositionWiseFeedForward(d_model, d_ff)
+        self.d_model, self.d_k, self.d_v, self.h, self.d_ff, self.dropout = d_model, d_k, d_v, h, d_ff, float(dropout)
+
+    def draw_keep(self, rows, device):
+        """The three uint8 keep masks of one call: (rows, d_model), (rows, d_ff), (rows, d_model), each element kept with probability 1 - dropout"""
+        return tuple((torch.rand(rows, n, device=device) >= self.dropout).to(torch.uint8) for n in (self.d_model, self.d_ff, self.d_model))
+
+    def forward(self, input_1, input_2, mask_self_att, mask_enc_att, pos_embed=None, _keep=None):
+        if mask_enc_att is not None:
+            raise ValueError("InterModuleAttnLayer serves mask_enc_att = None, as the high-level model calls it (seq2seq_highlevel_cma.py:200-201)")
+        att, ln1, ff = self.enc_att.attention, self.enc_att.layer_norm, self.pwff
+        p = self.dropout if self.training else 0.0
+        keep = _keep
+        if keep is None and p > 0:
+            keep = self.draw_keep(input_1.shape[0] * input_1.shape[1], input_1.device)
+        q = att.fc_q(input_1)
+        kv = torch.cat([att.fc_k(input_2), att.fc_v(input_2)], -1)
+        args = (q, input_1, kv, att.fc_o.weight, att.fc_o.bias, ff.fc1.weight, ff.fc1.bias, ff.fc2.weight, ff.fc2.bias,
+                ln1.weight, ln1.bias, ff.layer_norm.weight, ff.layer_norm.bias)
+        if not input_1.is_cuda:
+            return vla_layer_ref(*args, keep=keep, p=p, heads=self.h)
+        if (self.d_model, self.d_k, self.d_v, self.h) != (VLA_D_MODEL, 64, 64, VLA_HEADS) or self.d_ff % 256 or not 256 <= self.d_ff <= VLA_MAX_D_FF:
+            raise ValueError(f"on the device InterModuleAttnLayer serves d_model {VLA_D_MODEL}, {VLA_HEADS} heads of 64 and d_ff a multiple of 256 up to "
+                             f"{VLA_MAX_D_FF} (got d_model {self.d_model}, d_k {self.d_k}, d_v {self.d_v}, h {self.h}, d_ff {self.d_ff})")
+        return vla_layer(*args, keep=keep, p=p)

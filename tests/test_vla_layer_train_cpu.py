@@ -1,0 +1,216 @@
+"""The differentiable cross-modal layer without a GPU: train.vla_layer_ref and the InterModuleAttnLayer drop-in against a fixture written from
+the imported reference module (tools/gen_vla_train_golden.py: eval mode, float64, (B, L, Lk) = (2, 5, 16), forward and autograd gradients),
+the module surface (state-dict keys, initialisation, seeded keep masks), mask-form dropout, the C ABI's declaration, binding and argument
+checks in front of every device call, and the ReLU-kink condition of every case of tests/vla_train_cases.py."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from robo_vln_amd import _lib, train
+from tests import vla_train_cases as vc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NO_DEVICE = not torch.cuda.is_available()
+KEYS = [f"enc_att.attention.fc_{n}.{w}" for n in "qkvo" for w in ("weight", "bias")] + \
+       [f"{m}.{w}" for m in ("enc_att.layer_norm", "pwff.fc1", "pwff.fc2", "pwff.layer_norm") for w in ("weight", "bias")]
+
+
+def _golden():
+    z = np.load(os.path.join(ROOT, "tests", "golden", "vla_train_L5_Lk16.npz"))
+    t = {k: torch.from_numpy(z[k]) for k in z.files}
+    sd = {k[3:]: v for k, v in t.items() if k.startswith("sd/")}
+    return t, sd, [int(v) for v in z["dims"]]
+
+
+def _module(sd, dims, dropout=0.25):
+    d_model, d_k, d_v, h, d_ff = dims
+    m = train.InterModuleAttnLayer(d_model=d_model, d_k=d_k, d_v=d_v, h=h, d_ff=d_ff, dropout=dropout).double()
+    m.load_state_dict(sd, strict=True)
+    return m
+
+
+def test_restatement_matches_the_reference_module():
+    """vla_layer_ref with the module's projections applied against the reference's InterModuleAttnLayer: output and every gradient to 1e-12"""
+    t, sd, dims = _golden()
+    h = dims[3]
+    leaves = {k: v.clone().requires_grad_() for k, v in sd.items()}
+    x1, x2 = t["input_1"].clone().requires_grad_(), t["input_2"].clone().requires_grad_()
+    lin = torch.nn.functional.linear
+    w = lambda n: (leaves[n + ".weight"], leaves[n + ".bias"])
+    q = lin(x1, *w("enc_att.attention.fc_q"))
+    kv = torch.cat([lin(x2, *w("enc_att.attention.fc_k")), lin(x2, *w("enc_att.attention.fc_v"))], -1)
+    out = train.vla_layer_ref(q, x1, kv, *w("enc_att.attention.fc_o"), *w("pwff.fc1"), *w("pwff.fc2"), *w("enc_att.layer_norm"), *w("pwff.layer_norm"),
+                              heads=h)
+    assert (out - t["out"]).abs().max().item() <= 1e-12
+    names = list(leaves)
+    grads = torch.autograd.grad(out, [x1, x2] + [leaves[n] for n in names], t["cotangent"])
+    for n, g in zip(["input_1", "input_2"] + names, grads):
+        assert (g - t["grad/" + n]).abs().max().item() <= 1e-12, n
+
+
+def test_drop_in_loads_the_reference_state_dict():
+    t, sd, dims = _golden()
+    assert list(sd) == KEYS
+    m = _module(sd, dims)
+    assert list(m.state_dict()) == list(sd) and len(sd) == 16
+    out = m.eval()(t["input_1"], t["input_2"], None, None)
+    assert (out - t["out"]).abs().max().item() <= 1e-12
+    assert list(train.InterModuleAttnLayer().state_dict()) == KEYS            # the default sizes are the high-level model's
+
+
+def test_drop_in_initialisation():
+    """xavier_normal_ weights and zero biases on the four attention projections, nn.Linear / nn.LayerNorm defaults elsewhere"""
+    torch.manual_seed(0)
+    m = train.InterModuleAttnLayer()
+    att = m.enc_att.attention
+    for fc in (att.fc_q, att.fc_k, att.fc_v, att.fc_o):
+        assert fc.bias.abs().max().item() == 0
+        std = fc.weight.std().item()
+        assert abs(std - (2.0 / 512) ** 0.5) < 0.05 * (2.0 / 512) ** 0.5, std        # xavier normal: sqrt(2 / (fan_in + fan_out))
+        assert fc.weight.abs().max().item() > 3 * (2.0 / 512) ** 0.5                  # a normal's tail, not a uniform's edge
+    assert m.pwff.fc1.weight.shape == (1024, 256) and m.pwff.fc1.bias.abs().max().item() > 0
+    assert torch.equal(m.enc_att.layer_norm.weight, torch.ones(256)) and m.enc_att.layer_norm.eps == 1e-5
+
+
+def test_drop_in_train_mode_is_seeded_and_masks_have_the_expected_mean():
+    t, sd, dims = _golden()
+    m = _module(sd, dims).train()
+    torch.manual_seed(5)
+    y1 = m(t["input_1"], t["input_2"], None, None)
+    torch.manual_seed(5)
+    y2 = m(t["input_1"], t["input_2"], None, None)
+    assert torch.equal(y1, y2) and not torch.equal(y1, m(t["input_1"], t["input_2"], None, None))
+    assert not torch.equal(y1, m.eval()(t["input_1"], t["input_2"], None, None))
+    big = train.InterModuleAttnLayer(dropout=0.25)
+    torch.manual_seed(6)
+    keep = big.draw_keep(40, "cpu")
+    assert [tuple(k.shape) for k in keep] == [(40, 256), (40, 1024), (40, 256)] and all(k.dtype == torch.uint8 for k in keep)
+    for k in keep:
+        n = k.numel()
+        assert abs(k.float().mean().item() - 0.75) <= 5 * (0.25 * 0.75 / n) ** 0.5          # five standard deviations of the binomial mean
+    torch.manual_seed(6)
+    assert all(torch.equal(a, b) for a, b in zip(keep, big.draw_keep(40, "cpu")))
+    # injected masks reach the restatement unchanged: the module with given masks is vla_layer_ref on its own projections with those masks
+    d_model, _, _, h, d_ff = dims
+    rows = t["input_1"].shape[0] * t["input_1"].shape[1]
+    g = torch.Generator().manual_seed(7)
+    given = tuple((torch.rand(rows, n, generator=g) >= 0.25).to(torch.uint8) for n in (d_model, d_ff, d_model))
+    att, ff = m.enc_att.attention, m.pwff
+    q = att.fc_q(t["input_1"])
+    kv = torch.cat([att.fc_k(t["input_2"]), att.fc_v(t["input_2"])], -1)
+    want = train.vla_layer_ref(q, t["input_1"], kv, att.fc_o.weight, att.fc_o.bias, ff.fc1.weight, ff.fc1.bias, ff.fc2.weight, ff.fc2.bias,
+                               m.enc_att.layer_norm.weight, m.enc_att.layer_norm.bias, ff.layer_norm.weight, ff.layer_norm.bias, keep=given, p=0.25, heads=h)
+    got = m.train()(t["input_1"], t["input_2"], None, None, _keep=given)
+    assert torch.equal(got, want) and not torch.equal(got, m.eval()(t["input_1"], t["input_2"], None, None))
+
+
+def test_mask_form_dropout():
+    g = torch.Generator().manual_seed(1)
+    x = torch.rand(6, 32, generator=g, dtype=torch.float64) - 0.5
+    keep = (torch.rand(6, 32, generator=g) >= 0.3).to(torch.uint8)
+    assert torch.equal(train.mask_dropout(x, keep, 0.3), x * keep / (1 - 0.3))
+    assert torch.equal(train.mask_dropout(x, keep.reshape(-1), 0.3), x * keep / (1 - 0.3))         # (rows, n) or flat: the element count decides
+    assert train.mask_dropout(x, None, 0.3) is x
+    assert train.mask_dropout(x, torch.zeros_like(keep), 0.3).abs().max().item() == 0
+    # as a layer: all-ones masks with p = 0 are the eval-mode layer, all-zero masks leave LN2(LN1(I))
+    args, _, _ = vc.make_inputs(2, 3, 4, 256, 0.0, 0)
+    a = [v.double() for v in args]
+    ones = tuple(torch.ones(6, n, dtype=torch.uint8) for n in (256, 256, 256))
+    assert torch.equal(train.vla_layer_ref(*a, keep=ones, p=0.0), train.vla_layer_ref(*a))
+    zeros = tuple(torch.zeros_like(k) for k in ones)
+    ln = torch.nn.functional.layer_norm
+    assert torch.equal(train.vla_layer_ref(*a, keep=zeros, p=0.25), ln(ln(a[1], (256,), a[9], a[10], 1e-5), (256,), a[11], a[12], 1e-5))
+
+
+def test_vla_layer_refuses_cpu_tensors_and_module_refuses_a_mask():
+    args, keep, _ = vc.make_inputs(1, 2, 3, 256, 0.25, 0)
+    with pytest.raises(ValueError, match="vla_layer_ref"):
+        train.vla_layer(*args)
+    with pytest.raises(ValueError):
+        train.vla_layer(*args, keep=keep, p=0.25)
+    m = train.InterModuleAttnLayer(d_ff=256)
+    with pytest.raises(ValueError, match="seq2seq_highlevel_cma.py:200-201"):
+        m(args[1], args[2][..., :256], None, torch.zeros(1, 4, 2, 3, dtype=torch.bool))
+    assert m(args[1], args[2][..., :256], None, None).shape == (1, 2, 256)
+
+
+@pytest.mark.parametrize("case", vc.CASES)
+def test_kink_condition_holds(case):
+    """every fc1 pre-activation of the case is at least 2e-5 from zero in float64 (float32 deviates by at most 3.2e-6)"""
+    c = vc.case(*case)
+    print(f"{case}: min |pre-activation| = {c['kink']:.3e}")
+    assert c["kink"] >= vc.KINK
+    args32 = c["args"]
+    q, I, kv, wo, bo, w1, b1 = args32[:7]
+    x1 = train.vla_attention_ref(q, I, kv, wo, bo, args32[9], args32[10], c["keep"][0] if c["keep"] else None, c["p"])
+    pre32 = torch.nn.functional.linear(x1, w1, b1)
+    a64 = [t.double() for t in args32]
+    x64 = train.vla_attention_ref(a64[0], a64[1], a64[2], a64[3], a64[4], a64[9], a64[10], c["keep"][0] if c["keep"] else None, c["p"])
+    pre64 = torch.nn.functional.linear(x64, a64[5], a64[6])
+    assert torch.equal(pre32 > 0, pre64 > 0)                       # no sign flips in float32
+    assert len(vc.CASES) == 7 and set(vc.SEEDS) == set(vc.CASES)
+
+
+# ---- C ABI without a device ----
+def test_header_declares_and_binding_agrees():
+    text = open(os.path.join(ROOT, "include", "hcm.h")).read()
+    for sym, n in (("hcm_op_vla_layer_train", 30), ("hcm_op_vla_layer_bwd", 29)):
+        mt = re.search(r"int %s\(([^;]*)\);" % sym, text)
+        assert mt, f"include/hcm.h does not declare {sym}"
+        n_args = len([a for a in mt.group(1).split(",") if a.strip()])
+        res, args = _lib.EXPORTS[sym]
+        assert res is C.c_int and len(args) == n_args == n, (sym, len(args), n_args)
+        assert hasattr(_lib.lib(), sym)
+    assert re.search(r"int64_t hcm_op_vla_train_work_floats\(int B, int L, int Lk, int d_ff\);", text)
+
+
+def test_work_floats_query():
+    l = _lib.lib()
+    for B, L, Lk, d_ff in ((1, 1, 1, 256), (64, 80, 16, 1024), (3, 17, 64, 512)):
+        rows = B * L
+        assert l.hcm_op_vla_train_work_floats(B, L, Lk, d_ff) == 256 * 256 + 2 * 256 * d_ff + rows * 256 + (rows + 63) // 64 * 1024
+    for bad in ((0, 1, 1, 256), (1, 0, 1, 256), (1, 1, 0, 256), (1, 1, 65, 256), (1, 1, 1, 1280), (1, 1, 1, 384), (1, 1, 1, 0)):
+        assert l.hcm_op_vla_train_work_floats(*bad) == 0, bad
+
+
+def _buf():
+    raw = (C.c_float * 80)()
+    addr = (C.addressof(raw) + 15) // 16 * 16
+    return raw, C.c_void_p(addr)
+
+
+def test_argument_errors_without_a_device():
+    """every refusal returns HCM_ERR_ARG in front of the first device call: null pointers, sizes, p, misaligned pointers"""
+    l = _lib.lib()
+    raw, p = _buf()
+
+    def fwd(ptrs=None, keep=(None, None, None), prob=0.0, B=1, L=1, Lk=1, d_ff=256):
+        ptrs = ptrs or [p] * 21
+        return l.hcm_op_vla_layer_train(*ptrs[:13], *keep, prob, *ptrs[13:21], B, L, Lk, d_ff, None)
+
+    def bwd(ptrs=None, keep=(None, None, None), prob=0.0, B=1, L=1, Lk=1, d_ff=256):
+        ptrs = ptrs or [p] * 20
+        return l.hcm_op_vla_layer_bwd(*ptrs[:8], *keep, prob, *ptrs[8:20], B, L, Lk, d_ff, None)
+
+    for call, n in ((fwd, 21), (bwd, 20)):
+        for i in range(n):
+            ptrs = [p] * n
+            ptrs[i] = None
+            assert call(ptrs) == -1, (call.__name__, i)
+        for kw in (dict(Lk=0), dict(Lk=65), dict(d_ff=1280), dict(d_ff=384), dict(B=0), dict(L=0), dict(prob=1.0), dict(prob=-0.1), dict(prob=float("nan"))):
+            assert call(**kw) == -1, (call.__name__, kw)
+        odd = C.c_void_p(p.value + 2)
+        assert call(keep=(odd, None, None)) == -1 and call(keep=(None, None, odd)) == -1
+        ptrs = [p] * n
+        ptrs[-1 if call is fwd else 8 + 4] = C.c_void_p(p.value + 4)         # the work buffer off its 16-byte alignment
+        assert call(ptrs) == -1
+    # an output inside the work buffer: every pointer here is the same buffer, so the otherwise valid call is refused for the overlap alone.
+    # Only that one check stands between this call and a launch on host memory, so it runs only where no device is visible (there a call that
+    # got past it would end in HCM_ERR_HIP, -2); with a device the overlap refusal is tests/test_vla_layer_train_gpu.py's, on device buffers.
+    if NO_DEVICE:
+        assert fwd() == -1 and bwd() == -1
+    del raw
