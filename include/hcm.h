@@ -713,6 +713,33 @@ int hcm_op_vla_layer_bwd(const float* d_out, const float* q, const float* kv, co
                          const float* x2hat, const float* rstd, float* work, float* d_q, float* d_I, float* d_kv, float* d_u, float* d_hpre, float* d_z,
                          float* d_ln, int B, int L, int Lk, int d_ff, void* stream);
 
+/* One half of Visual_Ling_Attn's prologue (transformer.py:262-274) in float32 and with what a backward pass needs (csrc/embed_train.hip): Linear, ReLU,
+ * dropout, LayerNorm and an optional additive table, output width 256.  rows >= 0; K a multiple of 64 from 64 to 1024; 0 <= p < 1; period >= 1 when
+ * post is given (rows need not be a multiple of it); anything else HCM_ERR_ARG.
+ *   pre  = x W^T + b;   r = keep s relu(pre), s = 1 / (1 - p)   (keep NULL: no dropout at all, r = relu(pre), and the backward takes p = 0)
+ *   xhat = (r - mean(r)) rstd, rstd = 1 / sqrt(var(r) + 1e-5) (biased variance);   y = xhat gamma + beta + post[row % period]   (post NULL: no table)
+ *   x (rows, K); w (256, K), b, gamma, beta (256) as torch stores them; keep (rows, 256) uint8; post (period, 256), e.g. the sinusoid table with
+ *   period = L; all on the device.
+ * Written by the forward, read by the backward (owned by the caller): xhat (rows, 256) and rstd (rows) float32, and gate (rows, 256) uint8 =
+ *   (pre > 0) && keep -- one byte per element instead of a saved r, written with or without dropout.  pre, relu(pre) and r never reach memory.
+ * work: hcm_op_embed_ln_work_floats(rows, K) floats (0 for unsupported sizes) owned by the caller, serving either op: the weight in the kernels'
+ *   operand order (float4 index (ntile * Kb/8 + kk) * 64 + lane holds B[k = 8 kk + 4 (lane >> 5) + j][n = 32 ntile + (lane & 31)], j = 0..3, with
+ *   B = W^T (Kb = K) forward and B = W (Kb = 256) backward; packed on `stream` in every call, nothing is cached) and the backward's LayerNorm
+ *   partial sums.  No output may overlap it (HCM_ERR_ARG).  Float tensors and work must be 16-byte aligned, keep and gate 4-byte aligned.
+ * Both ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible.
+ * rows = 0: HCM_OK; the backward writes zeros to d_ln; nothing else is touched and the row pointers may be NULL. */
+int64_t hcm_op_embed_ln_work_floats(int rows, int K);
+int hcm_op_embed_ln_train(const float* x, const float* w, const float* b, const float* gamma, const float* beta, const uint8_t* keep, float p,
+                          const float* post, int period, float* y, float* xhat, float* rstd, uint8_t* gate, float* work, int rows, int K, void* stream);
+/* Backward of hcm_op_embed_ln_train from d_y (rows, 256) and what the forward saved; w, gamma and p as the forward had them.
+ *   dxh = d_y gamma;  d_r = rstd (dxh - mean(dxh) - xhat mean(dxh xhat));  d_pre = gate s d_r;  d_x = d_pre W
+ *   out: d_pre (rows, 256), the row-local gradient of the pre-activation, so that dW = d_pre^T x and db = its column sum -- dense reductions over
+ *        all rows, left to the caller; d_x (rows, K), or NULL: the product and the weight pack are skipped; d_ln (2, 256) = d_gamma = sum_rows
+ *        d_y xhat and d_beta = sum_rows d_y, reduced here (per-workgroup partials in `work`, summed in workgroup order).
+ * Up to three launches on `stream` (pack, row kernel, reduce), no host synchronisation. */
+int hcm_op_embed_ln_bwd(const float* d_y, const float* w, const float* gamma, const float* xhat, const float* rstd, const uint8_t* gate, float p,
+                        float* work, float* d_pre, float* d_x, float* d_ln, int rows, int K, void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

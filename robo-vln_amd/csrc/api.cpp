@@ -1813,6 +1813,35 @@ int hcm_op_vla_layer_bwd(const float* d_out, const float* q, const float* kv, co
     return op_rc(launch_vla_train_bwd(t, (hipStream_t)stream));
 }
 
+int64_t hcm_op_embed_ln_work_floats(int rows, int K) { return embed_train_ok(rows, K) ? (int64_t)embed_train_work_floats(rows, K) : 0; }
+
+int hcm_op_embed_ln_train(const float* x, const float* w, const float* b, const float* gamma, const float* beta, const uint8_t* keep, float p,
+                          const float* post, int period, float* y, float* xhat, float* rstd, uint8_t* gate, float* work, int rows, int K, void* stream) {
+    if (!embed_train_ok(rows, K) || !(p >= 0.f && p < 1.f) || (post && period < 1)) return HCM_ERR_ARG;
+    if (rows == 0) return HCM_OK;
+    if (!x || !w || !b || !gamma || !beta || !y || !xhat || !rstd || !gate || !work) return HCM_ERR_ARG;
+    if (!vla_train_aligned({x, w, gamma, beta, post, y, xhat, work}, {keep, gate})) return HCM_ERR_ARG;
+    const size_t n = (size_t)rows * 256;
+    if (vla_train_in_work(work, embed_train_work_floats(rows, K), {{y, n}, {xhat, n}, {rstd, (size_t)rows}, {gate, n / 4}})) return HCM_ERR_ARG;
+    EmbedTrainArgs t;
+    t.x = x; t.w = w; t.b = b; t.gamma = gamma; t.beta = beta; t.keep = keep; t.p = p; t.post = post; t.period = period;
+    t.y = y; t.xhat = xhat; t.rstd = rstd; t.gate = gate; t.work = work; t.rows = rows; t.K = K;
+    return op_rc(launch_embed_train_fwd(t, (hipStream_t)stream));
+}
+
+int hcm_op_embed_ln_bwd(const float* d_y, const float* w, const float* gamma, const float* xhat, const float* rstd, const uint8_t* gate, float p,
+                        float* work, float* d_pre, float* d_x, float* d_ln, int rows, int K, void* stream) {
+    if (!embed_train_ok(rows, K) || !(p >= 0.f && p < 1.f) || !d_ln || !work) return HCM_ERR_ARG;
+    if (rows && (!d_y || !w || !gamma || !xhat || !rstd || !gate || !d_pre)) return HCM_ERR_ARG;
+    if (!vla_train_aligned({d_y, w, gamma, xhat, work, d_pre, d_x}, {gate})) return HCM_ERR_ARG;
+    const size_t n = (size_t)rows * 256;
+    if (vla_train_in_work(work, embed_train_work_floats(rows, K), {{d_pre, n}, {d_x, (size_t)rows * K}, {d_ln, 512}})) return HCM_ERR_ARG;
+    EmbedTrainArgs t;
+    t.d_y = d_y; t.w = w; t.gamma = gamma; t.xhat = const_cast<float*>(xhat); t.rstd = const_cast<float*>(rstd); t.gate = const_cast<uint8_t*>(gate);
+    t.p = p; t.work = work; t.d_pre = d_pre; t.d_x = d_x; t.d_ln = d_ln; t.rows = rows; t.K = K;
+    return op_rc(launch_embed_train_bwd(t, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

@@ -314,6 +314,27 @@ bool vla_train_ok(int B, int L, int Lk, int d_ff);
 size_t vla_train_work_floats(int B, int L, int Lk, int d_ff);
 hipError_t launch_vla_train_fwd(const VlaTrainArgs& t, hipStream_t s);
 hipError_t launch_vla_train_bwd(const VlaTrainArgs& t, hipStream_t s);
+// vla_train.hip's weight pack (B[k][n] = trans ? src[n * ld + k] : src[k * ld + n], K x N, into fragment order) and LayerNorm partial reduce
+// (d_ln[v][c] = sum over nwg workgroups of part[g][v][c], g stride 1024 floats, v < nvec <= 4) for embed_train.hip
+hipError_t launch_train_pack(const float* src, float* dst, int ld, int trans, int K, int N, hipStream_t s);
+hipError_t launch_train_ln_reduce(const float* part, float* d_ln, int nwg, int nvec, hipStream_t s);
+// Visual_Ling_Attn's prologue in float32 with a backward pass (embed_train.hip): y = LN(keep s relu(x W^T + b)) + post[row % period], width 256,
+// K a multiple of 64 from 64 to 1024, rows >= 0.  One argument block for both directions, as VlaTrainArgs.
+struct EmbedTrainArgs {
+    const float *x = nullptr, *w = nullptr, *b = nullptr, *gamma = nullptr, *beta = nullptr, *post = nullptr;   // [rows][K], [256][K], [256] x 3, [period][256] or null
+    const uint8_t* keep = nullptr;                                             // [rows][256] or null
+    float p = 0.f;
+    float *y = nullptr, *xhat = nullptr, *rstd = nullptr;                      // forward out / backward in: [rows][256], [rows][256], [rows]
+    uint8_t* gate = nullptr;                                                   // [rows][256]
+    const float* d_y = nullptr;
+    float *d_pre = nullptr, *d_x = nullptr, *d_ln = nullptr;                   // [rows][256], [rows][K] or null (not computed), [2][256]
+    float* work = nullptr;                                                     // embed_train_work_floats()
+    int rows = 0, K = 0, period = 0;
+};
+bool embed_train_ok(int rows, int K);
+size_t embed_train_work_floats(int rows, int K);
+hipError_t launch_embed_train_fwd(const EmbedTrainArgs& t, hipStream_t s);
+hipError_t launch_embed_train_bwd(const EmbedTrainArgs& t, hipStream_t s);
 // split-K: fixed-order sum of S f32 partial results [S][M][N] + bias + activation (see Fwd::linear)
 // How many K slices a skinny long-K linear layer is cut into (forward.cpp Fwd::linear and hcm_op_linear use the same rule, so an operator call
 // reproduces the model path bit for bit): powers of two while the (64 x 32-tile) grid stays under 256 workgroups and a slice keeps >= 256 columns

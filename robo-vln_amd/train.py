@@ -9,7 +9,12 @@ it is what the GPU tests compare against, not a fallback for a missing kernel.
 Differentiable cross-modal layer: the reference's InterModuleAttnLayer (models/transformer/transformer.py:209-221) with everything behind the
 three projections -- attention, fc_o, dropout, LayerNorm, the feed-forward block, dropout, LayerNorm -- on the float32 HIP kernels of
 csrc/vla_train.hip, forward and backward.  `vla_layer` is the autograd function, `InterModuleAttnLayer` the drop-in module, `vla_layer_ref` the
-pure-torch restatement (CPU path of the module, and what the tests compare against)."""
+pure-torch restatement (CPU path of the module, and what the tests compare against).
+
+Differentiable Visual_Ling_Attn: the reference's whole cross-modal encoder (transformer.py:250-282).  Its prologue -- Linear, ReLU, dropout, the
+shared LayerNorm, and for the instruction half the sinusoid table -- is `embed_ln` on the float32 HIP kernels of csrc/embed_train.hip, one launch
+forward and one backward per half; `embed_ln_ref` is the pure-torch restatement, `sinusoid_table` the reference's table, `Visual_Ling_Attn` the
+drop-in module around `InterModuleAttnLayer`."""
 import ctypes as C
 import math
 
@@ -21,6 +26,7 @@ from . import _lib
 
 SCAN_HIDDEN = 512
 VLA_D_MODEL, VLA_HEADS, VLA_MAX_KEYS, VLA_MAX_D_FF = 256, 4, 64, 1024
+EMBED_K_STEP, EMBED_MAX_K = 64, 1024
 
 
 def _ptr(t):
@@ -374,3 +380,163 @@ class InterModuleAttnLayer(nn.Module):
             raise ValueError(f"on the device InterModuleAttnLayer serves d_model {VLA_D_MODEL}, {VLA_HEADS} heads of 64 and d_ff a multiple of 256 up to "
                              f"{VLA_MAX_D_FF} (got d_model {self.d_model}, d_k {self.d_k}, d_v {self.d_v}, h {self.h}, d_ff {self.d_ff})")
         return vla_layer(*args, keep=keep, p=p)
+
+
+def sinusoid_table(L, d):
+    """The reference's sinusoid_encoding_table(L, d) (common/utils.py:167-185): float32 on the CPU, by the reference's own expression"""
+    pos = torch.arange(L, dtype=torch.float32).view(-1, 1)
+    dim = torch.arange(d // 2, dtype=torch.float32).view(1, -1)
+    out = torch.zeros((L, d))
+    out[:, ::2] = torch.sin(pos / 10000 ** (2 * dim / d))
+    out[:, 1::2] = torch.cos(pos / 10000 ** (2 * dim / d))
+    return out
+
+
+def embed_ln_ref(x, w, b, gamma, beta, keep=None, p=0.0, post=None):
+    """Pure-torch restatement of one half of Visual_Ling_Attn's prologue, any width, dtype and device: LayerNorm(dropout(relu(x W^T + b))) with
+    the dropout's keep mask given (None = no dropout), plus post[row % period] for an additive table post (period, width), rows counted over
+    all leading dimensions of x."""
+    r = mask_dropout(torch.relu(torch.nn.functional.linear(x, w, b)), keep, p)
+    y = torch.nn.functional.layer_norm(r, r.shape[-1:], gamma, beta, 1e-5)
+    if post is not None:
+        rows = y.numel() // y.shape[-1]
+        y = y + post[torch.arange(rows, device=post.device) % post.shape[0]].reshape(y.shape)
+    return y
+
+
+def embed_k_ok(K):
+    return EMBED_K_STEP <= K <= EMBED_MAX_K and K % EMBED_K_STEP == 0
+
+
+class _EmbedLn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, keep, p, post):
+        if not x.is_cuda:
+            raise ValueError("embed_ln runs on the device; CPU tensors go through embed_ln_ref")
+        for name, t in (("w", w), ("b", b), ("gamma", gamma), ("beta", beta), ("keep", keep), ("post", post)):
+            if t is not None and t.device != x.device:    # the kernels take raw pointers: a host pointer would fault on the device
+                raise ValueError(f"embed_ln: {name} is on {t.device}, x on {x.device}")
+        D, K = VLA_D_MODEL, x.shape[-1] if x.dim() else 0
+        if x.dim() < 2 or not embed_k_ok(K):
+            raise ValueError(f"embed_ln serves x (..., K) with K a multiple of {EMBED_K_STEP} from {EMBED_K_STEP} to {EMBED_MAX_K}, got {tuple(x.shape)}")
+        for name, t, shape in (("w", w, (D, K)), ("b", b, (D,)), ("gamma", gamma, (D,)), ("beta", beta, (D,))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"embed_ln: {name} has shape {tuple(t.shape)}, expected {shape}")
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"embed_ln: p must be in [0, 1), got {p}")
+        rows = x.numel() // K
+        if keep is not None and (keep.dtype != torch.uint8 or keep.numel() != rows * D):
+            raise ValueError(f"embed_ln: keep must be uint8 with {rows} x {D} elements, got {keep.dtype} {tuple(keep.shape)}")
+        if post is not None and (post.dim() != 2 or post.shape[0] < 1 or post.shape[1] != D):
+            raise ValueError(f"embed_ln: post must be (period >= 1, {D}), got {tuple(post.shape)}")
+        if keep is None:
+            p = 0.0                                       # no mask, no scaling: the backward's s must be 1 as well
+        x2, w, b, gamma, beta = (_f32c(t) for t in (x.reshape(rows, K), w, b, gamma, beta))
+        keep = None if keep is None else keep.contiguous()
+        post = None if post is None else _f32c(post)
+        dev = x.device
+        y, xhat = torch.empty(rows, D, device=dev), torch.empty(rows, D, device=dev)
+        rstd = torch.empty(rows, device=dev)
+        gate = torch.empty(rows, D, dtype=torch.uint8, device=dev)
+        work = torch.empty(_lib.lib().hcm_op_embed_ln_work_floats(rows, K), device=dev)
+        _lib.check(_lib.lib().hcm_op_embed_ln_train(_ptr(x2), _ptr(w), _ptr(b), _ptr(gamma), _ptr(beta), _ptr(keep), p, _ptr(post),
+                                                    post.shape[0] if post is not None else 0, _ptr(y), _ptr(xhat), _ptr(rstd), _ptr(gate), _ptr(work),
+                                                    rows, K, _stream()))
+        ctx.save_for_backward(x2, w, gamma, xhat, rstd, gate)
+        ctx.dims = (rows, K, p, tuple(x.shape))
+        return y.reshape(*x.shape[:-1], D)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        x2, w, gamma, xhat, rstd, gate = ctx.saved_tensors
+        rows, K, p, shape = ctx.dims
+        D, dev = VLA_D_MODEL, x2.device
+        need = ctx.needs_input_grad
+        d_y = _f32c(d_y).reshape(rows, D)
+        d_pre = torch.empty(rows, D, device=dev)
+        d_x = torch.empty(rows, K, device=dev) if need[0] else None
+        d_ln = torch.empty(2, D, device=dev)
+        work = torch.empty(_lib.lib().hcm_op_embed_ln_work_floats(rows, K), device=dev)
+        _lib.check(_lib.lib().hcm_op_embed_ln_bwd(_ptr(d_y), _ptr(w), _ptr(gamma), _ptr(xhat), _ptr(rstd), _ptr(gate), p, _ptr(work), _ptr(d_pre),
+                                                  _ptr(d_x), _ptr(d_ln), rows, K, _stream()))
+        return (d_x.reshape(shape) if need[0] else None, d_pre.t() @ x2 if need[1] else None, d_pre.sum(0) if need[2] else None,
+                d_ln[0] if need[3] else None, d_ln[1] if need[4] else None, None, None, None)
+
+
+def embed_ln(x, w, b, gamma, beta, keep=None, p=0.0, post=None):
+    """One half of Visual_Ling_Attn's prologue (float32, on the device) with gradients to x, w, b, gamma, beta: arguments as embed_ln_ref; x
+    (..., K) with K a multiple of 64 from 64 to 1024, w (256, K), keep None or a uint8 keep mask with rows x 256 elements, post None or a
+    (period, 256) table added behind the LayerNorm.
+
+    Forward: hcm_op_embed_ln_train (weight pack and one fused launch) saves the normalised rows, their reciprocal standard deviations and one
+    gate byte per element.  Backward: hcm_op_embed_ln_bwd gives the row-local d_pre, the two LayerNorm parameter gradients, and d_x = d_pre W
+    only when x requires a gradient; dW = d_pre.T @ x and db = d_pre.sum(0) are dense reductions over all rows and stay in torch, the split
+    vla_layer's backward made.  Nothing is cached between calls."""
+    return _EmbedLn.apply(x, w, b, gamma, beta, keep, float(p), post)
+
+
+class Visual_Ling_Attn(nn.Module):
+    """Drop-in for the reference's Visual_Ling_Attn (transformer.py:250-282), `image_cm_encoder` of the high-level model: the reference's state-dict
+    keys (layers.{i}.<the sixteen keys of InterModuleAttnLayer>, vis_fc.*, ins_fc.*, layer_norm.*), initialisation and forward signature.  Takes the
+    reference's config object (N, vis_in_features, ins_in_features, d_model, h, d_ff, dropout) or the same names as keyword arguments, which win.
+
+    Both prologue halves are embed_ln on the device and embed_ln_ref on the CPU; one layer_norm serves both, and its gradient accumulates
+    through autograd.  The sinusoid table is kept per (L, device) in the plain dict `_tables` -- no buffer, not in the state dict -- so the device
+    path copies nothing per call.  In train mode with dropout > 0 the keep masks are drawn by draw_keep with torch's generator on the input's
+    device, in the order vis half, ins half, then each layer's three, so torch.manual_seed governs them; `_keep` takes them explicitly."""
+
+    def __init__(self, config=None, **kw):
+        super().__init__()
+        names = ("N", "vis_in_features", "ins_in_features", "d_model", "h", "d_ff", "dropout")
+        unknown = set(kw) - set(names)
+        if unknown:
+            raise TypeError(f"Visual_Ling_Attn: unknown arguments {sorted(unknown)}")
+        missing = [n for n in names if n not in kw and not hasattr(config, n)]
+        if missing:
+            raise TypeError(f"Visual_Ling_Attn: missing {missing}")
+        N, vis_in, ins_in, d_model, h, d_ff, dropout = (kw[n] if n in kw else getattr(config, n) for n in names)
+        self.d_model, self.d_att, self.p = d_model, int(d_model / h), float(dropout)
+        self.layers = nn.ModuleList([InterModuleAttnLayer(d_model, self.d_att, self.d_att, h, d_ff, dropout) for _ in range(N)])
+        self.vis_fc = nn.Linear(vis_in, d_model)
+        self.ins_fc = nn.Linear(ins_in, d_model)
+        self.layer_norm = nn.LayerNorm(d_model)
+        self._tables = {}
+
+    def table(self, L, device):
+        key = (L, torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = sinusoid_table(L, self.d_model).to(device)
+        return self._tables[key]
+
+    def draw_keep(self, B, L, Lk, device):
+        """The uint8 keep masks of one call in their fixed order: (vis half (B*Lk, d_model), ins half (B*L, d_model), layer 0's three, layer 1's three, ...)"""
+        def draw(rows):
+            return (torch.rand(rows, self.d_model, device=device) >= self.p).to(torch.uint8)
+        vis, ins = draw(B * Lk), draw(B * L)
+        return (vis, ins, *(layer.draw_keep(B * L, device) for layer in self.layers))
+
+    def _embed(self, x, fc, keep, p, post):
+        args = (x, fc.weight, fc.bias, self.layer_norm.weight, self.layer_norm.bias)
+        if not x.is_cuda:
+            return embed_ln_ref(*args, keep=keep, p=p, post=post)
+        if self.d_model != VLA_D_MODEL or not embed_k_ok(fc.in_features):
+            raise ValueError(f"on the device Visual_Ling_Attn serves d_model {VLA_D_MODEL} and input widths that are multiples of {EMBED_K_STEP} from "
+                             f"{EMBED_K_STEP} to {EMBED_MAX_K} (got d_model {self.d_model}, in_features {fc.in_features})")
+        return embed_ln(*args, keep=keep, p=p, post=post)
+
+    def forward(self, input, input_2, self_att_mask, enc_att_mask, _keep=None):
+        if self_att_mask is not None or enc_att_mask is not None:
+            raise ValueError("Visual_Ling_Attn serves self_att_mask = enc_att_mask = None, as the high-level model calls it (seq2seq_highlevel_cma.py:200-201)")
+        if input.dim() != 3 or input_2.dim() != 3 or input.shape[0] != input_2.shape[0]:
+            raise ValueError(f"Visual_Ling_Attn takes input (B, L, ins_in) and input_2 (B, Lk, vis_in), got {tuple(input.shape)}, {tuple(input_2.shape)}")
+        B, L, Lk = input.shape[0], input.shape[1], input_2.shape[1]
+        p = self.p if self.training else 0.0
+        keep = _keep
+        if keep is None:
+            keep = self.draw_keep(B, L, Lk, input.device) if p > 0 else (None, None) + (None,) * len(self.layers)
+        out = self._embed(input_2, self.vis_fc, keep[0], p, None)
+        inp = self._embed(input, self.ins_fc, keep[1], p, self.table(L, input.device))
+        for layer, k in zip(self.layers, keep[2:]):
+            out = layer(inp, out, None, None, _keep=k)
+        return out

@@ -1,0 +1,451 @@
+"""The differentiable Visual_Ling_Attn on the GPU: robo_vln_amd.train.embed_ln (hcm_op_embed_ln_train + hcm_op_embed_ln_bwd) against float64 on the
+CPU on the cases of tests/embed_train_cases.py, the raw C ABI (determinism, sentinel pre-fill with guard elements, NULL keep / post / d_x, zero
+rows), the refusals, the Visual_Ling_Attn module against its own float64 CPU path (eval, train with injected masks, one module for an RGB and a
+depth call, seeded masks, vis input without gradient), an optimizer step between two calls and a non-default stream.
+
+Bound, the project's rule (vla_train_cases.rel): per tensor max|g - g64| / max|g64| <= 1e-5, a reference that is identically zero matched exactly."""
+import ctypes as C
+import functools
+
+import pytest
+import torch
+
+from robo_vln_amd import _lib, train
+from tests import embed_train_cases as ec
+
+pytestmark = pytest.mark.gpu
+
+BOUND = 1e-5
+D = 256
+GUARD = 64
+NAN = float("nan")
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _cu(t):
+    return None if t is None else t.cuda()
+
+
+class _Buf:
+    """n elements pre-filled with a sentinel (NaN, or 0xAB for bytes) with GUARD more behind them"""
+
+    def __init__(self, n, dtype=torch.float32):
+        self.n, self.fill = n, (0xAB if dtype == torch.uint8 else NAN)
+        self.all = torch.full((n + GUARD,), self.fill, dtype=dtype, device="cuda")
+        self.t = self.all[:n]
+
+    def untouched(self, t):
+        return bool(torch.isnan(t).all()) if self.fill != 0xAB else bool((t == 0xAB).all())
+
+    def guard_ok(self):
+        return self.untouched(self.all[self.n:])
+
+    def written(self):
+        return bool(torch.isfinite(self.t).all()) if self.fill != 0xAB else bool((self.t <= 1).all())
+
+
+def _raw_forward(a, keep, p, post, rows, K, work=None, period=None):
+    l = _lib.lib()
+    o = dict(y=_Buf(rows * D), xhat=_Buf(rows * D), rstd=_Buf(rows), gate=_Buf(rows * D, torch.uint8))
+    work = torch.empty(l.hcm_op_embed_ln_work_floats(rows, K), device="cuda") if work is None else work
+    period = (post.shape[0] if post is not None else 0) if period is None else period
+    rc = l.hcm_op_embed_ln_train(*[_p(t) for t in a], _p(keep), p, _p(post), period, _p(o["y"].t), _p(o["xhat"].t), _p(o["rstd"].t), _p(o["gate"].t),
+                                 _p(work), rows, K, None)
+    return rc, o
+
+
+def _raw_backward(a, p, fw, d_y, rows, K, want_dx=True):
+    l = _lib.lib()
+    o = dict(d_pre=_Buf(rows * D), d_x=_Buf(rows * K), d_ln=_Buf(2 * D))
+    work = torch.empty(l.hcm_op_embed_ln_work_floats(rows, K), device="cuda")
+    rc = l.hcm_op_embed_ln_bwd(_p(d_y), _p(a[1]), _p(a[3]), _p(fw["xhat"].t), _p(fw["rstd"].t), _p(fw["gate"].t), p, _p(work), _p(o["d_pre"].t),
+                               _p(o["d_x"].t) if want_dx else None, _p(o["d_ln"].t), rows, K, None)
+    return rc, o
+
+
+@functools.lru_cache(maxsize=None)
+def _gpu(case):
+    """the case through the raw forward (y, xhat, rstd, gate) and through the autograd function (gradients), once"""
+    rows, K, period, p, want_dx = case
+    c = ec.case(*case)
+    a = [t.cuda() for t in c["args"]]
+    rc, fw = _raw_forward(a, _cu(c["keep"]), p, _cu(c["post"]), rows, K)
+    assert rc == 0
+    leaves = [t.cuda().requires_grad_(i > 0 or want_dx) for i, t in enumerate(c["args"])]
+    y = train.embed_ln(*leaves, keep=_cu(c["keep"]), p=p, post=_cu(c["post"]))
+    grads = torch.autograd.grad(y, leaves[0 if want_dx else 1:], c["cot"].cuda())
+    torch.cuda.synchronize()
+    assert all(b.guard_ok() and b.written() for b in fw.values())
+    names = ec.NAMES[0 if want_dx else 1:]
+    return {k: b.t.cpu() for k, b in fw.items()}, y.detach().cpu(), dict(zip(names, [g.cpu() for g in grads]))
+
+
+@pytest.mark.parametrize("case", ec.CASES)
+def test_forward_matches_float64(case):
+    rows = case[0]
+    c = ec.case(*case)
+    fw, y, _ = _gpu(case)
+    assert torch.equal(fw["y"].reshape(rows, D), y)                       # the autograd function returns the raw call's bits
+    worst = {n: ec.rel(fw[n].reshape(c[n + "64"].shape), c[n + "64"], f"{case} {n}") for n in ("y", "xhat", "rstd")}
+    assert max(worst.values()) <= BOUND, worst
+    assert torch.equal(fw["gate"].reshape(rows, D), c["gate"])
+
+
+@pytest.mark.parametrize("case", ec.CASES)
+def test_gradients_match_float64_autograd(case):
+    c = ec.case(*case)
+    _, _, grads = _gpu(case)
+    assert ("d_x" in grads) == case[4]
+    worst = {n: ec.rel(g, c["ref"][n], f"{case} {n}") for n, g in grads.items()}
+    assert all(torch.isfinite(g).all() for g in grads.values())
+    assert max(worst.values()) <= BOUND, worst
+
+
+# ---- raw C ABI ----
+RAW_CASES = [(65, 768, 13, 0.25, False), (130, 768, 65, 0.1, True), (63, 128, 0, 0.25, True)]
+
+
+@pytest.mark.parametrize("case", RAW_CASES)
+def test_raw_abi_bitwise_fully_written_and_guards(case):
+    """two forward and two backward calls on the same inputs are bitwise equal; every output is fully written and the GUARD elements behind each
+    buffer keep the sentinel; with a NULL d_x, d_pre and d_ln carry the bits of the call that computes it and d_x is not touched"""
+    rows, K, period, p, _ = case
+    c = ec.case(*case)
+    a = [t.cuda() for t in c["args"]]
+    keep, post, cot = _cu(c["keep"]), _cu(c["post"]), c["cot"].cuda()
+    rc1, f1 = _raw_forward(a, keep, p, post, rows, K)
+    rc2, f2 = _raw_forward(a, keep, p, post, rows, K)
+    assert rc1 == 0 and rc2 == 0
+    rc1, b1 = _raw_backward(a, p, f1, cot, rows, K)
+    rc2, b2 = _raw_backward(a, p, f2, cot, rows, K)
+    rc3, b3 = _raw_backward(a, p, f1, cot, rows, K, want_dx=False)
+    assert rc1 == 0 and rc2 == 0 and rc3 == 0
+    torch.cuda.synchronize()
+    for n in f1:
+        assert f1[n].written() and f1[n].guard_ok() and torch.equal(f1[n].t, f2[n].t), n
+    for n in b1:
+        assert b1[n].written() and b1[n].guard_ok() and torch.equal(b1[n].t, b2[n].t), n
+    assert torch.equal(b3["d_pre"].t, b1["d_pre"].t) and torch.equal(b3["d_ln"].t, b1["d_ln"].t)
+    assert b3["d_x"].untouched(b3["d_x"].all) and b3["d_pre"].guard_ok() and b3["d_ln"].guard_ok()
+    ref = c["ref"]
+    assert ec.rel(b1["d_x"].t.cpu().reshape(rows, K), ref["d_x"], f"{case} raw d_x") <= BOUND
+    assert ec.rel(b1["d_ln"].t.cpu()[:D], ref["d_gamma"], f"{case} raw d_gamma") <= BOUND
+    assert ec.rel(b1["d_ln"].t.cpu()[D:], ref["d_beta"], f"{case} raw d_beta") <= BOUND
+
+
+def test_null_keep_and_null_post_equal_their_trivial_forms():
+    """NULL keep with p = 0 equals an all-ones mask, NULL post a table of zeros, bit for bit, forward and backward"""
+    case = (130, 768, 65, 0.1, True)
+    rows, K, period = case[:3]
+    c = ec.case(*case)
+    a = [t.cuda() for t in c["args"]]
+    cot, post = c["cot"].cuda(), c["post"].cuda()
+    ones, zeros = torch.ones(rows, D, dtype=torch.uint8, device="cuda"), torch.zeros(period, D, device="cuda")
+    runs = {}
+    for name, keep, tab in (("null_keep", None, post), ("ones_keep", ones, post), ("null_post", None, None), ("zero_post", None, zeros)):
+        rc, fw = _raw_forward(a, keep, 0.0, tab, rows, K)
+        assert rc == 0
+        rc, bw = _raw_backward(a, 0.0, fw, cot, rows, K)
+        assert rc == 0
+        runs[name] = {**fw, **bw}
+    torch.cuda.synchronize()
+    for x, y in (("null_keep", "ones_keep"), ("null_post", "zero_post")):
+        for n in runs[x]:
+            assert torch.equal(runs[x][n].t, runs[y][n].t), (x, n)
+    assert not torch.equal(runs["null_keep"]["y"].t, runs["null_post"]["y"].t)
+
+
+def test_rows_not_a_multiple_of_the_period():
+    """the table's row is row % period whatever the row count: 65 rows over a period of 7, against float64"""
+    rows, K, period = 65, 128, 7
+    (x, w, b, gamma, beta), _, _, _ = ec.make_inputs(rows, K, 0, 0.0, 0)
+    post = train.sinusoid_table(period, D)
+    rc, fw = _raw_forward([t.cuda() for t in (x, w, b, gamma, beta)], None, 0.0, post.cuda(), rows, K)
+    assert rc == 0
+    torch.cuda.synchronize()
+    y64 = train.embed_ln_ref(x.double(), w.double(), b.double(), gamma.double(), beta.double(), post=post)
+    assert ec.rel(fw["y"].t.cpu().reshape(rows, D), y64, "period 7") <= BOUND
+
+
+def test_zero_rows():
+    """rows = 0: HCM_OK, the backward writes zeros to d_ln, nothing else is touched"""
+    a = [t.cuda() for t in ec.make_inputs(1, 64, 0, 0.0, 0)[0]]
+    rc, fw = _raw_forward(a, None, 0.0, None, 0, 64)
+    assert rc == 0
+    rc, bw = _raw_backward(a, 0.0, fw, torch.empty(0, D, device="cuda"), 0, 64)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert all(b.guard_ok() for b in (*fw.values(), *bw.values()))
+    assert torch.equal(bw["d_ln"].t, torch.zeros(2 * D, device="cuda"))
+    x = torch.empty(0, 64, device="cuda", requires_grad=True)
+    leaves = [x] + [t.requires_grad_() for t in a[1:]]
+    y = train.embed_ln(*leaves)
+    assert tuple(y.shape) == (0, D)
+    grads = torch.autograd.grad(y.sum(), leaves)
+    assert tuple(grads[0].shape) == (0, 64) and all(g.abs().max().item() == 0 for g in grads[1:])
+
+
+# ---- refusals: an error code or ValueError, and no launch ----
+def _nothing_written(o):
+    torch.cuda.synchronize()
+    return all(b.untouched(b.all) for b in o.values())
+
+
+@pytest.mark.parametrize("K", [32, 96, 1088])
+def test_unsupported_k_is_refused(K):
+    rows = 3
+    l = _lib.lib()
+    assert l.hcm_op_embed_ln_work_floats(rows, K) == 0
+    g = torch.Generator().manual_seed(0)
+    a = [torch.rand(*s, generator=g).cuda() for s in ((rows, K), (D, K), (D,), (D,), (D,))]
+    work = torch.zeros(l.hcm_op_embed_ln_work_floats(rows, 1024) + 256 * 64, device="cuda")
+    rc, fw = _raw_forward(a, None, 0.0, None, rows, K, work=work)
+    assert rc == -1 and _nothing_written(fw)
+    rc, bw = _raw_backward(a, 0.0, fw, torch.zeros(rows, D, device="cuda"), rows, K)
+    assert rc == -1 and _nothing_written(bw)
+    with pytest.raises(ValueError):
+        train.embed_ln(*a)
+    with pytest.raises(ValueError):
+        train.Visual_Ling_Attn(N=1, vis_in_features=K, ins_in_features=64, d_model=256, h=4, d_ff=256, dropout=0.0).cuda()(
+            torch.rand(1, 2, 64, device="cuda"), torch.rand(1, 2, K, device="cuda"), None, None)
+
+
+def test_bad_p_period_and_alignment_are_refused():
+    rows, K = 5, 256
+    c = ec.case(5, 256, 5, 0.25, True)
+    a = [t.cuda() for t in c["args"]]
+    keep, post = c["keep"].cuda(), c["post"].cuda()
+    rc, fw = _raw_forward(a, keep, 1.0, post, rows, K)
+    assert rc == -1 and _nothing_written(fw)
+    rc, fw = _raw_forward(a, keep, 0.25, post, rows, K, period=0)
+    assert rc == -1 and _nothing_written(fw)
+    big = torch.rand(rows * K + 4, device="cuda")
+    rc, fw = _raw_forward([big[1:1 + rows * K]] + a[1:], keep, 0.25, post, rows, K)        # x four bytes off a 16-byte boundary
+    assert rc == -1 and _nothing_written(fw)
+    rc, ok = _raw_forward(a, keep, 0.25, post, rows, K)
+    assert rc == 0
+    rc, bw = _raw_backward(a, 1.0, ok, c["cot"].cuda(), rows, K)
+    assert rc == -1 and _nothing_written(bw)
+    rc, bw = _raw_backward(a, 0.25, ok, torch.rand(rows * D + 4, device="cuda")[1:1 + rows * D], rows, K)
+    assert rc == -1 and _nothing_written(bw)
+    with pytest.raises(ValueError):
+        train.embed_ln(*a, keep=keep, p=1.0, post=post)
+    with pytest.raises(ValueError):
+        train.embed_ln(*a, keep=keep, p=0.25, post=post[:0])
+
+
+def test_work_buffer_overlapping_an_output_is_refused():
+    rows, K = 5, 256
+    c = ec.case(5, 256, 5, 0.25, True)
+    a = [t.cuda() for t in c["args"]]
+    l = _lib.lib()
+    n = l.hcm_op_embed_ln_work_floats(rows, K)
+    big = torch.full((n + rows * K,), NAN, device="cuda")
+    inside = big[n - 4:]                                                  # starts in the work buffer's last 16 bytes
+    rc, fw = _raw_forward(a, None, 0.0, None, rows, K)
+    assert rc == 0
+    o = dict(y=_Buf(rows * D), xhat=_Buf(rows * D), rstd=_Buf(rows), gate=_Buf(rows * D, torch.uint8))
+    for bad in ("y", "xhat", "rstd"):
+        ptr = {k: _p(inside) if k == bad else _p(b.t) for k, b in o.items()}
+        assert l.hcm_op_embed_ln_train(*[_p(t) for t in a], None, 0.0, None, 0, ptr["y"], ptr["xhat"], ptr["rstd"], ptr["gate"], _p(big), rows, K, None) == -1, bad
+    b = dict(d_pre=_Buf(rows * D), d_x=_Buf(rows * K), d_ln=_Buf(2 * D))
+    for bad in ("d_pre", "d_x", "d_ln"):
+        ptr = {k: _p(inside) if k == bad else _p(t.t) for k, t in b.items()}
+        assert l.hcm_op_embed_ln_bwd(_p(c["cot"].cuda()), _p(a[1]), _p(a[3]), _p(fw["xhat"].t), _p(fw["rstd"].t), _p(fw["gate"].t), 0.0, _p(big), ptr["d_pre"],
+                                     ptr["d_x"], ptr["d_ln"], rows, K, None) == -1, bad
+    assert _nothing_written(o) and _nothing_written(b)
+    assert torch.isnan(big).all()
+
+
+def test_host_tensor_is_refused_at_the_python_level():
+    c = ec.case(5, 256, 5, 0.25, True)
+    a = [t.cuda() for t in c["args"]]
+    for i in (1, 2, 4):
+        mixed = list(a)
+        mixed[i] = c["args"][i]
+        with pytest.raises(ValueError):
+            train.embed_ln(*mixed)
+    with pytest.raises(ValueError):
+        train.embed_ln(*a, keep=c["keep"], p=0.25)                        # keep mask on the host
+    with pytest.raises(ValueError):
+        train.embed_ln(*a, post=c["post"])                                # table on the host
+    with pytest.raises(ValueError):
+        train.embed_ln(*c["args"])
+
+
+# ---- module ----
+MB, ML, MLK = 2, 5, 6
+MCFG = dict(N=2, vis_in_features=256, ins_in_features=768, d_model=256, h=4, d_ff=256)
+
+
+def _module_pair(dropout, seed):
+    torch.manual_seed(seed)
+    m_cpu = train.Visual_Ling_Attn(dropout=dropout, **MCFG).double()
+    with torch.no_grad():
+        for n, prm in m_cpu.named_parameters():                     # LayerNorm parameters and biases off their trivial initial values
+            if "layer_norm" in n or n.endswith("bias"):
+                prm.add_(torch.rand_like(prm) * 0.2 - 0.1)
+    m_gpu = train.Visual_Ling_Attn(dropout=dropout, **MCFG)
+    m_gpu.load_state_dict(m_cpu.state_dict(), strict=True)
+    return m_cpu, m_gpu.cuda()
+
+
+def _inputs(seed, Lk=MLK):
+    g = torch.Generator().manual_seed(seed)
+    u = lambda *s: torch.rand(*s, generator=g) * 2 - 1
+    return u(MB, ML, 768), u(MB, Lk, 256), u(MB, ML, D)
+
+
+def _assert_params_close(m_gpu, m_cpu, what):
+    """every parameter gradient against float64 by the project's rule.  fc_k.bias as in tests/test_vla_layer_train_gpu.py: its exact gradient is
+    zero, float64 autograd leaves rounding noise rather than an identical zero, so it is held to the bound on fc_k.weight's scale."""
+    worst = {}
+    gc = {n: p.grad for n, p in m_cpu.named_parameters()}
+    for n, pg in m_gpu.named_parameters():
+        if n.endswith("enc_att.attention.fc_k.bias"):
+            scale = gc[n[:-4] + "weight"].abs().max().item()
+            assert gc[n].abs().max().item() <= 1e-12 * scale
+            worst[n] = (pg.grad.cpu().double() - gc[n]).abs().max().item() / scale
+            print(f"{what} {n} (on fc_k.weight's scale): {worst[n]:.3e}")
+        else:
+            worst[n] = ec.rel(pg.grad.cpu(), gc[n], f"{what} {n}")
+    assert max(worst.values()) <= BOUND, worst
+
+
+def _keep_to(keep, dev):
+    return tuple(k.to(dev) if torch.is_tensor(k) else tuple(t.to(dev) for t in k) for k in keep)
+
+
+@pytest.mark.parametrize("mode", ["eval", "train"])
+def test_module_matches_its_cpu_path(mode):
+    """Visual_Ling_Attn on the device against its own float64 CPU path with the same state dict (and, in train mode, the same injected keep masks):
+    output, both input gradients and every parameter gradient"""
+    p = 0.25
+    m_cpu, m_gpu = _module_pair(p, 3)
+    x, x2, cot = _inputs(4)
+    keep = None
+    if mode == "train":
+        torch.manual_seed(9)
+        keep = m_cpu.draw_keep(MB, ML, MLK, "cpu")
+    else:
+        m_cpu.eval(), m_gpu.eval()
+    a_c, b_c = x.double().requires_grad_(), x2.double().requires_grad_()
+    out_c = m_cpu(a_c, b_c, None, None, _keep=keep)
+    out_c.backward(cot.double())
+    a_g, b_g = x.cuda().requires_grad_(), x2.cuda().requires_grad_()
+    out_g = m_gpu(a_g, b_g, None, None, _keep=None if keep is None else _keep_to(keep, "cuda"))
+    out_g.backward(cot.cuda())
+    torch.cuda.synchronize()
+    assert ec.rel(out_g.detach().cpu(), out_c.detach(), f"{mode} out") <= BOUND
+    assert ec.rel(a_g.grad.cpu(), a_c.grad, f"{mode} d_input") <= BOUND and ec.rel(b_g.grad.cpu(), b_c.grad, f"{mode} d_input_2") <= BOUND
+    _assert_params_close(m_gpu, m_cpu, mode)
+    assert list(m_gpu._tables) == [(ML, a_g.device)] and m_gpu._tables[(ML, a_g.device)].is_cuda        # one table per (L, device), kept on the device
+
+
+def test_module_shared_between_rgb_and_depth_calls():
+    """one module called twice in one graph (6 RGB-like and 9 depth-like keys), losses summed: the parameter gradients accumulate as in float64,
+    the shared layer_norm's included"""
+    m_cpu, m_gpu = _module_pair(0.0, 5)
+    ins, rgb, c1 = _inputs(6)
+    _, dep, c2 = _inputs(7, Lk=9)
+    loss_c = (m_cpu(ins.double(), rgb.double(), None, None) * c1.double()).sum() + (m_cpu(ins.double(), dep.double(), None, None) * c2.double()).sum()
+    loss_c.backward()
+    loss_g = (m_gpu(ins.cuda(), rgb.cuda(), None, None) * c1.cuda()).sum() + (m_gpu(ins.cuda(), dep.cuda(), None, None) * c2.cuda()).sum()
+    loss_g.backward()
+    torch.cuda.synchronize()
+    _assert_params_close(m_gpu, m_cpu, "shared")
+
+
+def test_module_train_mode_is_seeded_on_the_device():
+    _, m = _module_pair(0.25, 11)
+    m.train()
+    x, x2, _ = (t.cuda() for t in _inputs(12))
+    torch.manual_seed(11)
+    y1 = m(x, x2, None, None)
+    torch.manual_seed(11)
+    y2 = m(x, x2, None, None)
+    torch.manual_seed(12)
+    y3 = m(x, x2, None, None)
+    assert torch.equal(y1, y2) and not torch.equal(y1, y3)
+    torch.manual_seed(11)
+    k1 = m.draw_keep(MB, ML, MLK, "cuda")
+    torch.manual_seed(12)
+    k2 = m.draw_keep(MB, ML, MLK, "cuda")
+    assert k1[0].is_cuda and not torch.equal(k1[0], k2[0]) and not torch.equal(k1[1], k2[1])
+    assert torch.equal(m(x, x2, None, None, _keep=k1), y1)
+    assert torch.equal(m.eval()(x, x2, None, None), m(x, x2, None, None))
+
+
+def test_vis_input_without_gradient_leaves_the_other_gradients_bitwise():
+    _, m = _module_pair(0.25, 13)
+    m.train()
+    x, x2, cot = (t.cuda() for t in _inputs(14))
+    torch.manual_seed(15)
+    keep = m.draw_keep(MB, ML, MLK, "cuda")
+    grads = []
+    for vis_grad in (True, False):
+        m.zero_grad()
+        a, b = x.clone().requires_grad_(), x2.clone().requires_grad_(vis_grad)
+        m(a, b, None, None, _keep=keep).backward(cot)
+        assert (b.grad is not None) == vis_grad
+        grads.append([a.grad.clone()] + [p.grad.clone() for p in m.parameters()])
+    torch.cuda.synchronize()
+    for i, (g1, g2) in enumerate(zip(*grads)):
+        assert torch.equal(g1, g2), i
+
+
+# ---- optimizer step ----
+def test_adam_step_between_two_calls():
+    """Adam (eps 1e-3: with the default eps the first update is lr * sign(g), which hides the gradient's magnitude) between two calls: the second
+    forward sees the updated weights, nothing is cached; the parameters after the second step match the float64 CPU run to 1e-5 relative.
+    lr = 1e-3, the step of tests/test_state_scan_train_gpu.py and tests/test_vla_layer_train_gpu.py: an update lr g / (|g| + eps) moves by at most
+    lr / eps = 1 times a gradient's error, so a parameter inherits the gradient's absolute float32 error, about 1e-6 of the tensor's max|g| (the
+    per-tensor tests above hold it to 1e-5), while the bound allows 1e-5 max|p| with max|p| as small as 1 / sqrt(768) = 0.036 (ins_fc, nn.Linear's
+    default).  That holds only where max|g| is well below max|p|: the loss is therefore the mean over the 2560 outputs, not their sum (through two
+    layers the sum's gradients reach 20 in the float64 run; the mean's, printed below, reach 1e-2, an absolute error near 1e-8 against an
+    allowance of 3.6e-7).  As in the single layer's test this is a check that the optimizer's step reaches the kernels (`moved` against `off`),
+    not a gradient-accuracy check; the per-tensor gradient tests carry that."""
+    m_cpu, m_gpu = _module_pair(0.0, 7)
+    x, x2, cot = _inputs(8)
+    outs = {}
+    for name, m, cv in (("cpu", m_cpu, lambda t: t.double()), ("gpu", m_gpu, lambda t: t.cuda())):
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3, eps=1e-3)
+        outs[name] = []
+        for _ in range(2):
+            opt.zero_grad()
+            out = m(cv(x), cv(x2), None, None)
+            (out * cv(cot)).mean().backward()
+            opt.step()
+            outs[name].append(out.detach().cpu().double())
+    torch.cuda.synchronize()
+    print("adam: float64 max|g| per tensor from", min(p.grad.abs().max().item() for p in m_cpu.parameters()), "to", max(p.grad.abs().max().item() for p in m_cpu.parameters()))
+    moved = (outs["cpu"][1] - outs["cpu"][0]).abs().max().item()
+    off = [(outs["gpu"][i] - outs["cpu"][i]).abs().max().item() / outs["cpu"][i].abs().max().item() for i in range(2)]
+    print(f"adam: the step moved the output by {moved:.3e}; device against float64 before / after the step {off[0]:.3e} / {off[1]:.3e} (relative)")
+    assert off[0] <= BOUND and off[1] <= BOUND
+    assert moved >= 50 * off[1] * outs["cpu"][1].abs().max().item()       # the step's own effect exceeds the error many times: the device saw the new weights
+    for (n, pg), (_, pc) in zip(m_gpu.named_parameters(), m_cpu.named_parameters()):
+        e = (pg.detach().cpu().double() - pc.detach()).abs().max().item() / pc.detach().abs().max().item()
+        print(f"adam {n}: {e:.3e}")
+        assert e <= 1e-5, (n, e)
+
+
+# ---- non-default stream ----
+def test_non_default_stream_bitwise():
+    case = (130, 768, 65, 0.1, True)
+    c = ec.case(*case)
+    _, y0, grads0 = _gpu(case)
+    s = torch.cuda.Stream()
+    leaves = [t.cuda().requires_grad_() for t in c["args"]]
+    keep, post, cot = c["keep"].cuda(), c["post"].cuda(), c["cot"].cuda()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        y = train.embed_ln(*leaves, keep=keep, p=c["p"], post=post)
+        grads = torch.autograd.grad(y, leaves, cot)
+    s.synchronize()
+    assert torch.equal(y.detach().cpu(), y0)
+    for n, gt in zip(ec.NAMES, grads):
+        assert torch.equal(gt.cpu(), grads0[n]), n
