@@ -740,6 +740,44 @@ int hcm_op_embed_ln_train(const float* x, const float* w, const float* b, const 
 int hcm_op_embed_ln_bwd(const float* d_y, const float* w, const float* gamma, const float* xhat, const float* rstd, const uint8_t* gate, float p,
                         float* work, float* d_pre, float* d_x, float* d_ln, int rows, int K, void* stream);
 
+/* The instruction encoder's packed scan (InstructionEncoder, models/encoders/instruction_encoder.py:70-92) in float32 with what a backward pass
+ * needs, and its reverse-time scan (csrc/instr_scan_train.hip): nn.LSTM (HCM_LSTM, gates i,f,g,o) or nn.GRU (HCM_GRU, gates r,z,n), one layer,
+ * dirs = 1 or 2 directions, hidden 256, any B, L >= 1.  Row b is active at tokens t < lengths[b] (clamped to [0, L]) as in a packed sequence: the
+ * reverse direction starts at the row's own last token, and a row of length 0 yields zeros everywhere and contributes nothing.  With G = 4 / 3:
+ *   pre (dirs, B*L, G*256) = emb W_ih^T + bias per direction (LSTM: b_ih + b_hh; GRU: b_ih + (b_hr, b_hz, 0)); b_hn (dirs, 256): GRU's b_hn, which
+ *   stays inside r * (W_hn h + b_hn) (NULL for LSTM); w_hh (dirs, G*256, 256) as torch stores weight_hh_l0 [/ _reverse]; lengths (B,) int32; all
+ *   on the device.
+ * hcm_op_instr_scan_train, ONE scan launch behind a weight pack, writes (owned by the caller)
+ *   out (B, L, dirs*256): h_t of every active token, zeros at inactive ones -- the per-token output, and the left operand of dW_hh;
+ *   final (B, 256), may be NULL: the forward direction's h at each row's own last token (final_state_only);
+ *   gates (dirs, B*L, 4*256): the post-activation gates of every active token -- LSTM i,f,g,o; GRU r,z,n and hn = W_hn h + b_hn;
+ *   c_seq (dirs, B*L, 256): c_t of every active token, LSTM only (NULL for GRU).  gates and c_seq are not written at inactive tokens.
+ *   With the same weights the results equal, bit for bit, those of the engines' one-launch scans (hcm_op_instr_scan_infer).
+ * hcm_op_instr_scan_bwd, ONE scan launch behind a weight pack, takes the cotangents d_out (B, L, dirs*256) and / or d_final (B, 256) -- either
+ *   may be NULL; d_final enters at t = lengths[b] - 1 of the forward direction; a cotangent at an inactive token is not read -- and gates, c_seq,
+ *   out, w_hh, lengths as the forward had them, and writes d_pre (dirs, B*L, G*256), the gradient with respect to `pre`, and for GRU
+ *   d_gh (dirs, B*L, 3*256) = [da_r, da_z, da_n * r], the h-side gate gradients (NULL for LSTM, where they are d_pre); exact zeros at inactive
+ *   tokens.  With h'[b, t] = out[b, t - 1] in the forward and out[b, t + 1] in the reverse direction (zero at each end), per direction:
+ *   dW_ih = d_pre^T emb, db_ih = sum d_pre, dW_hh = d_gh^T h', db_hh = sum d_gh, d_emb = d_pre W_ih -- dense reductions left to the caller.
+ * work: hcm_op_instr_scan_work_floats(B, L, dirs, rnn_type) floats (0 for unsupported arguments) owned by the caller, serving either op: W_hh in
+ *   the launch's order ([k][unit][4 gates] forward, [row quad][k][4 rows] reverse), packed on `stream` in every call -- nothing is cached, weights
+ *   change at every optimizer step.  No output may overlap it.  Float tensors and work must be 16-byte aligned, lengths 4-byte aligned.
+ * HCM_ERR_ARG with a message (hcm_last_error(NULL)), never a launch: hidden != 256, dirs outside {1, 2}, a NULL required pointer, an output
+ *   overlapping work, a misaligned pointer.
+ * The ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible. */
+int64_t hcm_op_instr_scan_work_floats(int B, int L, int dirs, int rnn_type);
+int hcm_op_instr_scan_train(const float* pre, const float* w_hh, const float* b_hn, const int32_t* lengths, float* out, float* final, float* gates,
+                            float* c_seq, float* work, int B, int L, int hidden, int dirs, int rnn_type, void* stream);
+int hcm_op_instr_scan_bwd(const float* d_out, const float* d_final, const float* gates, const float* c_seq, const float* out, const float* w_hh,
+                          const int32_t* lengths, float* work, float* d_pre, float* d_gh, int B, int L, int hidden, int dirs, int rnn_type,
+                          void* stream);
+/* A comparison hook for the tests, not an operator to build on (it checks sizes and NULLs, not alignment or overlap): the engines' existing
+ * one-launch inference scans on their own (csrc/elementwise.hip), to hold hcm_op_instr_scan_train against: pre, b_hn and
+ * lengths as above, wt (dirs, 256, 256, 4) = W_hh already in the forward order (what hcm_op_instr_scan_train leaves in `work`).  final_only != 0:
+ * instr_final_scan_kernel, dirs = 1, out (B, 256); otherwise instr_lstm_scan_kernel, LSTM only, out (B, L, dirs*256). */
+int hcm_op_instr_scan_infer(const float* pre, const float* wt, const float* b_hn, const int32_t* lengths, float* out, int B, int L, int hidden, int dirs,
+                            int rnn_type, int final_only, void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

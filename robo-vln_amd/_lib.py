@@ -147,6 +147,10 @@ EXPORTS = {
     "hcm_op_embed_ln_work_floats": (C.c_int64, [C.c_int] * 2),
     "hcm_op_embed_ln_train": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p]),
     "hcm_op_embed_ln_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p]),
+    "hcm_op_instr_scan_work_floats": (C.c_int64, [C.c_int] * 4),
+    "hcm_op_instr_scan_train": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 5 + [C.c_void_p]),
+    "hcm_op_instr_scan_bwd": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_void_p]),
+    "hcm_op_instr_scan_infer": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
     "hcm_op_feat_ingest": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),

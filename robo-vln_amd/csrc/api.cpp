@@ -1842,6 +1842,71 @@ int hcm_op_embed_ln_bwd(const float* d_y, const float* w, const float* gamma, co
     return op_rc(launch_embed_train_bwd(t, (hipStream_t)stream));
 }
 
+int64_t hcm_op_instr_scan_work_floats(int B, int L, int dirs, int rnn_type) {
+    if (!instr_scan_train_ok(B, L, 256, dirs) || (rnn_type != HCM_LSTM && rnn_type != HCM_GRU)) return 0;
+    return (int64_t)instr_scan_work_floats(dirs);
+}
+
+static int instr_arg_err(const char* what) {
+    g_create_err = std::string("instruction scan: ") + what;
+    return HCM_ERR_ARG;
+}
+// hidden size, directions and cell kind of the three instruction-scan ops
+static int instr_scan_dims(int B, int L, int hidden, int dirs, int rnn_type) {
+    if (hidden != 256) return instr_arg_err("hidden size must be 256 (256 units x 4 partitions = 1024 threads)");
+    if (dirs != 1 && dirs != 2) return instr_arg_err("dirs must be 1 or 2");
+    if (rnn_type != HCM_LSTM && rnn_type != HCM_GRU) return instr_arg_err("rnn_type must be HCM_LSTM or HCM_GRU");
+    if (B < 1 || L < 1) return instr_arg_err("B and L must be at least 1");
+    return HCM_OK;
+}
+
+int hcm_op_instr_scan_train(const float* pre, const float* w_hh, const float* b_hn, const int32_t* lengths, float* out, float* final, float* gates,
+                            float* c_seq, float* work, int B, int L, int hidden, int dirs, int rnn_type, void* stream) {
+    const int rc = instr_scan_dims(B, L, hidden, dirs, rnn_type);
+    if (rc != HCM_OK) return rc;
+    const bool gru = rnn_type == HCM_GRU;
+    if (!pre || !w_hh || !lengths || !out || !gates || !work) return instr_arg_err("a required pointer is NULL");
+    if (gru && !b_hn) return instr_arg_err("b_hn is required for GRU");
+    if ((c_seq == nullptr) != gru) return instr_arg_err("c_seq is required for LSTM and must be NULL for GRU");
+    if (!vla_train_aligned({pre, w_hh, b_hn, out, final, gates, c_seq, work}, {lengths})) return instr_arg_err("float tensors must be 16-byte aligned, lengths 4-byte");
+    const size_t BL = (size_t)B * L, H = 256;
+    if (vla_train_in_work(work, instr_scan_work_floats(dirs), {{out, BL * dirs * H}, {final, (size_t)B * H}, {gates, dirs * BL * 4 * H}, {c_seq, dirs * BL * H}}))
+        return instr_arg_err("an output overlaps work");
+    return op_rc(launch_instr_scan_train(pre, w_hh, b_hn, lengths, out, final, gates, c_seq, work, B, L, hidden, dirs, gru ? 1 : 0, (hipStream_t)stream));
+}
+
+int hcm_op_instr_scan_bwd(const float* d_out, const float* d_final, const float* gates, const float* c_seq, const float* out, const float* w_hh,
+                          const int32_t* lengths, float* work, float* d_pre, float* d_gh, int B, int L, int hidden, int dirs, int rnn_type,
+                          void* stream) {
+    const int rc = instr_scan_dims(B, L, hidden, dirs, rnn_type);
+    if (rc != HCM_OK) return rc;
+    const bool gru = rnn_type == HCM_GRU;
+    if (!gates || !out || !w_hh || !lengths || !work || !d_pre) return instr_arg_err("a required pointer is NULL");
+    if ((c_seq == nullptr) != gru) return instr_arg_err("c_seq is required for LSTM and must be NULL for GRU");
+    if ((d_gh == nullptr) == gru) return instr_arg_err("d_gh is required for GRU and must be NULL for LSTM");
+    if (!vla_train_aligned({d_out, d_final, gates, c_seq, out, w_hh, work, d_pre, d_gh}, {lengths})) return instr_arg_err("float tensors must be 16-byte aligned, lengths 4-byte");
+    const size_t n = (size_t)dirs * B * L * (gru ? 3 : 4) * 256;
+    if (vla_train_in_work(work, instr_scan_work_floats(dirs), {{d_pre, n}, {d_gh, n}})) return instr_arg_err("an output overlaps work");
+    return op_rc(launch_instr_scan_bwd(d_out, d_final, gates, c_seq, out, w_hh, lengths, work, d_pre, d_gh, B, L, hidden, dirs, gru ? 1 : 0,
+                                       (hipStream_t)stream));
+}
+
+int hcm_op_instr_scan_infer(const float* pre, const float* wt, const float* b_hn, const int32_t* lengths, float* out, int B, int L, int hidden, int dirs,
+                            int rnn_type, int final_only, void* stream) {
+    const int rc = instr_scan_dims(B, L, hidden, dirs, rnn_type);
+    if (rc != HCM_OK) return rc;
+    const bool gru = rnn_type == HCM_GRU;
+    if (!pre || !wt || !lengths || !out || (gru && !b_hn)) return instr_arg_err("a required pointer is NULL");
+    if (final_only) {
+        if (dirs != 1) return instr_arg_err("the final-state scan has one direction");
+        return op_rc(launch_instr_final_scan(pre, wt, b_hn, lengths, out, B, B, L, hidden, gru ? 1 : 0, hidden, (hipStream_t)stream));
+    }
+    if (gru) return instr_arg_err("the engines have no one-launch full-output GRU scan");
+    const size_t BL = (size_t)B * L;
+    return op_rc(launch_instr_lstm_scan(pre, dirs == 2 ? pre + BL * 4 * hidden : nullptr, wt, dirs == 2 ? wt + (size_t)4 * hidden * hidden : nullptr, lengths,
+                                        out, B, L, hidden, dirs, dirs * hidden, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

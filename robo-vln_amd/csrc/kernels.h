@@ -366,6 +366,18 @@ hipError_t launch_instr_lstm_scan(const float* pre0, const float* pre1, const fl
 // H == 256.  A workgroup runs max(length) of its own samples steps, not L.
 hipError_t launch_instr_final_scan(const float* pre, const float* wt, const float* bhn, const int* lengths, float* out, int Bi, int rows, int L, int H,
                                    int gru, int ld_out, hipStream_t s);
+// The differentiable instruction encoder (instr_scan_train.hip): the packed scan above with what a backward pass needs, and its reverse scan; ONE
+// launch each behind a weight pack on the stream, H == 256, dirs 1 or 2, any B, L >= 1.  Tensors with a leading `dirs` are stacked per direction:
+//   pre (dirs, B*L, G*H), w_hh (dirs, G*H, H) as torch stores it, bhn (dirs, H) (GRU), gates (dirs, B*L, 4H), cseq (dirs, B*L, H) (LSTM; null for GRU),
+//   d_pre (dirs, B*L, G*H), d_gh (dirs, B*L, 3H) (GRU; null for LSTM); out / d_out (B, L, dirs*H); fin / d_fin (B, H), forward direction, may be null.
+// work: instr_scan_work_floats(dirs) floats, W_hh in the launch's order.  No allocation, no host copy, no synchronisation.
+bool instr_scan_train_ok(int B, int L, int H, int dirs);
+size_t instr_scan_work_floats(int dirs);
+int instr_scan_train_sb(int B, int dirs);                  // samples per workgroup the two launches choose
+hipError_t launch_instr_scan_train(const float* pre, const float* w_hh, const float* bhn, const int* lengths, float* out, float* fin, float* gates,
+                                   float* cseq, float* work, int B, int L, int H, int dirs, int gru, hipStream_t s);
+hipError_t launch_instr_scan_bwd(const float* d_out, const float* d_fin, const float* gates, const float* cseq, const float* out, const float* w_hh,
+                                 const int* lengths, float* work, float* d_pre, float* d_gh, int B, int L, int H, int dirs, int gru, hipStream_t s);
 // dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
 // out[r][0..H) = all[b][max(len_b, 1) - 1][0..H) with b = (Bi == 1 ? 0 : r): the last active step of an all-outputs scan (len_b == 0: zeros)
 hipError_t launch_gather_last(const float* all, const int* lengths, float* out, int Bi, int rows, int L, int H, int ld_out, hipStream_t s);

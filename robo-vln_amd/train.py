@@ -14,7 +14,12 @@ pure-torch restatement (CPU path of the module, and what the tests compare again
 Differentiable Visual_Ling_Attn: the reference's whole cross-modal encoder (transformer.py:250-282).  Its prologue -- Linear, ReLU, dropout, the
 shared LayerNorm, and for the instruction half the sinusoid table -- is `embed_ln` on the float32 HIP kernels of csrc/embed_train.hip, one launch
 forward and one backward per half; `embed_ln_ref` is the pure-torch restatement, `sinusoid_table` the reference's table, `Visual_Ling_Attn` the
-drop-in module around `InterModuleAttnLayer`."""
+drop-in module around `InterModuleAttnLayer`.
+
+Differentiable instruction encoder: the reference's InstructionEncoder (models/encoders/instruction_encoder.py:70-92), a packed nn.LSTM / nn.GRU
+with hidden size 256 in one or two directions, with the whole scan forward and the whole scan backward one launch each (csrc/instr_scan_train.hip)
+and the lengths read on the device.  `instr_scan` is the autograd function, `instr_encoder_ref` the pure-torch restatement, `InstructionEncoder`
+the drop-in module."""
 import ctypes as C
 import math
 
@@ -25,6 +30,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 SCAN_HIDDEN = 512
+INSTR_HIDDEN = 256
 VLA_D_MODEL, VLA_HEADS, VLA_MAX_KEYS, VLA_MAX_D_FF = 256, 4, 64, 1024
 EMBED_K_STEP, EMBED_MAX_K = 64, 1024
 
@@ -540,3 +546,225 @@ class Visual_Ling_Attn(nn.Module):
         for layer, k in zip(self.layers, keep[2:]):
             out = layer(inp, out, None, None, _keep=k)
         return out
+
+
+def _instr_params(params):
+    """params: per direction (weight_ih, weight_hh, bias_ih, bias_hh), one or two directions -> (list of 4-tuples, H, G, E)"""
+    params = [tuple(p) for p in params]
+    if len(params) not in (1, 2) or any(len(p) != 4 for p in params):
+        raise ValueError(f"instruction scan: params holds (weight_ih, weight_hh, bias_ih, bias_hh) for one or two directions, got {len(params)} entries")
+    w_ih, w_hh = params[0][0], params[0][1]
+    if w_hh.dim() != 2 or w_ih.dim() != 2 or w_hh.shape[1] < 1 or w_hh.shape[0] % w_hh.shape[1] or w_hh.shape[0] // w_hh.shape[1] not in (3, 4):
+        raise ValueError(f"instruction scan: weight_hh must be (G*H, H) with G = 4 (LSTM) or 3 (GRU), got {tuple(w_hh.shape)}")
+    H, G, E = w_hh.shape[1], w_hh.shape[0] // w_hh.shape[1], w_ih.shape[1]
+    for d, p in enumerate(params):
+        for name, t, shape in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), p, ((G * H, E), (G * H, H), (G * H,), (G * H,))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"instruction scan: {name} of direction {d} has shape {tuple(t.shape)}, expected {shape}")
+    return params, H, G, E
+
+
+def instr_encoder_ref(embedded, lengths, params, final_state_only):
+    """Pure-torch restatement of the packed instruction scan for any size, dtype and device: a per-token cell loop with each row frozen beyond its
+    length -- row b is active at tokens t < lengths[b]; the forward direction walks t = 0 .. L-1 and the reverse t = L-1 .. 0, each from the zero
+    state, and an inactive token neither changes the state nor produces output.  That is pack_padded_sequence(enforce_sorted=False) -> nn.LSTM /
+    nn.GRU -> pad_packed_sequence(total_length=L) without the packing.  embedded (B, L, E), lengths (B,), params as instr_scan.  Returns
+    (B, L, dirs*H), zeros at inactive tokens, or with final_state_only (B, H): the forward direction's state at each row's own last token (zeros
+    for a row of length 0)."""
+    params, H, G, _ = _instr_params(params)
+    if final_state_only and len(params) != 1:
+        raise ValueError("instruction scan: final_state_only serves one direction")
+    B, L = embedded.shape[0], embedded.shape[1]
+    lstm = G == 4
+    outs, fin = [], None
+    for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(params):
+        gi_all = torch.nn.functional.linear(embedded, w_ih, b_ih)
+        h = embedded.new_zeros(B, H)
+        c = embedded.new_zeros(B, H)
+        seq = [None] * L
+        for t in (range(L - 1, -1, -1) if d else range(L)):
+            act = (t < lengths).reshape(B, 1)
+            gi, gh = gi_all[:, t], torch.nn.functional.linear(h, w_hh, b_hh)
+            if lstm:
+                i, f, g, o = (gi + gh).chunk(4, 1)
+                c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+                h2 = torch.sigmoid(o) * torch.tanh(c2)
+                c = torch.where(act, c2, c)
+            else:
+                (i_r, i_z, i_n), (h_r, h_z, h_n) = gi.chunk(3, 1), gh.chunk(3, 1)
+                r, z = torch.sigmoid(i_r + h_r), torch.sigmoid(i_z + h_z)
+                h2 = (1 - z) * torch.tanh(i_n + r * h_n) + z * h
+            h = torch.where(act, h2, h)
+            seq[t] = torch.where(act, h2, torch.zeros_like(h2))
+        outs.append(torch.stack(seq, 1))
+        if d == 0:
+            fin = h
+    return fin if final_state_only else torch.cat(outs, 2)
+
+
+class _InstrScan(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, embedded, lengths, final_state_only, *flat):
+        params, H, G, E = _instr_params([flat[i:i + 4] for i in range(0, len(flat), 4)])
+        if not embedded.is_cuda:
+            raise ValueError("instr_scan runs on the device; CPU tensors go through instr_encoder_ref")
+        for d, p in enumerate(params):
+            for name, t in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), p):
+                if t.device != embedded.device:       # the kernels take raw pointers: a host pointer would fault on the device
+                    raise ValueError(f"instr_scan: {name} of direction {d} is on {t.device}, embedded on {embedded.device}")
+        if lengths.device != embedded.device:
+            raise ValueError(f"instr_scan: lengths is on {lengths.device}, embedded on {embedded.device}")
+        if H != INSTR_HIDDEN:
+            raise ValueError(f"instr_scan serves hidden size {INSTR_HIDDEN} (256 units x 4 partitions = 1024 threads), got weight_hh {tuple(params[0][1].shape)}")
+        dirs, lstm = len(params), G == 4
+        if final_state_only and dirs != 1:
+            raise ValueError("instr_scan: final_state_only serves one direction")
+        if embedded.dim() != 3 or embedded.shape[0] < 1 or embedded.shape[1] < 1 or embedded.shape[2] != E:
+            raise ValueError(f"instr_scan takes embedded (B >= 1, L >= 1, {E}), got {tuple(embedded.shape)}")
+        B, L = embedded.shape[0], embedded.shape[1]
+        if tuple(lengths.shape) != (B,) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError(f"instr_scan: lengths must be an integer tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+        dev = embedded.device
+        emb = _f32c(embedded).reshape(B * L, E)
+        len32 = lengths.detach().to(torch.int32).contiguous()
+        params = [tuple(_f32c(t) for t in p) for p in params]
+        # the convention of include/hcm.h: LSTM adds both biases to `pre`; GRU adds (b_hr, b_hz, 0) and hands b_hn to the kernel
+        pre = torch.empty(dirs, B * L, G * H, device=dev)
+        for d, (w_ih, _, b_ih, b_hh) in enumerate(params):
+            bias = b_ih + b_hh if lstm else b_ih + torch.cat([b_hh[:2 * H], b_hh.new_zeros(H)])
+            torch.addmm(bias, emb, w_ih.t(), out=pre[d])
+        w_hh = torch.stack([p[1] for p in params])
+        b_hn = None if lstm else torch.stack([p[3][2 * H:] for p in params])
+        out = torch.empty(B, L, dirs * H, device=dev)
+        fin = torch.empty(B, H, device=dev) if final_state_only else None
+        gates = torch.empty(dirs, B * L, 4 * H, device=dev)
+        c_seq = torch.empty(dirs, B * L, H, device=dev) if lstm else None
+        kind = _lib.HCM_LSTM if lstm else _lib.HCM_GRU
+        work = torch.empty(_lib.lib().hcm_op_instr_scan_work_floats(B, L, dirs, kind), device=dev)
+        _lib.check(_lib.lib().hcm_op_instr_scan_train(_ptr(pre), _ptr(w_hh), _ptr(b_hn), _ptr(len32), _ptr(out), _ptr(fin), _ptr(gates), _ptr(c_seq),
+                                                      _ptr(work), B, L, H, dirs, kind, _stream()))
+        ctx.save_for_backward(emb, len32, w_hh, out, gates, c_seq, *(p[0] for p in params))
+        ctx.dims = (B, L, E, dirs, lstm, bool(final_state_only))
+        return fin if final_state_only else out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        emb, len32, w_hh, out, gates, c_seq, *w_ih = ctx.saved_tensors
+        B, L, E, dirs, lstm, final = ctx.dims
+        H, G, dev = INSTR_HIDDEN, 4 if lstm else 3, emb.device
+        d = _f32c(d)
+        d_pre = torch.empty(dirs, B * L, G * H, device=dev)
+        d_gh = None if lstm else torch.empty(dirs, B * L, G * H, device=dev)
+        kind = _lib.HCM_LSTM if lstm else _lib.HCM_GRU
+        work = torch.empty(_lib.lib().hcm_op_instr_scan_work_floats(B, L, dirs, kind), device=dev)
+        _lib.check(_lib.lib().hcm_op_instr_scan_bwd(None if final else _ptr(d), _ptr(d) if final else None, _ptr(gates), _ptr(c_seq), _ptr(out), _ptr(w_hh),
+                                                    _ptr(len32), _ptr(work), _ptr(d_pre), _ptr(d_gh), B, L, H, dirs, kind, _stream()))
+        if lstm:
+            d_gh = d_pre
+        need = ctx.needs_input_grad
+        grads = []
+        for k in range(dirs):
+            n = need[3 + 4 * k:7 + 4 * k]
+            dw_hh = None
+            if n[1]:
+                # h' is `out` shifted by one token against the direction (zero at each end, and `out` is zero at inactive tokens)
+                g3, o3 = d_gh[k].view(B, L, G * H), out[:, :, k * H:(k + 1) * H]
+                if L == 1:
+                    dw_hh = torch.zeros(G * H, H, device=dev)
+                elif k == 0:
+                    dw_hh = g3[:, 1:].reshape(-1, G * H).t() @ o3[:, :-1].reshape(-1, H)
+                else:
+                    dw_hh = g3[:, :-1].reshape(-1, G * H).t() @ o3[:, 1:].reshape(-1, H)
+            grads += [d_pre[k].t() @ emb if n[0] else None, dw_hh, d_pre[k].sum(0) if n[2] else None, d_gh[k].sum(0) if n[3] else None]
+        d_emb = None
+        if need[0]:
+            d_emb = d_pre[0] @ w_ih[0]
+            if dirs == 2:
+                d_emb = torch.addmm(d_emb, d_pre[1], w_ih[1])
+            d_emb = d_emb.reshape(B, L, E)
+        return (d_emb, None, None, *grads)
+
+
+def instr_scan(embedded, lengths, params, final_state_only):
+    """The packed instruction scan (hidden 256, one layer, float32, on the device) with gradients to `embedded` and the parameters: embedded
+    (B, L, E), lengths (B,) integer on the device (row b is active at tokens t < lengths[b]; nothing is read back to the host), params per
+    direction torch's (weight_ih, weight_hh, bias_ih, bias_hh) -- one entry, or two for a bidirectional encoder (the second is the `_reverse`
+    set); LSTM or GRU is read off weight_hh's row count.  Returns (B, L, dirs*256) with zeros at inactive tokens, or with final_state_only
+    (one direction) the (B, 256) state at each row's own last token.  The semantics are instr_encoder_ref's.
+
+    Forward: `pre` by torch.addmm over all B*L rows, then hcm_op_instr_scan_train, one launch for the whole scan on the current stream, which
+    saves the gates, c_t and h_t.  Backward: hcm_op_instr_scan_bwd, one launch for the whole reverse scan, gives d_pre and d_gh; the dense
+    reductions behind it -- dW_ih = d_pre.T @ emb, db_ih = d_pre.sum(0), dW_hh = d_gh.T @ h', db_hh = d_gh.sum(0) with h' the output shifted by
+    one token against the direction and d_gh = d_pre for LSTM -- stay in torch, the split state_scan made; d_emb = d_pre @ W_ih is computed
+    only when `embedded` requires a gradient (with frozen embeddings it never runs).  Nothing is cached between calls: the weights are packed
+    for the kernels on the device in every call."""
+    return _InstrScan.apply(embedded, lengths, bool(final_state_only), *(t for p in params for t in p))
+
+
+class InstructionEncoder(nn.Module):
+    """Drop-in for the reference's InstructionEncoder (models/encoders/instruction_encoder.py): the reference's state-dict keys --
+    embedding_layer.weight and encoder_rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0, with the _reverse suffix for the second direction -- in a
+    real nn.Embedding and a real nn.LSTM / nn.GRU (storage and initialisation only), so load_state_dict takes a reference checkpoint's keys
+    unchanged.  Takes the reference's config object (vocab_size, embedding_size, hidden_size, rnn_type, bidirectional, final_state_only,
+    fine_tune_embeddings) or the same names as keyword arguments, which win.  `embeddings=` (vocab, E) stands in for the reference's file load:
+    the table is nn.Embedding.from_pretrained(embeddings, freeze=not fine_tune_embeddings), as with use_pretrained_embeddings; without it the
+    table is a trainable nn.Embedding(vocab_size, embedding_size, padding_idx=0), as in the reference.
+
+    forward(instruction) takes (B, L) token ids, 0 = padding, and derives lengths = (instruction != 0).sum(1) on the device: nothing is read
+    back to the host.  With final_state_only it returns (B, hidden); otherwise (B, D, L), D = hidden * directions: the reference's
+    (B, D, max(lengths)) zero-padded to L -- trimming to max(lengths) would need the host read this module exists to remove.  CMANet masks
+    all-zero columns (cma.py:273), so the model's outputs are unchanged.
+
+    Device tensors go through instr_scan (hidden size 256; anything else raises), CPU tensors through instr_encoder_ref.  final_state_only
+    together with bidirectional is refused: the reference returns a (2, B, H) tensor there that no model can consume."""
+
+    NAMES = ("vocab_size", "embedding_size", "hidden_size", "rnn_type", "bidirectional", "final_state_only", "fine_tune_embeddings")
+
+    def __init__(self, config=None, embeddings=None, **kw):
+        super().__init__()
+        unknown = set(kw) - set(self.NAMES)
+        if unknown:
+            raise TypeError(f"InstructionEncoder: unknown arguments {sorted(unknown)}")
+        given = dict(fine_tune_embeddings=False)
+        if embeddings is not None:
+            given.update(vocab_size=embeddings.shape[0], embedding_size=embeddings.shape[1])
+        given.update({n: getattr(config, n) for n in self.NAMES if hasattr(config, n)})
+        given.update(kw)
+        missing = [n for n in self.NAMES if n not in given]
+        if missing:
+            raise TypeError(f"InstructionEncoder: missing {missing}")
+        vocab, E, H, rnn_type, bidir, final, fine_tune = (given[n] for n in self.NAMES)
+        if rnn_type not in ("GRU", "LSTM"):
+            raise ValueError(f"rnn_type must be GRU or LSTM, got {rnn_type!r}")
+        if final and bidir:
+            raise ValueError("InstructionEncoder: final_state_only with bidirectional is refused (the reference returns a (2, B, H) tensor no model consumes)")
+        if embeddings is not None:
+            if tuple(embeddings.shape) != (vocab, E):
+                raise ValueError(f"InstructionEncoder: embeddings has shape {tuple(embeddings.shape)}, expected {(vocab, E)}")
+            self.embedding_layer = nn.Embedding.from_pretrained(embeddings.detach().clone().float(), freeze=not fine_tune)
+        else:
+            self.embedding_layer = nn.Embedding(num_embeddings=vocab, embedding_dim=E, padding_idx=0)
+        self.encoder_rnn = getattr(nn, rnn_type)(input_size=E, hidden_size=H, bidirectional=bool(bidir))
+        self.rnn_type, self.hidden_size, self.bidir, self.final_state_only = rnn_type, H, bool(bidir), bool(final)
+
+    @property
+    def output_size(self):
+        return self.hidden_size * (2 if self.bidir else 1)
+
+    def _params(self):
+        return [tuple(getattr(self.encoder_rnn, f"{n}_l0{sfx}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                for sfx in (("", "_reverse") if self.bidir else ("",))]
+
+    def forward(self, instruction):
+        if instruction.dim() != 2:
+            raise ValueError(f"InstructionEncoder takes instruction (B, L), got {tuple(instruction.shape)}")
+        lengths = (instruction != 0).sum(1)
+        embedded = self.embedding_layer(instruction.long())
+        if not instruction.is_cuda:
+            y = instr_encoder_ref(embedded, lengths, self._params(), self.final_state_only)
+        else:
+            if self.hidden_size != INSTR_HIDDEN:
+                raise ValueError(f"on the device InstructionEncoder serves hidden_size {INSTR_HIDDEN} (got {self.hidden_size})")
+            y = instr_scan(embedded, lengths, self._params(), self.final_state_only)
+        return y if self.final_state_only else y.permute(0, 2, 1)
