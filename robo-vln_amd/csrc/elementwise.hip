@@ -2,6 +2,7 @@
 // embeddings, recurrent cells + heads, small glue.  All are HBM/L2-bound: 16-byte vector accesses,
 // grid-stride loops, wave64 reductions.
 #include <cstdlib>
+#include <type_traits>
 #include "kernels.h"
 #include "dev.h"
 
@@ -413,6 +414,15 @@ hipError_t launch_fill_cols(const float* tab, void* y, int dt, int B, int S, int
 // squares in registers (a thread always sees the same 16-byte channel chunk), wave-shuffle + LDS reduce to per-group
 // mean / rstd in f32; pass 2 re-reads the slab (L2-resident: HW*CS*2 B <= 64 KB for every layer of the trunk),
 // normalises, adds the residual, applies ReLU and stores.  No atomics, no memset, no stats buffer.
+// float32 storage (gn_pivot<T>): the sums run over x - K, K = the group's first element of the sample (read before anything is stored), so that
+// var = q / n - (a / n)^2 cancels against |mean - K|, not against |mean| -- E[x^2] - mean^2 loses (mean / std)^2 ulps.  For a conv output whose
+// first element is an ordinary draw |mean - K| <~ 2 std.  Worst case: that element is itself an outlier (a spike at pixel 0 of a sparse map); then
+// |mean - K| / std reaches sqrt(n) -- 45 at 2 048 elements, 362 at 131 072 -- and the shifted sums cancel worse than the plain ones would have
+// (tests/test_norm_conditioning_gpu.py, test_groupnorm_float32_outlier_in_the_pivot_element: a relative error of 1.5 d 2^-24 (1 + r^2) at most,
+// d the depth of the summation).  Groups with zero-padded channels (cg_true) keep K = 0 and so the plain one-pass sums: the padding would enter
+// the shifted ones.  16-bit storage keeps the plain sums: its values carry
+// |mean| / std <= 2^8 .. 2^11 at best, and the kernels share their arithmetic with the conv-epilogue statistics.
+template <typename T> constexpr bool gn_pivot = std::is_same<T, float>::value;
 template <typename T>
 __global__ __launch_bounds__(256) void gn_fused_kernel(T* __restrict__ x, const T* __restrict__ res, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int HW, int C, int G, int CS, float eps, int relu, int cg_true) {
@@ -435,11 +445,24 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(T* __restrict__ x, const 
     float s1[CH], s2[CH];
 #pragma unroll
     for (int j = 0; j < CH; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    const T* x0 = x + (size_t)b * HW * C + c_base;      // pixel 0 of the slab: the pivots (this workgroup alone stores to the slab, in pass 2)
+    float piv[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) piv[j] = 0.f;
+    if constexpr (gn_pivot<T>) {
+        if (!cg_true) {
+#pragma unroll
+            for (int j = 0; j < CH; ++j) piv[j] = Tr<T>::ld(x0 + ((cc * CH + j) / Cg) * Cg);
+        }
+    }
     for (int p = prow; p < HW; p += pstep) {
         float v[CH];
         ld_chunk(xb + (size_t)p * C, v);
 #pragma unroll
-        for (int j = 0; j < CH; ++j) { s1[j] += v[j]; s2[j] += v[j] * v[j]; }
+        for (int j = 0; j < CH; ++j) {
+            if constexpr (gn_pivot<T>) v[j] -= piv[j];
+            s1[j] += v[j]; s2[j] += v[j] * v[j];
+        }
     }
     // lanes with equal (lane % cpr) hold the same channels: butterfly over the other lane bits
     for (int o = 32; o >= cpr; o >>= 1) {
@@ -462,8 +485,9 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(T* __restrict__ x, const 
         float a = 0.f, q = 0.f;
         for (int j = 0; j < Cg; ++j) { a += s_sum[g0 + j]; q += s_sq[g0 + j]; }
         const float inv_n = 1.0f / ((float)HW * (float)(cg_true > 0 ? cg_true : Cg));     // cg_true: the group's other channels are zero padding
-        const float mean = a * inv_n;
+        float mean = a * inv_n;
         const float var = relu_f(q * inv_n - mean * mean);
+        if constexpr (gn_pivot<T>) { if (!cg_true) mean += Tr<T>::ld(x0 + g0); }
         const float rstd = rsqrtf(var + eps);
         const float ga = gamma[c_base + ch];
         s_mean[ch] = mean * rstd * ga - beta[c_base + ch];     // y = x*scale - shift'
@@ -497,9 +521,11 @@ static long gn_slab_limit() {
 // pixel rows -- every access is a full 128-byte-or-wider run, where the slab kernel above would touch 16 bytes of each
 // line (the stem's 64 x 64 x 64 map: 143 us -> ~30 us).  Launch 1 writes per-(sample, chunk, group) sum / sum of squares;
 // launch 2 adds the <= 16 partials of its sample in a fixed order (deterministic, no atomics), normalises its chunk, adds
-// the residual, applies ReLU.
+// the residual, applies ReLU.  float32 storage (gn_pivot<T>, see gn_fused_kernel): the partial sums run over x - K, K = the (sample, group)'s
+// first element, which the chunk-0 workgroup also leaves in pivot[b * G + g] for the apply pass (that pass stores over x).
 template <typename T>
-__global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, int HW, int C, int G, int P) {
+__global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, float* __restrict__ pivot, int HW, int C, int G,
+                                                        int P) {
     constexpr int CH = Tr<T>::CH;
     __shared__ float s_p1[4][512], s_p2[4][512];     // C <= 512 on this path
     const int b = blockIdx.y, pc = blockIdx.x;
@@ -508,14 +534,26 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
     const int cc = tid % cpr, prow = tid / cpr, pstep = 256 / cpr;
     const int chunk = HW / P;
     const T* xb = x + ((size_t)b * HW + (size_t)pc * chunk) * C + cc * CH;
+    const T* x0 = x + (size_t)b * HW * C;          // pixel 0 of the sample: the pivots
+    const int Cg = C / G;
     float s1[CH], s2[CH];
 #pragma unroll
     for (int j = 0; j < CH; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+    float piv[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) piv[j] = 0.f;
+    if constexpr (gn_pivot<T>) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) piv[j] = Tr<T>::ld(x0 + ((cc * CH + j) / Cg) * Cg);
+    }
     for (int p = prow; p < chunk; p += pstep) {
         float v[CH];
         ld_chunk(xb + (size_t)p * C, v);
 #pragma unroll
-        for (int j = 0; j < CH; ++j) { s1[j] += v[j]; s2[j] += v[j] * v[j]; }
+        for (int j = 0; j < CH; ++j) {
+            if constexpr (gn_pivot<T>) v[j] -= piv[j];
+            s1[j] += v[j]; s2[j] += v[j] * v[j];
+        }
     }
     for (int o = 32; o >= cpr; o >>= 1) {
 #pragma unroll
@@ -531,7 +569,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
         for (int j = 0; j < CH; ++j) { s_p1[wv][cc * CH + j] = s1[j]; s_p2[wv][cc * CH + j] = s2[j]; }
     }
     __syncthreads();
-    const int Cg = C / G;
     for (int g = tid; g < G; g += 256) {
         float a = 0.f, q = 0.f;
         for (int j = 0; j < Cg; ++j) {
@@ -541,13 +578,15 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
         }
         float* o = part + (((size_t)b * P + pc) * G + g) * 2;
         o[0] = a; o[1] = q;
+        if constexpr (gn_pivot<T>) { if (pc == 0) pivot[(size_t)b * G + g] = Tr<T>::ld(x0 + g * Cg); }
     }
 }
 
-template <typename T>
+// PIV: the partial sums are gn_stats_kernel's shifted ones and pivot[b * G + g] holds the shift; epilogue-fed calls (plain sums) run PIV = false.
+template <typename T, bool PIV>
 __global__ __launch_bounds__(256) void gn_apply_kernel(T* __restrict__ x, const T* __restrict__ res, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, const float* __restrict__ part, int HW, int C, int G,
-                                                        int P, float eps, int relu, int PS) {
+                                                        const float* __restrict__ beta, const float* __restrict__ part,
+                                                        const float* __restrict__ pivot, int HW, int C, int G, int P, float eps, int relu, int PS) {
     constexpr int CH = Tr<T>::CH;
     __shared__ float s_scale[512], s_shift[512];
     __shared__ float s_mean[256], s_rstd[256];
@@ -570,8 +609,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(T* __restrict__ x, const 
             for (; i < PS; ++i) { const float2 t = pp[(size_t)i * G]; a += t.x; q += t.y; }
         }
         const float inv_n = 1.0f / ((float)HW * (float)Cg);
-        const float mean = a * inv_n;
+        float mean = a * inv_n;
         const float var = relu_f(q * inv_n - mean * mean);
+        if constexpr (PIV) mean += pivot[(size_t)b * G + g];
         s_mean[g] = mean;
         s_rstd[g] = rsqrtf(var + eps);
     }
@@ -616,9 +656,12 @@ __global__ __launch_bounds__(256) void gn_generic_kernel(T* __restrict__ x, cons
     const T* rb = res ? res + (size_t)b * HW * C + (size_t)g * Cg : nullptr;
     const int n = HW * Cg;
     float a = 0.f, q = 0.f;
+    float K = 0.f;                                   // float32: the group's first element (see gn_fused_kernel); stores start behind the barriers below
+    if constexpr (gn_pivot<T>) { if (!cg_true) K = Tr<T>::ld(xb); }
     for (int e = tid; e < n; e += 256) {
         const int p = e / Cg, c = e - p * Cg;
-        const float v = Tr<T>::ld(xb + (size_t)p * C + c);
+        float v = Tr<T>::ld(xb + (size_t)p * C + c);
+        if constexpr (gn_pivot<T>) v -= K;
         a += v; q += v * v;
     }
     s_a[tid] = a; s_q[tid] = q;
@@ -628,8 +671,9 @@ __global__ __launch_bounds__(256) void gn_generic_kernel(T* __restrict__ x, cons
         __syncthreads();
     }
     const float inv_n = 1.0f / ((float)HW * (float)(cg_true > 0 ? cg_true : Cg));
-    const float mean = s_a[0] * inv_n;
+    float mean = s_a[0] * inv_n;
     const float rstd = rsqrtf(relu_f(s_q[0] * inv_n - mean * mean) + eps);
+    if constexpr (gn_pivot<T>) mean += K;
     for (int e = tid; e < n; e += 256) {
         const int p = e / Cg, c = e - p * Cg;
         const size_t off = (size_t)p * C + c;
@@ -652,8 +696,10 @@ hipError_t launch_groupnorm(void* x, const void* res, const float* gamma, const 
     if (two_pass && !cg_true && stats && P > 0 && !(cprw & (cprw - 1)) && cprw <= 128 && C <= 512 && G <= 256 && HW % P == 0 &&
         (HW >= 1024 || C <= 256)) {             // 16 x 16 maps with 512 channels: the slab kernel is faster (13 vs 21 us)
         HCM_DISPATCH_T(dt, {
-            hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(P, B), dim3(256), 0, s, (const T*)x, stats, HW, C, G, P);
-            hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(P, B), dim3(256), 0, s, (T*)x, (const T*)res, gamma, beta, stats, HW, C, G, P, eps, relu, P);
+            float* pivot = stats + gn_pivot_offset(B, HW, G);
+            hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(P, B), dim3(256), 0, s, (const T*)x, stats, pivot, HW, C, G, P);
+            hipLaunchKernelGGL((gn_apply_kernel<T, gn_pivot<T>>), dim3(P, B), dim3(256), 0, s, (T*)x, (const T*)res, gamma, beta, stats, (const float*)pivot, HW,
+                               C, G, P, eps, relu, P);
         });
         return hipGetLastError();
     }
@@ -687,8 +733,8 @@ hipError_t launch_groupnorm_apply(void* x, const void* res, const float* gamma, 
                                   int HW, int C, int G, float eps, int relu, hipStream_t s) {
     if (!groupnorm_apply_ok(dt, HW, C, G) || PS < 1) return hipErrorInvalidValue;
     const int P = gn_partials(HW);
-    HCM_DISPATCH_T(dt, hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(P, B), dim3(256), 0, s, (T*)x, (const T*)res, gamma, beta, part, HW, C, G, P, eps,
-                                          relu, PS));
+    HCM_DISPATCH_T(dt, hipLaunchKernelGGL((gn_apply_kernel<T, false>), dim3(P, B), dim3(256), 0, s, (T*)x, (const T*)res, gamma, beta, part,
+                                          (const float*)nullptr, HW, C, G, P, eps, relu, PS));
     return hipGetLastError();
 }
 

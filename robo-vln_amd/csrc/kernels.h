@@ -198,8 +198,9 @@ inline int gn_partials(int HW) { return HW >= 256 ? (HW / 64 < 16 ? HW / 64 : 16
 inline size_t gn_stats_floats(int B, int HW, int G) {
     const int P = gn_partials(HW), PS = HW % 64 == 0 ? HW / 64 : 0;          // two-launch chunks / 64-row blocks of the epilogue statistics
     const int n = P > PS ? P : PS;
-    return (size_t)B * (n > 0 ? n : 1) * G * 2;
+    return (size_t)B * (n > 0 ? n : 1) * G * 2 + (size_t)B * G;           // the partial sums, then one pivot per (sample, group) (float32 two-launch path)
 }
+inline size_t gn_pivot_offset(int B, int HW, int G) { return gn_stats_floats(B, HW, G) - (size_t)B * G; }
 // second half of the two-launch GroupNorm alone: statistics come from `part` = PS partial sums per (sample, group) (launch_igemm's cs_part)
 hipError_t launch_groupnorm_apply(void* x, const void* res, const float* gamma, const float* beta, const float* part, int PS, int dt, int B,
                                   int HW, int C, int G, float eps, int relu, hipStream_t s);
