@@ -17,11 +17,20 @@ from tests.vla_train_cases import rel  # noqa: F401  (the project's bound rule, 
 D = 256
 KINK = 2e-5
 # (rows, K, period or 0, p, want_dx): one row, smallest K; a few rows with a table; one short of the 64-row block; one row past it at BERT's width
-# without d_x; two blocks and a ragged tail with K in three slices; whole blocks at the largest K without dropout or table
+# without d_x; two blocks and a ragged tail with K in three slices; whole blocks at the largest K without dropout or table.
+# Then K past one 256 slice without being a multiple of it (a full slice, then a ragged one of 64 or 192 with zero fill behind it; in the backward
+# a last d_x panel of 2 or 6 tiles at a non-zero offset into the packed weight): one full slice + 64; 192 behind one full slice with two row blocks
+# and a table whose period does not divide the block; two full slices + 64; three full + 192 on exactly one row block; a single 192 slice; and
+# three row blocks with three full slices + 64 without d_x; and, to complete the tails behind a full slice, one full slice + 128 (a 4-tile d_x panel
+# at a non-zero offset)
 CASES = [(1, 64, 0, 0.0, True), (5, 256, 5, 0.25, True), (63, 128, 0, 0.25, True), (65, 768, 13, 0.25, False), (130, 768, 65, 0.1, True),
-         (128, 1024, 0, 0.0, True)]
+         (128, 1024, 0, 0.0, True),
+         (3, 320, 0, 0.25, True), (66, 448, 7, 0.1, True), (5, 576, 0, 0.0, True), (64, 960, 0, 0.25, True), (2, 192, 2, 0.0, True),
+         (129, 832, 0, 0.25, False), (4, 384, 3, 0.1, True)]
 SEEDS = {(1, 64, 0, 0.0, True): 0, (5, 256, 5, 0.25, True): 0, (63, 128, 0, 0.25, True): 2, (65, 768, 13, 0.25, False): 1,
-         (130, 768, 65, 0.1, True): 1, (128, 1024, 0, 0.0, True): 0}          # first_seed() of each case
+         (130, 768, 65, 0.1, True): 1, (128, 1024, 0, 0.0, True): 0,
+         (3, 320, 0, 0.25, True): 0, (66, 448, 7, 0.1, True): 0, (5, 576, 0, 0.0, True): 0, (64, 960, 0, 0.25, True): 2, (2, 192, 2, 0.0, True): 0,
+         (129, 832, 0, 0.25, False): 1, (4, 384, 3, 0.1, True): 0}          # first_seed() of each case
 NAMES = ("d_x", "d_w", "d_b", "d_gamma", "d_beta")
 
 

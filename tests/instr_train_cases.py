@@ -2,7 +2,9 @@
 CPU-autograd reference through train.instr_encoder_ref, computed once per case and never modified.
 
 Inputs: weights and biases uniform in +-0.1, embedded rows and the cotangent uniform in +-1.  A case is (rnn, dirs, final, B, L): the lengths
-come from LENGTHS, the cotangent has the shape of the result -- (B, L, dirs*H), or (B, H) for the final state."""
+come from LENGTHS, the cotangent has the shape of the result -- (B, L, dirs*H), or (B, H) for the final state.  EDGE_CASES hold lengths of 0,
+below 0 and past L (instr_encoder_ref's activity test is t < lengths, so they need no other reference), the 200-token horizon and eight samples
+per workgroup in one direction; SATURATED_CASES are built with weight_ih times SATURATED_IH_SCALE."""
 import functools
 
 import torch
@@ -23,7 +25,35 @@ LENGTHS = {
     (9, 12): (12, 3, 7, 1, 9, 12, 5, 10, 2),
     (130, 3): tuple(1 + (3 * b + b // 7) % 3 for b in range(130)),
     (260, 2): tuple(1 + (b + b // 5) % 2 for b in range(260)),
+    # the edges of include/hcm.h's packed-sequence promise (EDGE_CASES below).  Rows of length 0, at two samples per workgroup a workgroup that owns
+    # only such rows (rows 2 and 3: it walks no step and reads nothing), and a negative length, which counts as 0
+    (6, 9): (9, 0, 0, 0, 4, -3),
+    # a length past L, which counts as L
+    (4, 5): (5, 9, 0, 1),
+    # the documented horizon of 200 tokens, beside an empty row
+    (3, 200): (200, 0, 137),
+    # eight samples per workgroup with ONE direction (ceil(513 / 4) = 129 workgroups are one too many): rows 8..15 empty, so the second workgroup is
+    # idle, and the last workgroup holds one sample
+    (513, 2): tuple(0 if 8 <= b < 16 else 1 + (b + b // 5) % 2 for b in range(513)),
+    # the saturated regime (SATURATED_CASES below): long enough for a saturated state to be carried, with an empty row and a row of one token
+    (4, 40): (40, 0, 23, 1),
 }
+# the settings each edge shape runs with: all six where the scan is short, four at the horizon, the one-direction three at 513 rows
+EDGE_SETTINGS = {
+    (6, 9): SETTINGS,
+    (4, 5): SETTINGS,
+    (3, 200): [("LSTM", 2, False), ("GRU", 1, True), ("GRU", 2, False), ("LSTM", 1, True)],
+    (513, 2): [("LSTM", 1, True), ("GRU", 1, True), ("LSTM", 1, False)],
+    # four samples per workgroup with ONE direction (257 .. 512 rows), which the two-direction cases of this shape do not reach
+    (260, 2): [("LSTM", 1, True), ("GRU", 1, False)],
+}
+# the cases of tests/test_instr_train_gpu.py in front of the edges: every setting at the four small shapes, two directions at the two large ones
+GPU_SHAPES = [(1, 1), (3, 7), (5, 33), (9, 12)]
+GPU_CASES = [(*s, B, L) for s in SETTINGS for B, L in GPU_SHAPES] + [(rnn, 2, False, B, L) for rnn in ("LSTM", "GRU") for B, L in ((130, 3), (260, 2))]
+EDGE_CASES = [(*s, B, L) for (B, L), settings in EDGE_SETTINGS.items() for s in settings]
+# weight_ih times 20, uniform in +-2: about a fifth of the input-side pre-activations pass +-6, where g (1 - g) and 1 - n^2 round towards zero
+SATURATED_IH_SCALE = 20.0
+SATURATED_CASES = [("LSTM", 2, False, 4, 40), ("GRU", 2, False, 4, 40)]
 PARAM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 
@@ -31,8 +61,9 @@ def grad_names(dirs):
     return ["d_emb"] + [f"d_{n}{sfx}" for sfx in ("", "_reverse")[:dirs] for n in PARAM_NAMES]
 
 
-def make_inputs(rnn, dirs, final, B, L, H, E, seed):
-    """(embedded (B, L, E), params per direction, cotangent), float32 on the CPU"""
+def make_inputs(rnn, dirs, final, B, L, H, E, seed, ih_scale=1.0):
+    """(embedded (B, L, E), params per direction, cotangent), float32 on the CPU; ih_scale multiplies every weight_ih behind the draws, so that
+    every other tensor of a seed is the same with and without it"""
     g = torch.Generator().manual_seed(seed)
 
     def u(*shape, scale=1.0):
@@ -42,7 +73,14 @@ def make_inputs(rnn, dirs, final, B, L, H, E, seed):
     params = [(u(G * H, E, scale=0.1), u(G * H, H, scale=0.1), u(G * H, scale=0.1), u(G * H, scale=0.1)) for _ in range(dirs)]
     emb = u(B, L, E)
     cot = u(B, H) if final else u(B, L, dirs * H)
+    if ih_scale != 1.0:
+        params = [(w_ih * ih_scale, w_hh, b_ih, b_hh) for w_ih, w_hh, b_ih, b_hh in params]
     return emb, params, cot
+
+
+def clamped(lengths, L):
+    """the lengths as the kernels read them: below 0 counts as 0, past L as L"""
+    return lengths.clamp(0, L)
 
 
 def reference(emb, lengths, params, final, cot):
@@ -55,9 +93,9 @@ def reference(emb, lengths, params, final, cot):
 
 
 @functools.lru_cache(maxsize=None)
-def case(rnn, dirs, final, B, L, H=256, E=50):
+def case(rnn, dirs, final, B, L, H=256, E=50, ih_scale=1.0):
     lengths = torch.tensor(LENGTHS[(B, L)])
-    emb, params, cot = make_inputs(rnn, dirs, final, B, L, H, E, 10000 * B + 100 * L + 10 * dirs + 2 * final + (rnn == "GRU"))
+    emb, params, cot = make_inputs(rnn, dirs, final, B, L, H, E, 10000 * B + 100 * L + 10 * dirs + 2 * final + (rnn == "GRU"), ih_scale)
     y64, g64 = reference(emb, lengths, params, final, cot)
     return dict(emb=emb, params=params, cot=cot, lengths=lengths, y64=y64, ref=dict(zip(grad_names(dirs), g64)))
 
@@ -75,7 +113,7 @@ def saved64(emb, lengths, params):
         w_ih, w_hh, b_ih, b_hh = (t.double() for t in p)
         for b in range(B):
             h, c = torch.zeros(H, dtype=torch.float64), torch.zeros(H, dtype=torch.float64)
-            n = int(lengths[b])
+            n = min(max(int(lengths[b]), 0), L)
             for t in (range(n - 1, -1, -1) if d else range(n)):
                 gi, gh = w_ih @ x[b, t] + b_ih, w_hh @ h + b_hh
                 if lstm:

@@ -163,7 +163,7 @@ def test_kink_condition_holds(case):
 
 def test_cases_straddle_the_row_block_and_the_k_slices():
     rows = [c[0] for c in ec.CASES]
-    assert {1, 63, 65, 130, 128} <= set(rows) and {64, 128, 256, 768, 1024} == {c[1] for c in ec.CASES}
+    assert {1, 63, 65, 130, 128} <= set(rows) and {64, 128, 192, 256, 320, 384, 448, 576, 768, 832, 960, 1024} == {c[1] for c in ec.CASES}
     assert any(not c[4] for c in ec.CASES) and any(c[2] for c in ec.CASES) and any(c[3] == 0 for c in ec.CASES)
 
 

@@ -105,7 +105,7 @@ def test_gradients_match_float64_autograd(case):
 
 
 # ---- raw C ABI ----
-RAW_CASES = [(65, 768, 13, 0.25, False), (130, 768, 65, 0.1, True), (63, 128, 0, 0.25, True)]
+RAW_CASES = [(65, 768, 13, 0.25, False), (130, 768, 65, 0.1, True), (63, 128, 0, 0.25, True)] + ec.CASES[6:]
 
 
 @pytest.mark.parametrize("case", RAW_CASES)

@@ -5,10 +5,13 @@ non-default stream, and the refusals.
 
 Gradient bound: per tensor max|g - g64| / max|g64| <= 1e-5 with exact zero where the reference is identically zero (`rel` / BOUND, the rule of
 tests/test_state_scan_train_gpu.py); forward outputs 1e-5 absolute.  torch's own float32 CPU path lies within 7.1e-7 (forward 1.7e-7) of float64
-on the first five shapes with these input distributions.  No element is excluded from any comparison.
+on the first five shapes with these input distributions.  No element is excluded from any comparison.  The edge cases of
+tests/instr_train_cases.py (lengths of 0, below 0 and past L, a workgroup of empty rows, 200 tokens, eight samples per workgroup in one direction)
+and the saturated ones run under the same bounds; tests/test_train_coverage_cpu.py holds the float32 CPU restatement to half of them there.
 
 Samples per workgroup: the launcher takes the fewest of 2, 4, 8 that keep the launch within 128 workgroups, the rule of launch_instr_lstm_scan;
-with two directions (130, 3) reaches 4 and (260, 2) reaches 8, every other case runs at 2.  The rule is restated in instr_scan_train_sb without
+with two directions (130, 3) reaches 4 and (260, 2) reaches 8, with one direction (260, 2) reaches 4 and (513, 2) reaches 8, every other case
+runs at 2 (tests/test_train_coverage_cpu.py computes this from the case lists).  The rule is restated in instr_scan_train_sb without
 launch_instr_lstm_scan's HCM_LSTM_SB override, which only the development build reads: on that build, with the variable set, the bitwise
 comparison would put the inference scan at another count than the training forward (the sums per sample are the same at every count, so the
 bits should still agree, but that is not what these cases were written to show).  These tests load the shipped library."""
@@ -24,15 +27,14 @@ from tests.instr_train_cases import BOUND, rel
 pytestmark = pytest.mark.gpu
 
 H, E = 256, 50
-SHAPES = [(1, 1), (3, 7), (5, 33), (9, 12)]
-CASES = [(*s, B, L) for s in cases.SETTINGS for B, L in SHAPES] + [(rnn, 2, False, B, L) for rnn in ("LSTM", "GRU") for B, L in ((130, 3), (260, 2))]
+SHAPES, CASES = cases.GPU_SHAPES, cases.GPU_CASES
 
 
-def _gpu(rnn, dirs, final, B, L, emb_grad=True):
-    c = cases.case(rnn, dirs, final, B, L)
+def _gpu(rnn, dirs, final, B, L, emb_grad=True, lengths=None, ih_scale=1.0):
+    c = cases.case(rnn, dirs, final, B, L, ih_scale=ih_scale)
     emb = c["emb"].cuda().requires_grad_(emb_grad)
     params = [tuple(t.cuda().requires_grad_() for t in p) for p in c["params"]]
-    y = train.instr_scan(emb, c["lengths"].cuda(), params, final)
+    y = train.instr_scan(emb, (c["lengths"] if lengths is None else lengths).cuda(), params, final)
     leaves = ([emb] if emb_grad else []) + [t for p in params for t in p]
     grads = torch.autograd.grad(y, leaves, c["cot"].cuda())
     torch.cuda.synchronize()
@@ -40,24 +42,66 @@ def _gpu(rnn, dirs, final, B, L, emb_grad=True):
     return y.detach().cpu(), dict(zip(names, (g.cpu() for g in grads)))
 
 
-@pytest.mark.parametrize("rnn,dirs,final,B,L", CASES)
-def test_gradients_match_float64_autograd(rnn, dirs, final, B, L):
-    c = cases.case(rnn, dirs, final, B, L)
-    y, grads = _gpu(rnn, dirs, final, B, L)
-    tag = f"[{rnn} dirs={dirs} final={final} B={B} L={L}]"
+def _check_against_float64(c, y, grads, tag, dirs, final, L):
     e_y = (y.double() - c["y64"]).abs().max().item()
     print(f"{tag} forward {e_y:.3e}")
     assert y.shape == c["y64"].shape and e_y <= 1e-5
+    active = torch.arange(L)[None, :] < c["lengths"][:, None]
+    empty = ~active.any(1)
     if not final:
-        active = torch.arange(L)[None, :] < c["lengths"][:, None]
         assert (y[~active] == 0).all()                                   # exact zeros at every inactive token
+    else:
+        assert (y[empty] == 0).all()                                     # the zero state of a row without a token
     errs = {k: rel(grads[k], c["ref"][k], f"{tag} {k}") for k in cases.grad_names(dirs)}
+    # an inactive token, and so every token of an empty sample, receives exactly nothing (as in the reference)
+    assert (c["ref"]["d_emb"][~active] == 0).all() and (grads["d_emb"][~active] == 0).all()
+    assert (grads["d_emb"][empty] == 0).all()
     assert max(errs.values()) <= BOUND, errs
 
 
-def _raw(rnn, dirs, final, B, L, nan_cot_at_padding=False):
-    """hcm_op_instr_scan_train, hcm_op_instr_scan_bwd and the engines' inference scan through the C ABI on one case's inputs"""
+@pytest.mark.parametrize("rnn,dirs,final,B,L", CASES + cases.EDGE_CASES)
+def test_gradients_match_float64_autograd(rnn, dirs, final, B, L):
     c = cases.case(rnn, dirs, final, B, L)
+    y, grads = _gpu(rnn, dirs, final, B, L)
+    _check_against_float64(c, y, grads, f"[{rnn} dirs={dirs} final={final} B={B} L={L}]", dirs, final, L)
+
+
+@pytest.mark.parametrize("rnn,dirs,final,B,L", cases.SATURATED_CASES)
+def test_gradients_match_float64_autograd_with_saturated_gates(rnn, dirs, final, B, L):
+    """weight_ih times 20: about a fifth of the input-side pre-activations pass +-6, so g (1 - g) and 1 - n^2 round towards zero.  The bound is the
+    one above; tests/test_train_coverage_cpu.py holds the float32 CPU restatement to half of it on the same inputs."""
+    c = cases.case(rnn, dirs, final, B, L, ih_scale=cases.SATURATED_IH_SCALE)
+    y, grads = _gpu(rnn, dirs, final, B, L, ih_scale=cases.SATURATED_IH_SCALE)
+    _check_against_float64(c, y, grads, f"[{rnn} dirs={dirs} final={final} B={B} L={L} saturated]", dirs, final, L)
+
+
+OUT_OF_RANGE = [(*s, B, L) for B, L in ((6, 9), (4, 5)) for s in cases.SETTINGS]
+
+
+@pytest.mark.parametrize("rnn,dirs,final,B,L", OUT_OF_RANGE)
+def test_out_of_range_lengths_are_the_clamped_lengths_bitwise(rnn, dirs, final, B, L):
+    """a length below 0 is 0 and one past L is L: the scans' own results -- the output through the autograd function, and out, final, d_pre and
+    d_gh through the C ABI -- carry the bits of a call whose lengths were clamped on the host.  (The parameter gradients end in torch GEMMs over
+    those d_pre / d_gh, the BLAS library's business, and are held to float64 above.)"""
+    raw_lengths = cases.case(rnn, dirs, final, B, L)["lengths"]
+    host = cases.clamped(raw_lengths, L)
+    assert not torch.equal(host, raw_lengths) and host.min() >= 0 and host.max() <= L
+    y, grads = _gpu(rnn, dirs, final, B, L)
+    y_c, grads_c = _gpu(rnn, dirs, final, B, L, lengths=host)
+    assert torch.equal(y, y_c)
+    for k in grads:
+        assert rel(grads[k], grads_c[k].double(), f"clamped on the host {k}") <= 1e-6
+    a, _ = _raw(rnn, dirs, final, B, L)
+    b, _ = _raw(rnn, dirs, final, B, L, lengths=host)
+    for k in ("out", "fin", "d_pre", "d_gh"):
+        if a[k] is not None:
+            assert not a[k].isnan().any() and torch.equal(a[k], b[k]), k
+
+
+def _raw(rnn, dirs, final, B, L, nan_cot_at_padding=False, lengths=None, ih_scale=1.0):
+    """hcm_op_instr_scan_train, hcm_op_instr_scan_bwd and the engines' inference scan through the C ABI on one case's inputs (or on `lengths` in
+    place of the case's); every output starts as NaN"""
+    c = cases.case(rnn, dirs, final, B, L, ih_scale=ih_scale)
     lstm = rnn == "LSTM"
     G = 4 if lstm else 3
     kind = _lib.HCM_LSTM if lstm else _lib.HCM_GRU
@@ -70,7 +114,7 @@ def _raw(rnn, dirs, final, B, L, nan_cot_at_padding=False):
                        for w_ih, _, b_ih, b_hh in params])
     w_hh = torch.stack([p[1] for p in params])
     b_hn = None if lstm else torch.stack([p[3][2 * H:] for p in params])
-    lens = c["lengths"].to(torch.int32).cuda()
+    lens = (c["lengths"] if lengths is None else lengths).to(torch.int32).cuda()
     nan = float("nan")
     o = dict(out=torch.full((B, L, dirs * H), nan, device="cuda"), fin=torch.full((B, H), nan, device="cuda"),
              gates=torch.full((dirs, B, L, 4 * H), nan, device="cuda"), c_seq=torch.full((dirs, B, L, H), nan, device="cuda") if lstm else None,
@@ -94,7 +138,7 @@ def _raw(rnn, dirs, final, B, L, nan_cot_at_padding=False):
     return o, ref
 
 
-RAW = [(*s, B, L) for s in cases.SETTINGS for B, L in ((3, 7), (5, 33))] + [("LSTM", 2, False, 130, 3), ("GRU", 2, False, 260, 2)]
+RAW = [(*s, B, L) for s in cases.SETTINGS for B, L in ((3, 7), (5, 33))] + [("LSTM", 2, False, 130, 3), ("GRU", 2, False, 260, 2)] + cases.EDGE_CASES
 
 
 @pytest.mark.parametrize("rnn,dirs,final,B,L", RAW)
@@ -102,21 +146,23 @@ def test_padding_is_exactly_zero_and_saved_tensors_are_written(rnn, dirs, final,
     c = cases.case(rnn, dirs, final, B, L)
     o, _ = _raw(rnn, dirs, final, B, L, nan_cot_at_padding=not final)
     g64, c64, active = cases.saved64(c["emb"], c["lengths"], c["params"])
-    out = o["out"].cpu()
+    out, fin = o["out"].cpu(), o["fin"].cpu()
     assert (out[~active] == 0).all() and not out.isnan().any()
+    assert not fin.isnan().any() and (fin[~active.any(1)] == 0).all()       # the zero state of a row without a token
     for k in ("d_pre", "d_gh"):
         if o[k] is not None:
             t = o[k].cpu()
             assert not t.isnan().any(), k                               # every element written, and the NaN cotangents at padding were not read
             assert (t[:, ~active] == 0).all(), k
-    # saved tensors started as NaN: every active element was written, each within 1e-5 of float64
+    # saved tensors started as NaN: every active element was written, each within 1e-5 of float64, and as include/hcm.h says nothing was
+    # written at an inactive token (GRU leaves nothing out of its four slots: r, z, n and hn)
     gates = o["gates"].cpu()
     e_g = (gates[:, active].double() - g64[:, active]).abs().max().item()
-    assert not gates[:, active].isnan().any()
+    assert not gates[:, active].isnan().any() and gates[:, ~active].isnan().all()
     e_c = 0.0
     if c64 is not None:
         cs = o["c_seq"].cpu()
-        assert not cs[:, active].isnan().any()
+        assert not cs[:, active].isnan().any() and cs[:, ~active].isnan().all()
         e_c = (cs[:, active].double() - c64[:, active]).abs().max().item()
     fin64 = c["y64"] if final else None
     e_f = (o["fin"].cpu().double() - fin64).abs().max().item() if final else 0.0
@@ -124,13 +170,42 @@ def test_padding_is_exactly_zero_and_saved_tensors_are_written(rnn, dirs, final,
     assert e_g <= 1e-5 and e_c <= 1e-5 and e_f <= 1e-5
 
 
+# (the inference hook serves the final-state scan of either cell and the per-token scan of the LSTM)
+INFER_EDGES = [s + shape for shape in ((6, 9), (3, 200), (513, 2)) for s in cases.EDGE_SETTINGS[shape] if s[2] or s[0] == "LSTM"]
+
+
 @pytest.mark.parametrize("rnn,dirs,final,B,L", [("LSTM", 1, True, 5, 33), ("GRU", 1, True, 5, 33), ("LSTM", 1, True, 9, 12), ("GRU", 1, True, 9, 12),
                                                 ("LSTM", 2, False, 5, 33), ("LSTM", 1, False, 9, 12), ("LSTM", 2, False, 130, 3),
-                                                ("LSTM", 2, False, 260, 2)])
+                                                ("LSTM", 2, False, 260, 2)] + INFER_EDGES)
 def test_training_forward_is_the_inference_scan_bitwise(rnn, dirs, final, B, L):
     o, ref = _raw(rnn, dirs, final, B, L)
     assert not ref.isnan().any()
     assert torch.equal(o["fin"] if final else o["out"], ref)
+
+
+@pytest.mark.parametrize("rnn,dirs,final", [("LSTM", 2, False), ("GRU", 2, False), ("LSTM", 1, True), ("GRU", 1, True)])
+def test_empty_rows_and_an_empty_workgroup_leave_zeros_and_untouched_saved_tensors(rnn, dirs, final):
+    """(6, 9): rows of length 0, a workgroup whose two samples are both empty (it runs no step) and a negative length, one call each of
+    hcm_op_instr_scan_train and hcm_op_instr_scan_bwd with every output pre-filled with NaN.  out, final, d_pre and d_gh come back without a NaN
+    and zero at every inactive token, the idle workgroup's rows included; gates and c_seq are written at active tokens only."""
+    B, L = 6, 9
+    c = cases.case(rnn, dirs, final, B, L)
+    o, _ = _raw(rnn, dirs, final, B, L, nan_cot_at_padding=not final)
+    active = torch.arange(L)[None, :] < c["lengths"][:, None]
+    empty = ~active.any(1)
+    assert empty.tolist() == [False, True, True, True, False, True] and active.sum().item() == 13
+    for k in ("out", "fin", "d_pre", "d_gh", "gates", "c_seq"):
+        if o[k] is None:
+            continue
+        t = o[k].cpu()
+        if k == "fin":
+            assert not t.isnan().any() and (t[empty] == 0).all() and (t[~empty] != 0).any(1).all()
+        elif k == "out":
+            assert not t.isnan().any() and (t[~active] == 0).all() and (t[active] != 0).any(1).all()
+        elif k in ("d_pre", "d_gh"):
+            assert not t.isnan().any() and (t[:, ~active] == 0).all() and (t[:, active] != 0).any(2).all(), k
+        else:
+            assert t[:, ~active].isnan().all() and t[:, active].isfinite().all(), k
 
 
 def test_the_final_state_is_the_last_active_output():
@@ -141,7 +216,9 @@ def test_the_final_state_is_the_last_active_output():
 
 
 @pytest.mark.parametrize("rnn,dirs,final,B,L", [("LSTM", 2, False, 5, 33), ("GRU", 2, False, 5, 33), ("LSTM", 1, True, 9, 12), ("GRU", 1, True, 9, 12),
-                                                ("GRU", 2, False, 130, 3)])
+                                                ("GRU", 2, False, 130, 3), ("LSTM", 2, False, 6, 9), ("GRU", 1, True, 6, 9), ("GRU", 2, False, 4, 5),
+                                                ("LSTM", 2, False, 3, 200), ("GRU", 2, False, 3, 200), ("LSTM", 1, True, 513, 2),
+                                                ("GRU", 1, True, 513, 2), ("LSTM", 1, False, 513, 2)])
 def test_two_runs_give_the_same_bits(rnn, dirs, final, B, L):
     a, _ = _raw(rnn, dirs, final, B, L)
     b, _ = _raw(rnn, dirs, final, B, L)
@@ -150,6 +227,27 @@ def test_two_runs_give_the_same_bits(rnn, dirs, final, B, L):
         if a[k] is not None:
             assert torch.equal(a[k], b[k]), k
     assert torch.equal(a["gates"][:, active], b["gates"][:, active])
+
+
+@pytest.mark.parametrize("rnn,dirs,final,B,L", cases.SATURATED_CASES)
+def test_saturated_gates_are_saved_and_two_runs_give_the_same_bits(rnn, dirs, final, B, L):
+    """the saturated cases through the C ABI: the saved gates (many within rounding of 0 or 1) and c within 1e-5 of float64, untouched at inactive
+    tokens, and every output of a second run bitwise equal"""
+    c = cases.case(rnn, dirs, final, B, L, ih_scale=cases.SATURATED_IH_SCALE)
+    a, _ = _raw(rnn, dirs, final, B, L, nan_cot_at_padding=True, ih_scale=cases.SATURATED_IH_SCALE)
+    b, _ = _raw(rnn, dirs, final, B, L, nan_cot_at_padding=True, ih_scale=cases.SATURATED_IH_SCALE)
+    g64, c64, active = cases.saved64(c["emb"], c["lengths"], c["params"])
+    gates = a["gates"].cpu()
+    assert gates[:, ~active].isnan().all()
+    e_g = (gates[:, active].double() - g64[:, active]).abs().max().item()
+    e_c = (a["c_seq"].cpu()[:, active].double() - c64[:, active]).abs().max().item() if c64 is not None else 0.0
+    sat = ((g64[:, active][..., :2 * H] < 1e-3) | (g64[:, active][..., :2 * H] > 1 - 1e-3)).double().mean().item()
+    print(f"[{rnn} dirs={dirs} final={final} B={B} L={L} saturated] saved gates {e_g:.3e} c_seq {e_c:.3e}; {sat:.3f} of the first two gates within 1e-3 of 0 or 1")
+    assert e_g <= 1e-5 and e_c <= 1e-5 and sat > 0.1
+    for k in ("out", "fin", "d_pre", "d_gh"):
+        if a[k] is not None:
+            assert not a[k].isnan().any() and torch.equal(a[k], b[k]), k
+    assert torch.equal(a["gates"][:, active.cuda()], b["gates"][:, active.cuda()])
 
 
 def test_d_emb_is_absent_when_the_input_does_not_require_it():

@@ -3,57 +3,26 @@ float64 CPU autograd through the cell loop, the training forward against hcm_op_
 module against its CPU path, an optimizer step between two calls, and a non-default stream.
 
 Gradient bound: per tensor max|g - g64| / max|g64| <= 1e-5, the bound the forward scans are held to against torch (tests/test_cma_seq_gpu.py);
-torch's own float32 CPU backward lands at 1e-7 .. 6e-7 on these cases.  Where g64 is identically zero the result must be exactly zero."""
+torch's own float32 CPU backward lands at 1e-7 .. 6e-7 on these cases.  Where g64 is identically zero the result must be exactly zero.
+The cases and their float64 references live in tests/state_scan_train_cases.py."""
 import ctypes as C
-import functools
 
 import pytest
 import torch
 
 from robo_vln_amd import _lib, train
+from tests import state_scan_train_cases as sc
+from tests.state_scan_train_cases import BOUND, CASES, H, I, NAMES, SHAPES
+from tests.state_scan_train_cases import case as _case
+from tests.state_scan_train_cases import masks as _masks
 
 pytestmark = pytest.mark.gpu
 
-H, I = 512, 32
-BOUND = 1e-5
-SHAPES = [(1, 3), (2, 1), (5, 9), (3, 8)]          # a partial sample block, one sample, a full block plus one, exactly one block
-CASES = [(T, N, "random") for T, N in SHAPES] + [(5, 9, "ones"), (1, 3, "zero0"), (3, 8, "zero0")]
-NAMES = ("dx", "dW_ih", "dW_hh", "db_ih", "db_hh", "d_h_in")
+RAW_SHAPES = SHAPES + [(33, 5), (6, 13)]           # through the C ABI as well: the horizon, and the sample blocks 8 + 5 / 4 + 4 + 4 + 1
 
 
-def _masks(T, N, kind, g):
-    if kind == "ones":
-        return torch.ones(T, N)
-    m = (torch.rand(T, N, generator=g) > 0.4).float()
-    m[0, 0] = 0
-    if T > 2:
-        m[T // 2, N // 2] = 0
-    m[T - 1, N - 1] = 0
-    if kind == "zero0":
-        m[0] = 0
-    return m
-
-
-@functools.lru_cache(maxsize=None)
-def _case(rnn, T, N, kind):
-    """Inputs (float32, CPU) and the float64 CPU-autograd reference of one case; computed once, never modified."""
-    g = torch.Generator().manual_seed(1000 * T + 10 * N + (rnn == "GRU") + 100 * len(kind))
-    G = 4 if rnn == "LSTM" else 3
-    R = 2 if rnn == "LSTM" else 1
-    p = [(torch.rand(s, generator=g) - 0.5) * 0.2 for s in ((G * H, I), (G * H, H), (G * H,), (G * H,))]     # uniform in +-0.1
-    x = torch.rand(T * N, I, generator=g) * 2 - 1
-    h0 = torch.rand(R, N, H, generator=g) - 0.5
-    m = _masks(T, N, kind, g)
-    cot = torch.rand(T * N, H, generator=g) * 2 - 1
-    leaves = [t.double().requires_grad_() for t in (x, *p, h0)]
-    seq64, hid64 = train.cell_loop(leaves[0], [tuple(leaves[1:5])], leaves[5], m.reshape(-1).double(), rnn)
-    g64 = torch.autograd.grad(seq64, leaves, cot.double())
-    ref = dict(zip(NAMES, g64))
-    return dict(x=x, p=p, h0=h0, m=m, cot=cot, seq64=seq64.detach(), hid64=hid64, ref=ref)
-
-
-def _gpu_grads(rnn, T, N, kind):
-    c = _case(rnn, T, N, kind)
+def _gpu_grads(rnn, T, N, kind, ih_scale=1.0):
+    c = _case(rnn, T, N, kind, ih_scale)
     leaves = [t.cuda().requires_grad_() for t in (c["x"], *c["p"], c["h0"])]
     seq, hid = train.state_scan(*leaves, c["m"].reshape(-1).cuda())
     assert not hid.requires_grad
@@ -91,12 +60,32 @@ def test_gradients_match_float64_autograd(rnn, T, N, kind):
         assert c["ref"]["d_h_in"][:, dead].abs().max().item() == 0 and grads["d_h_in"][:, dead].abs().max().item() == 0
     if kind == "zero0" and T == 1:
         assert c["ref"]["dW_hh"].abs().max().item() == 0 and grads["dW_hh"].abs().max().item() == 0
+    if kind == "cut":
+        # every sample is reset in front of step T // 2 and the cotangent in front of it is zero: the first half receives nothing
+        n = (T // 2) * N
+        assert c["ref"]["dx"][:n].abs().max().item() == 0 and grads["dx"][:n].abs().max().item() == 0
+        assert c["ref"]["dx"][n:].abs().max().item() > 0
+        assert c["ref"]["d_h_in"].abs().max().item() == 0 and grads["d_h_in"].abs().max().item() == 0
     assert max(errs.values()) <= BOUND, errs
 
 
-def _raw(rnn, T, N, kind):
-    """hcm_op_state_scan_train and hcm_op_state_scan_bwd through the C ABI on one case's inputs"""
-    c = _case(rnn, T, N, kind)
+@pytest.mark.parametrize("T,N,kind", sc.SATURATED_CASES)
+@pytest.mark.parametrize("rnn", ["LSTM", "GRU"])
+def test_gradients_match_float64_autograd_with_saturated_gates(rnn, T, N, kind):
+    """weight_ih times 20: about a fifth of the input-side pre-activations pass +-6, so g (1 - g) and 1 - n^2 round towards zero.  The bound is the
+    one above; tests/test_train_coverage_cpu.py holds the float32 CPU restatement to half of it on the same inputs."""
+    c = _case(rnn, T, N, kind, sc.SATURATED_IH_SCALE)
+    seq, hid, grads = _gpu_grads(rnn, T, N, kind, sc.SATURATED_IH_SCALE)
+    e_s, e_h = (seq.double() - c["seq64"]).abs().max().item(), (hid.double() - c["hid64"]).abs().max().item()
+    print(f"[{rnn} T={T} N={N} {kind} saturated] seq {e_s:.3e} hidden {e_h:.3e}")
+    assert e_s <= 1e-5 and e_h <= 1e-5
+    errs = {k: _rel(grads[k], c["ref"][k], f"[{rnn} T={T} N={N} {kind} saturated] {k}") for k in NAMES}
+    assert max(errs.values()) <= BOUND, errs
+
+
+def _raw(rnn, T, N, kind, ih_scale=1.0, fill=None):
+    """hcm_op_state_scan_train and hcm_op_state_scan_bwd through the C ABI on one case's inputs; every output starts as `fill` where one is given"""
+    c = _case(rnn, T, N, kind, ih_scale)
     lstm = rnn == "LSTM"
     G = 4 if lstm else 3
     w_ih, w_hh, b_ih, b_hh = (t.cuda() for t in c["p"])
@@ -106,9 +95,9 @@ def _raw(rnn, T, N, kind):
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     pt = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     lib = _lib.lib()
-    o = dict(seq=torch.empty(T * N, H, device="cuda"), h_out=torch.empty_like(h_in), gates=torch.full((T * N, 4 * H), float("nan"), device="cuda"),
-             c_seq=torch.empty(T * N, H, device="cuda") if lstm else None, d_pre=torch.empty(T * N, G * H, device="cuda"),
-             d_gh=None if lstm else torch.empty(T * N, G * H, device="cuda"), d_h_in=torch.empty_like(h_in))
+    new = (lambda *s: torch.empty(*s, device="cuda")) if fill is None else (lambda *s: torch.full(s, fill, device="cuda"))
+    o = dict(seq=new(T * N, H), h_out=new(*h_in.shape), gates=torch.full((T * N, 4 * H), float("nan"), device="cuda"),
+             c_seq=new(T * N, H) if lstm else None, d_pre=new(T * N, G * H), d_gh=None if lstm else new(T * N, G * H), d_h_in=new(*h_in.shape))
     work = torch.empty(4 * H * H + 4 * N * H, device="cuda")
     bh = None if lstm else b_hh
     assert lib.hcm_op_state_scan_train(pt(pre), pt(w_hh), pt(bh), pt(h_in), pt(m), pt(o["seq"]), pt(o["h_out"]), pt(o["gates"]), pt(o["c_seq"]), pt(work),
@@ -148,7 +137,7 @@ def _saved64(rnn, T, N, kind):
     return torch.cat(gates, 0), (torch.cat(cs, 0) if cs else None)
 
 
-@pytest.mark.parametrize("T,N", SHAPES)
+@pytest.mark.parametrize("T,N", RAW_SHAPES)
 @pytest.mark.parametrize("rnn", ["LSTM", "GRU"])
 def test_training_forward_is_the_forward_scan_bitwise_and_saves_the_gates(rnn, T, N):
     o, seq0, h_out0 = _raw(rnn, T, N, "random")
@@ -158,6 +147,19 @@ def test_training_forward_is_the_forward_scan_bitwise_and_saves_the_gates(rnn, T
     e_c = (o["c_seq"].cpu().double() - c64).abs().max().item() if c64 is not None else 0.0
     print(f"[{rnn} T={T} N={N}] saved gates {e_g:.3e} c_seq {e_c:.3e}")
     assert e_g <= 1e-5 and e_c <= 1e-5              # (gates start as NaN: every element was written)
+
+
+@pytest.mark.parametrize("T,N,kind,ih_scale", [(33, 5, "random", 1.0), (6, 13, "random", 1.0), (8, 5, "cut", 1.0), (12, 5, "random", sc.SATURATED_IH_SCALE)])
+@pytest.mark.parametrize("rnn", ["LSTM", "GRU"])
+def test_two_runs_give_the_same_bits_at_the_horizon_and_the_edges(rnn, T, N, kind, ih_scale):
+    """outputs pre-filled with NaN: fully written, and the same bits on a second run"""
+    nan = float("nan")
+    a, _, _ = _raw(rnn, T, N, kind, ih_scale, fill=nan)
+    b, _, _ = _raw(rnn, T, N, kind, ih_scale, fill=nan)
+    for k, t in a.items():
+        if t is not None:
+            assert not t.isnan().any(), k
+            assert torch.equal(t, b[k]), k
 
 
 @pytest.mark.parametrize("rnn", ["LSTM", "GRU"])
