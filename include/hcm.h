@@ -778,6 +778,36 @@ int hcm_op_instr_scan_bwd(const float* d_out, const float* d_final, const float*
 int hcm_op_instr_scan_infer(const float* pre, const float* wt, const float* b_hn, const int32_t* lengths, float* out, int B, int L, int hidden, int dirs,
                             int rnn_type, int final_only, void* stream);
 
+/* CMANet's attention stage (models/cma.py:271-311) in float32 with a backward pass (csrc/cma_attn_train.hip).  Every _attn call there has one query
+ * per sample and keys that are a 1x1 convolution of the raw tokens X, so with qt = q W_k (the caller's product; q.b_k is the same for every
+ * position and cancels in the softmax) and X = [x | e], C = C0 + Ce channels and I positions:
+ *   a = softmax_i(scale (x_i . qt - 1e8 mask_i)),   xbar = sum_i a_i x_i       (text: xbar is the output; RGB / depth: out = xbar W_v^T + b_v)
+ *   qt (B, C); x (B, I, C0) with layout = HCM_ATTN_TOKEN_MAJOR (the instruction encoder's output as hcm_op_instr_scan_train stores it) or (B, C0, I)
+ *   with HCM_ATTN_CHANNEL_MAJOR (the reference's NCHW trunk feature, flattened); e (I, Ce): Ce further channels shared by all samples (the spatial
+ *   embedding, read where it lies -- no concatenated copy), or NULL with Ce = 0; all float32 on the device.
+ *   mask_zero != 0: position i of sample b is masked exactly when all C channels compare == 0.0f (-0.0 counts, NaN does not; cma.py:273), derived
+ *   in the pass that forms the logits; 1e8 is subtracted before the scale as the reference writes it, so a fully masked sample gets uniform
+ *   weights and xbar = exact zeros.
+ * hcm_op_attn1q_train, ONE launch, writes a (B, I) and xbar (B, C).  It needs no work buffer; `work` may be NULL.
+ * hcm_op_attn1q_bwd takes d_xbar (B, C) and qt, x, e, a, layout, scale as the forward had them, and writes, with da_i = x_i . d_xbar and
+ *   dlog_i = scale a_i (da_i - sum_j a_j da_j):   d_qt (B, C) = sum_i dlog_i x_i;   d_x[c, i] = d_xbar_c a_i + qt_c dlog_i in x's layout, or NULL:
+ *   not computed (frozen features);   d_e (I, Ce) = the same expression over the tail channels summed over the samples -- required exactly when e
+ *   is given; per-sample partials in `work`, summed in sample order by a second launch.
+ * work: hcm_op_attn1q_work_floats(B, C0, Ce, I) floats (B I Ce; 0 for unsupported sizes) owned by the caller, required by the backward when e is
+ *   given.  No output may overlap it.  The kernels move 16 bytes per lane where the shape keeps every access aligned (token-major: C0 % 4 == 0;
+ *   channel-major: I % 4 == 0) and a dword otherwise, chosen per call; every sum runs in an order fixed by (layout, C0, Ce, I).
+ * HCM_ERR_ARG with a message (hcm_last_error(NULL)), never a launch: a NULL required pointer, e and Ce disagreeing, I outside 1..256, C above
+ *   4096, Ce % 4 != 0, an unknown layout, an output overlapping work, a float tensor that is not 16-byte aligned.
+ * B = 0: HCM_OK; the backward writes zeros to d_e; nothing else is touched and the per-sample pointers may be NULL.
+ * The ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible. */
+#define HCM_ATTN_TOKEN_MAJOR 0
+#define HCM_ATTN_CHANNEL_MAJOR 1
+int64_t hcm_op_attn1q_work_floats(int B, int C0, int Ce, int I);
+int hcm_op_attn1q_train(const float* qt, const float* x, const float* e, int layout, int mask_zero, float scale, float* a, float* xbar, float* work,
+                        int B, int C0, int Ce, int I, void* stream);
+int hcm_op_attn1q_bwd(const float* d_xbar, const float* qt, const float* x, const float* e, const float* a, int layout, float scale, float* d_qt,
+                      float* d_x, float* d_e, float* work, int B, int C0, int Ce, int I, void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

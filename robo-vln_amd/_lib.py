@@ -12,6 +12,7 @@ HCM_FEATURES = 6            # as rgb_dtype: `rgb` is a host hcm_features* (HcmFe
 HCM_HIGH, HCM_LOW, HCM_CMA, HCM_S2S = 0, 1, 2, 3
 HCM_ENC_RESNET, HCM_ENC_SIMPLECNN = 0, 1
 HCM_LSTM, HCM_GRU = 0, 1
+HCM_ATTN_TOKEN_MAJOR, HCM_ATTN_CHANNEL_MAJOR = 0, 1
 (HCM_NUM_RECURRENT_LAYERS, HCM_HIDDEN_SIZE, HCM_NUM_ACTIONS, HCM_RECORD_WIDTH, HCM_WORKSPACE_BYTES,
  HCM_WEIGHT_BYTES, HCM_MAX_BATCH, HCM_GRAPH_LAUNCHES, HCM_EAGER_LAUNCHES, HCM_FP16_FALLBACK, HCM_CALIB_MAX_BERT, HCM_CALIB_MAX_DEPTH,
  HCM_CALIB_NONFINITE, HCM_CALIB_MAX_RGB, HCM_CALIB_MAX_VLA, HCM_STEP_NONFINITE, HCM_RANGE_FOLD, HCM_GATHER_JOINED) = range(18)
@@ -151,7 +152,10 @@ EXPORTS = {
     "hcm_op_instr_scan_train": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 5 + [C.c_void_p]),
     "hcm_op_instr_scan_bwd": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_void_p]),
     "hcm_op_instr_scan_infer": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
-    "hcm_op_feat_ingest": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "hcm_op_attn1q_work_floats": (C.c_int64, [C.c_int] * 4),
+    "hcm_op_attn1q_train": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_attn1q_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_float] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_feat_ingest":(C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
 }

@@ -1907,6 +1907,57 @@ int hcm_op_instr_scan_infer(const float* pre, const float* wt, const float* b_hn
                                         out, B, L, hidden, dirs, dirs * hidden, (hipStream_t)stream));
 }
 
+int64_t hcm_op_attn1q_work_floats(int B, int C0, int Ce, int I) {
+    return attn1q_train_ok(B, C0, Ce, I) ? (int64_t)attn1q_train_work_floats(B, C0, Ce, I) : 0;
+}
+
+static int attn1q_arg_err(const char* what) {
+    g_create_err = std::string("attn1q: ") + what;
+    return HCM_ERR_ARG;
+}
+// layout, sizes and the tail of the two attn1q ops
+static int attn1q_dims(const float* e, int layout, int B, int C0, int Ce, int I) {
+    if (layout != HCM_ATTN_TOKEN_MAJOR && layout != HCM_ATTN_CHANNEL_MAJOR) return attn1q_arg_err("layout must be HCM_ATTN_TOKEN_MAJOR or HCM_ATTN_CHANNEL_MAJOR");
+    if (B < 0 || C0 < 1 || Ce < 0) return attn1q_arg_err("B and Ce must be at least 0, C0 at least 1");
+    if (I < 1 || I > 256) return attn1q_arg_err("I must be in 1..256");
+    if ((int64_t)C0 + Ce > 4096) return attn1q_arg_err("C0 + Ce must be at most 4096");
+    if (Ce % 4) return attn1q_arg_err("Ce must be a multiple of 4");
+    if ((e != nullptr) != (Ce > 0)) return attn1q_arg_err("e is given exactly when Ce > 0");
+    return HCM_OK;
+}
+
+int hcm_op_attn1q_train(const float* qt, const float* x, const float* e, int layout, int mask_zero, float scale, float* a, float* xbar, float* work,
+                        int B, int C0, int Ce, int I, void* stream) {
+    const int rc = attn1q_dims(e, layout, B, C0, Ce, I);
+    if (rc != HCM_OK) return rc;
+    if (B == 0) return HCM_OK;
+    if (!qt || !x || !a || !xbar) return attn1q_arg_err("a required pointer is NULL");
+    if (!vla_train_aligned({qt, x, e, a, xbar, work}, {})) return attn1q_arg_err("float tensors must be 16-byte aligned");
+    if (work && vla_train_in_work(work, attn1q_train_work_floats(B, C0, Ce, I), {{a, (size_t)B * I}, {xbar, (size_t)B * (C0 + Ce)}}))
+        return attn1q_arg_err("an output overlaps work");
+    Attn1qTrainArgs t;
+    t.qt = qt; t.x = x; t.e = e; t.layout = layout; t.mask_zero = mask_zero; t.scale = scale; t.a = a; t.xbar = xbar; t.work = work;
+    t.B = B; t.C0 = C0; t.Ce = Ce; t.I = I;
+    return op_rc(launch_attn1q_train_fwd(t, (hipStream_t)stream));
+}
+
+int hcm_op_attn1q_bwd(const float* d_xbar, const float* qt, const float* x, const float* e, const float* a, int layout, float scale, float* d_qt,
+                      float* d_x, float* d_e, float* work, int B, int C0, int Ce, int I, void* stream) {
+    const int rc = attn1q_dims(e, layout, B, C0, Ce, I);
+    if (rc != HCM_OK) return rc;
+    if ((d_e != nullptr) != (Ce > 0)) return attn1q_arg_err("d_e is required exactly when e is given");
+    if (Ce && B && !work) return attn1q_arg_err("work is required when e is given");
+    if (B && (!d_xbar || !qt || !x || !a || !d_qt)) return attn1q_arg_err("a required pointer is NULL");
+    if (!vla_train_aligned({d_xbar, qt, x, e, a, d_qt, d_x, d_e, work}, {})) return attn1q_arg_err("float tensors must be 16-byte aligned");
+    const size_t C = (size_t)C0 + Ce;
+    if (work && vla_train_in_work(work, attn1q_train_work_floats(B, C0, Ce, I), {{d_qt, B * C}, {d_x, (size_t)B * C0 * I}, {d_e, (size_t)I * Ce}}))
+        return attn1q_arg_err("an output overlaps work");
+    Attn1qTrainArgs t;
+    t.d_xbar = d_xbar; t.qt = qt; t.x = x; t.e = e; t.a = const_cast<float*>(a); t.layout = layout; t.scale = scale;
+    t.d_qt = d_qt; t.d_x = d_x; t.d_e = d_e; t.work = work; t.B = B; t.C0 = C0; t.Ce = Ce; t.I = I;
+    return op_rc(launch_attn1q_train_bwd(t, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

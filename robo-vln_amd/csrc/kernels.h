@@ -379,6 +379,25 @@ hipError_t launch_instr_scan_train(const float* pre, const float* w_hh, const fl
                                    float* cseq, float* work, int B, int L, int H, int dirs, int gru, hipStream_t s);
 hipError_t launch_instr_scan_bwd(const float* d_out, const float* d_fin, const float* gates, const float* cseq, const float* out, const float* w_hh,
                                  const int* lengths, float* work, float* d_pre, float* d_gh, int B, int L, int H, int dirs, int gru, hipStream_t s);
+// CMANet's attention stage in float32 with a backward pass (cma_attn_train.hip), one query per sample with the key projection folded into the
+// query:  a = softmax(scale (X^T qt - 1e8 mask)),  xbar = X a,  X = [x | e] with C = C0 + Ce channels and I positions.  x is (B, I, C0)
+// (layout 0, token-major) or (B, C0, I) (layout 1, channel-major); e (I, Ce) is a channel tail shared by all samples, or null with Ce = 0.
+// One argument block for both directions, as VlaTrainArgs.  work: attn1q_train_work_floats() floats, the per-sample d_e partials (0 with Ce = 0).
+// No allocation, no host copy, no synchronisation, no atomics.
+struct Attn1qTrainArgs {
+    const float *qt = nullptr, *x = nullptr, *e = nullptr;                     // [B][C], layout above, [I][Ce] or null
+    int layout = 0, mask_zero = 0;
+    float scale = 1.f;
+    float *a = nullptr, *xbar = nullptr;                                       // forward out / backward in (a): [B][I], [B][C]
+    const float* d_xbar = nullptr;                                             // [B][C]
+    float *d_qt = nullptr, *d_x = nullptr, *d_e = nullptr;                     // [B][C], x's layout or null (not computed), [I][Ce] or null
+    float* work = nullptr;
+    int B = 0, C0 = 0, Ce = 0, I = 0;
+};
+bool attn1q_train_ok(int B, int C0, int Ce, int I);
+size_t attn1q_train_work_floats(int B, int C0, int Ce, int I);
+hipError_t launch_attn1q_train_fwd(const Attn1qTrainArgs& t, hipStream_t s);
+hipError_t launch_attn1q_train_bwd(const Attn1qTrainArgs& t, hipStream_t s);
 // dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
 // out[r][0..H) = all[b][max(len_b, 1) - 1][0..H) with b = (Bi == 1 ? 0 : r): the last active step of an all-outputs scan (len_b == 0: zeros)
 hipError_t launch_gather_last(const float* all, const int* lengths, float* out, int Bi, int rows, int L, int H, int ld_out, hipStream_t s);

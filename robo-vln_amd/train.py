@@ -19,7 +19,12 @@ drop-in module around `InterModuleAttnLayer`.
 Differentiable instruction encoder: the reference's InstructionEncoder (models/encoders/instruction_encoder.py:70-92), a packed nn.LSTM / nn.GRU
 with hidden size 256 in one or two directions, with the whole scan forward and the whole scan backward one launch each (csrc/instr_scan_train.hip)
 and the lengths read on the device.  `instr_scan` is the autograd function, `instr_encoder_ref` the pure-torch restatement, `InstructionEncoder`
-the drop-in module."""
+the drop-in module.
+
+Differentiable CMANet: the reference's flat baseline (models/cma.py) from cached trunk features.  Its attention stage (cma.py:271-311) has one query
+per sample and keys that are a 1x1 convolution of the raw tokens, so the key projection folds into the query (qt = q W_k; q.b_k cancels in the
+softmax) and K and V are never formed: `attn1q` is the autograd function over csrc/cma_attn_train.hip, `attn1q_ref` the pure-torch restatement,
+`CMANet` the trainable model around it, `InstructionEncoder` and two `RNNStateEncoder`s."""
 import ctypes as C
 import math
 
@@ -768,3 +773,238 @@ class InstructionEncoder(nn.Module):
                 raise ValueError(f"on the device InstructionEncoder serves hidden_size {INSTR_HIDDEN} (got {self.hidden_size})")
             y = instr_scan(embedded, lengths, self._params(), self.final_state_only)
         return y if self.final_state_only else y.permute(0, 2, 1)
+
+
+TOKEN_MAJOR, CHANNEL_MAJOR = _lib.HCM_ATTN_TOKEN_MAJOR, _lib.HCM_ATTN_CHANNEL_MAJOR
+ATTN1Q_MAX_I, ATTN1Q_MAX_C = 256, 4096
+
+
+def attn1q_access(layout, C0, I):
+    """Bytes per lane the kernels move for x of this shape (the launcher's rule, csrc/cma_attn_train.hip): 16 where the shape keeps every access on a
+    16-byte boundary -- token-major rows with C0 % 4 == 0, channel-major rows with I % 4 == 0 -- and 4 otherwise"""
+    return 16 if (C0 if layout == TOKEN_MAJOR else I) % 4 == 0 else 4
+
+
+def attn1q_ref(qt, x, e, mask_zero, scale, layout, _taps=None):
+    """Pure-torch restatement of CMANet's attention with the key projection folded into the query, any dtype and device: qt (B, C0 + Ce) = q W_k;
+    x (B, I, C0) with layout TOKEN_MAJOR or (B, C0, I) with CHANNEL_MAJOR; e (I, Ce), a tail of further channels shared by all samples, or None.
+    a = softmax(scale (X^T qt - 1e8 mask)) and the result is xbar = X a (B, C0 + Ce); with mask_zero a position is masked exactly when all its
+    channels compare == 0 (cma.py:273), and 1e8 leaves the logit before the scale, as the reference writes it (cma.py:205-207)."""
+    X = x if layout == TOKEN_MAJOR else x.transpose(1, 2)
+    C0 = X.shape[2]
+    logits = torch.einsum("bic,bc->bi", X, qt[:, :C0])
+    if e is not None:
+        logits = logits + qt[:, C0:] @ e.t()
+    if mask_zero:
+        mask = (X == 0).all(2)
+        if e is not None:
+            mask = mask & (e == 0).all(1)[None]
+        logits = logits - mask.to(logits.dtype) * 1e8
+    a = torch.softmax(logits * scale, 1)
+    if _taps is not None:
+        _taps["a"] = a
+    xbar = torch.einsum("bi,bic->bc", a, X)
+    return xbar if e is None else torch.cat([xbar, a @ e], 1)
+
+
+class _Attn1q(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qt, x, e, mask_zero, scale, layout):
+        if not qt.is_cuda:
+            raise ValueError("attn1q runs on the device; CPU tensors go through attn1q_ref")
+        for name, t in (("x", x), ("e", e)):
+            if t is not None and t.device != qt.device:   # the kernels take raw pointers: a host pointer would fault on the device
+                raise ValueError(f"attn1q: {name} is on {t.device}, qt on {qt.device}")
+        if layout not in (TOKEN_MAJOR, CHANNEL_MAJOR):
+            raise ValueError(f"attn1q: layout must be TOKEN_MAJOR or CHANNEL_MAJOR, got {layout!r}")
+        if x.dim() != 3 or qt.dim() != 2 or x.shape[0] != qt.shape[0] or (e is not None and e.dim() != 2):
+            raise ValueError(f"attn1q takes qt (B, C), x (B, I, C0) or (B, C0, I) and e (I, Ce), got {tuple(qt.shape)}, {tuple(x.shape)}, "
+                             f"{None if e is None else tuple(e.shape)}")
+        B = x.shape[0]
+        I, C0 = (x.shape[1], x.shape[2]) if layout == TOKEN_MAJOR else (x.shape[2], x.shape[1])
+        Ce = 0 if e is None else e.shape[1]
+        if B < 1 or C0 < 1 or not 1 <= I <= ATTN1Q_MAX_I or C0 + Ce > ATTN1Q_MAX_C or Ce % 4 or (e is not None and (Ce < 1 or e.shape[0] != I)) \
+                or qt.shape[1] != C0 + Ce:
+            raise ValueError(f"attn1q serves B >= 1, 1..{ATTN1Q_MAX_I} positions, C0 + Ce <= {ATTN1Q_MAX_C} channels with Ce a multiple of 4, e (I, Ce) and "
+                             f"qt (B, C0 + Ce), got B {B}, I {I}, C0 {C0}, e {None if e is None else tuple(e.shape)}, qt {tuple(qt.shape)}")
+        qt, x = _f32c(qt), _f32c(x)
+        e = None if e is None else _f32c(e)
+        a = torch.empty(B, I, device=qt.device)
+        xbar = torch.empty(B, C0 + Ce, device=qt.device)
+        _lib.check(_lib.lib().hcm_op_attn1q_train(_ptr(qt), _ptr(x), _ptr(e), layout, int(bool(mask_zero)), scale, _ptr(a), _ptr(xbar), None,
+                                                  B, C0, Ce, I, _stream()))
+        ctx.save_for_backward(qt, x, e, a)
+        ctx.dims = (B, C0, Ce, I, layout, scale)
+        return xbar
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_xbar):
+        qt, x, e, a = ctx.saved_tensors
+        B, C0, Ce, I, layout, scale = ctx.dims
+        need = ctx.needs_input_grad
+        d_xbar = _f32c(d_xbar)
+        d_qt = torch.empty_like(qt)
+        d_x = torch.empty_like(x) if need[1] else None
+        d_e = torch.empty_like(e) if e is not None else None
+        n = _lib.lib().hcm_op_attn1q_work_floats(B, C0, Ce, I)
+        work = torch.empty(n, device=qt.device) if n else None
+        _lib.check(_lib.lib().hcm_op_attn1q_bwd(_ptr(d_xbar), _ptr(qt), _ptr(x), _ptr(e), _ptr(a), layout, scale, _ptr(d_qt), _ptr(d_x), _ptr(d_e),
+                                                _ptr(work), B, C0, Ce, I, _stream()))
+        return d_qt if need[0] else None, d_x, d_e if need[2] else None, None, None, None
+
+
+def attn1q(qt, x, e, mask_zero, scale, layout):
+    """CMANet's attention with one query per sample (float32, on the device) with gradients to qt, x and e: arguments and result as attn1q_ref;
+    1..256 positions, at most 4096 channels, Ce a multiple of 4; x in either layout is read where it lies, and so is e: no (B, C0 + Ce, I) tensor
+    is formed.
+
+    Forward: hcm_op_attn1q_train, one launch with one workgroup per sample, derives the mask in the pass that forms the logits and saves the
+    weights a (B, I); K and V do not exist.  Backward: hcm_op_attn1q_bwd, one launch for d_qt (and d_x, computed only when x requires a gradient:
+    with frozen trunk features it never is) plus an ordered reduce over the samples for d_e.  The projections around it -- qt = q W_k,
+    xbar W_v^T + b_v -- are dense products and stay in torch.  Nothing is cached between calls."""
+    return _Attn1q.apply(qt, x, e, bool(mask_zero), float(scale), int(layout))
+
+
+class _CancelledBias(torch.autograd.Function):
+    """y unchanged; `bias` -- a key projection's bias, which cancels in the softmax and takes no part in the forward -- receives a gradient of
+    exact zeros, not None, so that an optimizer treats it as the reference's does"""
+
+    @staticmethod
+    def forward(ctx, y, bias):
+        ctx.save_for_backward(bias)
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, torch.zeros_like(ctx.saved_tensors[0])
+
+
+class _SpatialEncoder(nn.Module):
+    """What a spatial encoder of the reference keeps outside its frozen trunk: the (positions, 64) table under `spatial_embeddings.weight`"""
+
+    def __init__(self, positions):
+        super().__init__()
+        self.spatial_embeddings = nn.Embedding(positions, 64)
+
+    def tail(self):
+        """(channels-major (64, I), kernel operand (I, 64)): the reference appends the table as `.view(1, -1, h, w)` (resnet_encoders.py:91-104,
+        :218-231) -- a raw reinterpretation of the (I, 64) storage as 64 channels of I positions, not a transpose -- so channel c of position i
+        is element c * I + i of the table"""
+        w = self.spatial_embeddings.weight
+        cm = w.view(64, w.shape[0])
+        return cm, cm.t().contiguous()
+
+
+CMA_TRUNK_PREFIXES = ("rgb_encoder.cnn.", "depth_encoder.visual_encoder.")
+
+
+class CMANet(nn.Module):
+    """The reference's CMANet (models/cma.py:28-333) as a trainable model from cached trunk features: the reference's parameters, buffer, state-dict
+    keys and shapes outside the two frozen trunks (robo_vln_amd.synth.cma_spec lists them), and its forward signature.  Takes a
+    robo_vln_amd.config.CMAConfig; `embeddings=` goes to InstructionEncoder.
+
+    forward((observations, rnn_hidden_states, prev_actions, masks)) -> (output, stop_out, rnn_hidden_states) as cma.py:211-333, with
+    observations["rgb_features"] (rows, 2048, 4, 4) and ["depth_features"] (rows, C, s, s) -- what CMAEngine.encode_features returns; an ablated
+    modality needs no key -- and ["instruction"] (rows, L) or (1, L).  The returned state is a new tensor (the reference writes into its argument).
+
+    The three attention stages are attn1q on the device and attn1q_ref on the CPU: text attention with qt = state_q(state) W_text_k over the
+    instruction encoder's (rows, L, D) output, token-major and masked; RGB and depth attention with qt = text_q(text) W_k over the trunk feature,
+    channel-major, with the spatial embedding as the shared tail, and the value projection xbar W_v^T + b_v behind it.  The instruction encoder is
+    train.InstructionEncoder and both state encoders train.RNNStateEncoder; the linear layers around them are torch.  rgb_linear and depth_linear
+    take the feature and the embedding as two operands, so no (rows, C + 64, I) tensor exists.  The key biases -- text_k.bias and the first
+    hidden/2 entries of rgb_kv.bias and depth_kv.bias -- cancel and receive exact zero gradients.  `_scale` is kept as the reference's buffer; the
+    stages use its constructor value 1 / sqrt(hidden / 2) as a host number, so nothing is read back from the device."""
+
+    def __init__(self, cfg, embeddings=None):
+        super().__init__()
+        cfg.validate()
+        self.cfg = cfg
+        hh, fs, cc = cfg.hidden // 2, cfg.depth_final_spatial(), cfg.depth_compress_channels()
+        self.hh, self.depth_shape = hh, (cc, fs * fs)
+        self.instruction_encoder = InstructionEncoder(vocab_size=cfg.vocab_size, embedding_size=cfg.embedding_size, hidden_size=cfg.instr_hidden,
+                                                      rnn_type=cfg.instr_rnn, bidirectional=cfg.bidirectional, final_state_only=False,
+                                                      fine_tune_embeddings=True, embeddings=embeddings)
+        self.depth_encoder = _SpatialEncoder(fs * fs)
+        self.rgb_encoder = _SpatialEncoder(16)
+        self.rgb_linear = nn.Sequential(nn.AdaptiveAvgPool1d(1), nn.Flatten(), nn.Linear(2048 + 64, cfg.rgb_out), nn.ReLU(True))
+        self.depth_linear = nn.Sequential(nn.Flatten(), nn.Linear((cc + 64) * fs * fs, cfg.depth_out), nn.ReLU(True))
+        self.state_encoder = RNNStateEncoder(cfg.rgb_out + cfg.depth_out, cfg.hidden, 1, cfg.rnn_type)
+        self.rgb_kv = nn.Conv1d(2048 + 64, hh + cfg.rgb_out, 1)
+        self.depth_kv = nn.Conv1d(cc + 64, hh + cfg.depth_out, 1)
+        self.state_q = nn.Linear(cfg.hidden, hh)
+        self.text_k = nn.Conv1d(cfg.instr_out, hh, 1)
+        self.text_q = nn.Linear(cfg.instr_out, hh)
+        self.scale = 1.0 / (hh ** 0.5)
+        self.register_buffer("_scale", torch.tensor(self.scale))
+        self.second_state_compress = nn.Sequential(nn.Linear(cfg.hidden + cfg.rgb_out + cfg.depth_out + cfg.instr_out, cfg.hidden), nn.ReLU(True))
+        self.second_state_encoder = RNNStateEncoder(cfg.hidden, cfg.hidden, 1, cfg.rnn_type)
+        self.progress_monitor = nn.Linear(cfg.hidden, 1)      # parameters only: the progress-monitor loss is not built (CMAConfig refuses the flag)
+        self.linear = nn.Linear(cfg.hidden, cfg.num_actions)
+        self.stop_linear = nn.Linear(cfg.hidden, 1)
+
+    @property
+    def num_recurrent_layers(self):
+        return self.state_encoder.num_recurrent_layers + self.second_state_encoder.num_recurrent_layers
+
+    def load_reference_state_dict(self, sd):
+        """Load a reference CMANet state dict (tensors or arrays): the keys of the two frozen trunks are dropped, everything else is strict --
+        a missing, unexpected or misshapen key raises"""
+        kept = {k: torch.as_tensor(v) for k, v in sd.items() if not k.startswith(CMA_TRUNK_PREFIXES)}
+        return self.load_state_dict(kept, strict=True)
+
+    def _attend(self, q, w_k, x, e, mask_zero, layout, kernel=True):
+        fn = attn1q if kernel and x.is_cuda else attn1q_ref
+        return fn(q @ w_k, x, e, mask_zero, self.scale, layout)
+
+    def _visual(self, name, feat, enc, fc, pooled, ablated, rows, C0, I, like):
+        """One modality's operands: (x (rows, C0, I), e (I, 64), input of the first state encoder (rows, out)) from the trunk feature.  The
+        visual FC takes the feature and the embedding as two operands: rgb_linear pools over the positions first (AdaptiveAvgPool1d(1)),
+        depth_linear flattens in NCHW order.  Ablated: zeros for the whole embedding, the spatial tail included (cma.py:238-241)."""
+        if ablated:
+            return like.new_zeros(rows, C0, I), like.new_zeros(I, 64), torch.relu(fc.bias).expand(rows, -1)
+        s = int(round(I ** 0.5))
+        if feat is None:
+            raise ValueError(f"CMANet trains from cached trunk features: observations['{name}_features'] is missing; CMAEngine.encode_features "
+                             "returns it from the frames")
+        if feat.dim() != 4 or tuple(feat.shape) != (rows, C0, s, s):
+            raise ValueError(f"CMANet takes {name}_features ({rows}, {C0}, {s}, {s}) as CMAEngine.encode_features returns them, got {tuple(feat.shape)}")
+        x = feat.flatten(2)
+        cm, e = enc.tail()
+        if pooled:
+            x_in = torch.addmm(torch.nn.functional.linear(cm.mean(1), fc.weight[:, C0:], fc.bias), x.mean(2), fc.weight[:, :C0].t())
+        else:
+            x_in = torch.addmm(torch.nn.functional.linear(cm.reshape(-1), fc.weight[:, C0 * I:], fc.bias), x.flatten(1), fc.weight[:, :C0 * I].t())
+        return x, e, torch.relu(x_in)
+
+    def forward(self, batch, taps=None):
+        observations, rnn_hidden_states, prev_actions, masks = batch
+        cfg, hh = self.cfg, self.hh
+        masks = masks.reshape(masks.shape[0], -1)[:, 0]
+        rows = masks.shape[0]
+        R = self.state_encoder.num_recurrent_layers
+        instruction = observations["instruction"].long()
+        instruction = instruction.expand(rows, instruction.shape[1])
+        ins = self.instruction_encoder(instruction).permute(0, 2, 1)            # (rows, L, D): the encoder's own storage order
+        if cfg.ablate_instruction:
+            ins = ins * 0                                                       # every position masked: uniform weights, text = exact zeros
+        cc, I_d = self.depth_shape
+        rgb_x, rgb_e, rgb_in = self._visual("rgb", observations.get("rgb_features"), self.rgb_encoder, self.rgb_linear[2], True, cfg.ablate_rgb,
+                                            rows, 2048, 16, ins)
+        dep_x, dep_e, dep_in = self._visual("depth", observations.get("depth_features"), self.depth_encoder, self.depth_linear[1], False,
+                                            cfg.ablate_depth, rows, cc, I_d, ins)
+        state, h1 = self.state_encoder(torch.cat([rgb_in, dep_in], 1), rnn_hidden_states[:R], masks)
+
+        text = self._attend(self.state_q(state), self.text_k.weight[:, :, 0], ins, None, True, TOKEN_MAJOR)
+        text = _CancelledBias.apply(text, self.text_k.bias)
+        text_q = self.text_q(text)
+        att = []
+        for x, e, kv, ablated in ((rgb_x, rgb_e, self.rgb_kv, cfg.ablate_rgb), (dep_x, dep_e, self.depth_kv, cfg.ablate_depth)):
+            xbar = self._attend(text_q, kv.weight[:hh, :, 0], x, e, False, CHANNEL_MAJOR, kernel=not ablated)
+            att.append(torch.nn.functional.linear(xbar, kv.weight[hh:, :, 0], kv.bias[hh:]))
+
+        x = self.second_state_compress(torch.cat([state, text, att[0], att[1]], 1))
+        x, h2 = self.second_state_encoder(x, rnn_hidden_states[R:], masks)
+        if taps is not None:
+            taps.update(state=state, text=text, rgb_att=att[0], depth_att=att[1], rnn2_out=x)
+        return self.linear(x), self.stop_linear(x), torch.cat([h1, h2], 0)
