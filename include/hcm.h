@@ -741,7 +741,7 @@ int hcm_op_embed_ln_bwd(const float* d_y, const float* w, const float* gamma, co
                         float* work, float* d_pre, float* d_x, float* d_ln, int rows, int K, void* stream);
 
 /* The instruction encoder's packed scan (InstructionEncoder, models/encoders/instruction_encoder.py:70-92) in float32 with what a backward pass
- * needs, and its reverse-time scan (csrc/instr_scan_train.hip): nn.LSTM (HCM_LSTM, gates i,f,g,o) or nn.GRU (HCM_GRU, gates r,z,n), one layer,
+ * needs, and its reverse-time scan (csrc/instr_scan.hip): nn.LSTM (HCM_LSTM, gates i,f,g,o) or nn.GRU (HCM_GRU, gates r,z,n), one layer,
  * dirs = 1 or 2 directions, hidden 256, any B, L >= 1.  Row b is active at tokens t < lengths[b] (clamped to [0, L]) as in a packed sequence: the
  * reverse direction starts at the row's own last token, and a row of length 0 yields zeros everywhere and contributes nothing.  With G = 4 / 3:
  *   pre (dirs, B*L, G*256) = emb W_ih^T + bias per direction (LSTM: b_ih + b_hh; GRU: b_ih + (b_hr, b_hz, 0)); b_hn (dirs, 256): GRU's b_hn, which
@@ -772,9 +772,9 @@ int hcm_op_instr_scan_bwd(const float* d_out, const float* d_final, const float*
                           const int32_t* lengths, float* work, float* d_pre, float* d_gh, int B, int L, int hidden, int dirs, int rnn_type,
                           void* stream);
 /* A comparison hook for the tests, not an operator to build on (it checks sizes and NULLs, not alignment or overlap): the engines' existing
- * one-launch inference scans on their own (csrc/elementwise.hip), to hold hcm_op_instr_scan_train against: pre, b_hn and
- * lengths as above, wt (dirs, 256, 256, 4) = W_hh already in the forward order (what hcm_op_instr_scan_train leaves in `work`).  final_only != 0:
- * instr_final_scan_kernel, dirs = 1, out (B, 256); otherwise instr_lstm_scan_kernel, LSTM only, out (B, L, dirs*256). */
+ * one-launch inference scans on their own (the forms of csrc/instr_scan.hip's kernel without the saved tensors), to hold hcm_op_instr_scan_train
+ * against: pre, b_hn and lengths as above, wt (dirs, 256, 256, 4) = W_hh already in the forward order (what hcm_op_instr_scan_train leaves in
+ * `work`).  final_only != 0: the final-state form, dirs = 1, out (B, 256); otherwise the per-token form, LSTM only, out (B, L, dirs*256). */
 int hcm_op_instr_scan_infer(const float* pre, const float* wt, const float* b_hn, const int32_t* lengths, float* out, int B, int L, int hidden, int dirs,
                             int rnn_type, int final_only, void* stream);
 

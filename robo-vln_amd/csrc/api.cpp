@@ -1859,6 +1859,17 @@ static int instr_scan_dims(int B, int L, int hidden, int dirs, int rnn_type) {
     if (B < 1 || L < 1) return instr_arg_err("B and L must be at least 1");
     return HCM_OK;
 }
+// the forward scan's inputs from tensors stacked per direction: pre (dirs, B*L, G*256), wt (dirs, 256, 256, 4), b_hn (dirs, 256) or null
+static InstrScanArgs instr_scan_args(const float* pre, const float* wt, const float* b_hn, const int32_t* lengths, int B, int L, int dirs, bool gru) {
+    InstrScanArgs a;
+    for (int d = 0; d < dirs; ++d) {
+        a.pre[d] = pre + (size_t)d * B * L * (gru ? 3 : 4) * 256;
+        a.wt[d] = wt + (size_t)d * 4 * 256 * 256;
+        a.bhn[d] = b_hn ? b_hn + (size_t)d * 256 : nullptr;
+    }
+    a.lengths = lengths; a.B = B; a.L = L;
+    return a;
+}
 
 int hcm_op_instr_scan_train(const float* pre, const float* w_hh, const float* b_hn, const int32_t* lengths, float* out, float* final, float* gates,
                             float* c_seq, float* work, int B, int L, int hidden, int dirs, int rnn_type, void* stream) {
@@ -1872,7 +1883,11 @@ int hcm_op_instr_scan_train(const float* pre, const float* w_hh, const float* b_
     const size_t BL = (size_t)B * L, H = 256;
     if (vla_train_in_work(work, instr_scan_work_floats(dirs), {{out, BL * dirs * H}, {final, (size_t)B * H}, {gates, dirs * BL * 4 * H}, {c_seq, dirs * BL * H}}))
         return instr_arg_err("an output overlaps work");
-    return op_rc(launch_instr_scan_train(pre, w_hh, b_hn, lengths, out, final, gates, c_seq, work, B, L, hidden, dirs, gru ? 1 : 0, (hipStream_t)stream));
+    const hipError_t e = launch_instr_scan_pack_fwd(w_hh, work, dirs, gru ? 1 : 0, (hipStream_t)stream);
+    if (e != hipSuccess) return op_rc(e);
+    InstrScanArgs a = instr_scan_args(pre, work, b_hn, lengths, B, L, dirs, gru);
+    a.out = out; a.ld_out = dirs * hidden; a.fin = final; a.ld_fin = hidden; a.fin_rows = B; a.gates = gates; a.cseq = c_seq;
+    return op_rc(launch_instr_scan(a, dirs, gru ? 1 : 0, (hipStream_t)stream));
 }
 
 int hcm_op_instr_scan_bwd(const float* d_out, const float* d_final, const float* gates, const float* c_seq, const float* out, const float* w_hh,
@@ -1897,14 +1912,12 @@ int hcm_op_instr_scan_infer(const float* pre, const float* wt, const float* b_hn
     if (rc != HCM_OK) return rc;
     const bool gru = rnn_type == HCM_GRU;
     if (!pre || !wt || !lengths || !out || (gru && !b_hn)) return instr_arg_err("a required pointer is NULL");
-    if (final_only) {
-        if (dirs != 1) return instr_arg_err("the final-state scan has one direction");
-        return op_rc(launch_instr_final_scan(pre, wt, b_hn, lengths, out, B, B, L, hidden, gru ? 1 : 0, hidden, (hipStream_t)stream));
-    }
-    if (gru) return instr_arg_err("the engines have no one-launch full-output GRU scan");
-    const size_t BL = (size_t)B * L;
-    return op_rc(launch_instr_lstm_scan(pre, dirs == 2 ? pre + BL * 4 * hidden : nullptr, wt, dirs == 2 ? wt + (size_t)4 * hidden * hidden : nullptr, lengths,
-                                        out, B, L, hidden, dirs, dirs * hidden, (hipStream_t)stream));
+    if (final_only && dirs != 1) return instr_arg_err("the final-state scan has one direction");
+    if (!final_only && gru) return instr_arg_err("the engines have no one-launch full-output GRU scan");
+    InstrScanArgs a = instr_scan_args(pre, wt, b_hn, lengths, B, L, dirs, gru);
+    if (final_only) a.fin = out, a.ld_fin = hidden, a.fin_rows = B;
+    else a.out = out, a.ld_out = dirs * hidden;
+    return op_rc(launch_instr_scan(a, dirs, gru ? 1 : 0, (hipStream_t)stream));
 }
 
 int64_t hcm_op_attn1q_work_floats(int B, int C0, int Ce, int I) {

@@ -1356,242 +1356,6 @@ hipError_t launch_instr_lstm_cell(const float* pre, const float* gh, float* h, f
     return hipGetLastError();
 }
 
-// The whole packed (bi)LSTM scan in ONE launch: a workgroup owns SB samples of one direction for all L steps.  h lives in LDS
-// (double-buffered, broadcast reads), c in registers; W_hh is read from L2 every step, transposed and gate-interleaved ([k][unit][4
-// gates]: the four gate weights of (k, unit j) are one 16-byte load, coalesced across the units) -- 4*H*H*4 bytes per step and
-// workgroup.  SB is chosen small (2 for B = 64, both directions: 64 workgroups): per step a thread then does SB * 256 FMAs behind 64
-// 16-byte loads, and the step is bounded by that weight stream (1 MB from L2) instead of by 8 samples' worth of FMAs and LDS
-// broadcasts on 16 CUs (CMANet step at B = 64, L = 80: 3.15 -> 2.56 ms; the trunks alone take 2.4).
-struct LstmScanArgs {
-    const float* pre[2];       // per direction: x_t W_ih^T + b_ih + b_hh for every token, [B*L][4H]
-    const float* wt[2];        // per direction: W_hh as [H (k)][H (unit)][4 (gate)]
-};
-// 1024 threads = 256 hidden units x 4 quarters of the k range: each thread streams a quarter of its unit's recurrent weights
-// (64 k x 4 gates, several loads in flight) for SB samples; the four partial sums per (gate, sample, unit) meet in LDS.
-template <int SB>
-__global__ __launch_bounds__(1024) void instr_lstm_scan_kernel(LstmScanArgs a, const int* __restrict__ lengths, float* __restrict__ out,
-                                                                int B, int L, int H, int ld_out) {
-    extern __shared__ float sm[];          // h [2][SB][H], partials [3][4][SB][H]
-    float* hs = sm;
-    float* ps = sm + 2 * SB * H;
-    const int dir = blockIdx.y;
-    const int b0 = blockIdx.x * SB;
-    const int j = threadIdx.x & 255, kq = threadIdx.x >> 8;
-    const int KQ = H / 4;
-    const float* __restrict__ pre = a.pre[dir];
-    const float* __restrict__ wt = a.wt[dir] + ((size_t)kq * KQ * H + j) * 4;
-    float c[SB];
-#pragma unroll
-    for (int s_ = 0; s_ < SB; ++s_) c[s_] = 0.f;
-    for (int i = threadIdx.x; i < 2 * SB * H; i += 1024) hs[i] = 0.f;
-    __syncthreads();
-    int cur = 0;
-    for (int step = 0; step < L; ++step) {
-        const int t = dir ? L - 1 - step : step;
-        float acc[4][SB];
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int s_ = 0; s_ < SB; ++s_) acc[g][s_] = 0.f;
-        const float* hc = hs + cur * SB * H + kq * KQ;
-#pragma unroll 8
-        for (int k = 0; k < KQ; ++k) {
-            const float4 w4 = *reinterpret_cast<const float4*>(wt + (size_t)k * 4 * H);
-            const float w0 = w4.x, w1 = w4.y, w2 = w4.z, w3 = w4.w;
-#pragma unroll
-            for (int s_ = 0; s_ < SB; ++s_) {
-                const float hk = hc[s_ * H + k];
-                acc[0][s_] += w0 * hk; acc[1][s_] += w1 * hk; acc[2][s_] += w2 * hk; acc[3][s_] += w3 * hk;
-            }
-        }
-        if (kq > 0) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int s_ = 0; s_ < SB; ++s_) ps[(((kq - 1) * 4 + g) * SB + s_) * H + j] = acc[g][s_];
-        }
-        __syncthreads();
-        float* hn = hs + (cur ^ 1) * SB * H;
-        if (kq == 0) {
-#pragma unroll
-            for (int s_ = 0; s_ < SB; ++s_) {
-                const int b = b0 + s_;
-                const bool valid = b < B;
-                const bool act = valid && t < lengths[valid ? b : 0];
-                float hv = hs[cur * SB * H + s_ * H + j], o = 0.f;
-                if (act) {
-                    const float* p = pre + ((size_t)b * L + t) * 4 * H + j;
-                    float gsum[4];
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        gsum[g] = p[g * H] + ((acc[g][s_] + ps[((0 * 4 + g) * SB + s_) * H + j]) + (ps[((1 * 4 + g) * SB + s_) * H + j] + ps[((2 * 4 + g) * SB + s_) * H + j]));
-                    const float gi = sigmoidf_(gsum[0]), gf = sigmoidf_(gsum[1]), gg = tanhf(gsum[2]), go = sigmoidf_(gsum[3]);
-                    c[s_] = gf * c[s_] + gi * gg;
-                    hv = go * tanhf(c[s_]);
-                    o = hv;
-                }
-                hn[s_ * H + j] = hv;
-                if (valid) out[((size_t)b * L + t) * ld_out + dir * H + j] = o;
-            }
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-}
-hipError_t launch_instr_lstm_scan(const float* pre0, const float* pre1, const float* wt0, const float* wt1, const int* lengths, float* out,
-                                  int B, int L, int H, int dirs, int ld_out, hipStream_t s) {
-    if (H != 256) return hipErrorInvalidValue;          // 256 hidden units x 4 k-quarters = 1024 threads
-    LstmScanArgs a;
-    a.pre[0] = pre0; a.pre[1] = pre1; a.wt[0] = wt0; a.wt[1] = wt1;
-    // samples per workgroup: the fewest that keep the launch within one workgroup per CU
-    static const char* fsb = dev_env("HCM_LSTM_SB");
-    // (SB = 1 is not built: slower at B = 64 -- 128 workgroups take the CUs from the trunks running beside the scan -- and its
-    // instantiation showed run-to-run differences of ~3e-5 whose cause was not found; SB = 2 / 4 / 8 are bitwise reproducible, tested)
-    int SB = 2;
-    while (SB < 8 && ((B + SB - 1) / SB) * dirs > 128) SB *= 2;
-    if (fsb) SB = atoi(fsb);
-    const size_t lds = (size_t)(2 * SB * H + 3 * 4 * SB * H) * sizeof(float);
-    const void* fn = SB == 2 ? reinterpret_cast<const void*>(instr_lstm_scan_kernel<2>)
-                   : SB == 4 ? reinterpret_cast<const void*>(instr_lstm_scan_kernel<4>) : SB == 8 ? reinterpret_cast<const void*>(instr_lstm_scan_kernel<8>) : nullptr;
-    if (!fn) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    void* args[] = {&a, &lengths, &out, &B, &L, &H, &ld_out};
-    return hipLaunchKernel(fn, dim3((B + SB - 1) / SB, dirs), dim3(1024), args, lds, s);
-}
-
-// Seq2SeqNet's instruction encoder: InstructionEncoder with final_state_only (instruction_encoder.py:86-90; both Seq2Seq paper configs) returns ONE
-// vector per sample, the hidden state at the sample's own last token.  Same layout as instr_lstm_scan_kernel (W_hh transposed and gate-interleaved,
-// one 16-byte load per (k, unit); h double-buffered in LDS; c in registers; 256 units x 4 k-quarters), for nn.LSTM (i,f,g,o) and nn.GRU (r,z,n: the
-// fourth weight slot is zero and not accumulated; b_hn stays inside the r * (.) product as in torch), with three differences:
-//   - no per-token output: the only global store is the final h, straight into the state encoder's input row (out, ld_out);
-//   - a workgroup runs max(length) over the SB samples it owns, not L steps (the lengths are read on the device: nothing for the host to wait
-//     for, the launch is graph-capturable); a sample's state is frozen once t >= length[b];
-//   - Bi == 1 with rows > 1: one instruction for `rows` frames (seq2seq.py:163 `.expand`) -- one sample is scanned, its result written to every row.
-// pre = x_t W_ih^T + bias [Bi*L][NG*H]: LSTM bias b_ih + b_hh; GRU bias b_ih + (b_hr, b_hz, 0).  No atomics, fixed summation order: bitwise
-// reproducible (the k-quarter partials are added as ((q0 + q1) + (q2 + q3)), as in instr_lstm_scan_kernel).
-template <int SB, bool GRU>
-__global__ __launch_bounds__(1024) void instr_final_scan_kernel(const float* __restrict__ pre, const float* __restrict__ wt, const float* __restrict__ bhn,
-                                                                 const int* __restrict__ lengths, float* __restrict__ out, int Bi, int rows, int L, int H,
-                                                                 int ld_out) {
-    constexpr int NG = GRU ? 3 : 4;
-    extern __shared__ float sm[];          // h [2][SB][H], partials [3][NG][SB][H]
-    __shared__ int len_s[SB];
-    float* hs = sm;
-    float* ps = sm + 2 * SB * H;
-    const int b0 = blockIdx.x * SB;
-    const int j = threadIdx.x & 255, kq = threadIdx.x >> 8;
-    const int KQ = H / 4;
-    const float* __restrict__ wq = wt + ((size_t)kq * KQ * H + j) * 4;
-    if (threadIdx.x < SB) {
-        const int b = b0 + threadIdx.x;
-        int l = b < Bi ? lengths[b] : 0;               // samples past the batch never become active
-        len_s[threadIdx.x] = l < 0 ? 0 : l > L ? L : l;
-    }
-    for (int i = threadIdx.x; i < 2 * SB * H; i += 1024) hs[i] = 0.f;
-    __syncthreads();
-    int tmax = 0;                                      // workgroup-uniform: every thread reads the same SB words
-#pragma unroll
-    for (int s_ = 0; s_ < SB; ++s_) tmax = len_s[s_] > tmax ? len_s[s_] : tmax;
-    float c[SB];
-#pragma unroll
-    for (int s_ = 0; s_ < SB; ++s_) c[s_] = 0.f;
-    const float bn = GRU ? bhn[j] : 0.f;
-    int cur = 0;
-    for (int t = 0; t < tmax; ++t) {
-        float acc[NG][SB];
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-            for (int s_ = 0; s_ < SB; ++s_) acc[g][s_] = 0.f;
-        const float* hc = hs + cur * SB * H + kq * KQ;
-#pragma unroll 8
-        for (int k = 0; k < KQ; ++k) {
-            const float4 w4 = *reinterpret_cast<const float4*>(wq + (size_t)k * 4 * H);
-            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-            for (int s_ = 0; s_ < SB; ++s_) {
-                const float hk = hc[s_ * H + k];
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g][s_] += wv[g] * hk;
-            }
-        }
-        if (kq > 0) {
-#pragma unroll
-            for (int g = 0; g < NG; ++g)
-#pragma unroll
-                for (int s_ = 0; s_ < SB; ++s_) ps[(((kq - 1) * NG + g) * SB + s_) * H + j] = acc[g][s_];
-        }
-        __syncthreads();
-        float* hn = hs + (cur ^ 1) * SB * H;
-        if (kq == 0) {
-#pragma unroll
-            for (int s_ = 0; s_ < SB; ++s_) {
-                float hv = hs[cur * SB * H + s_ * H + j];
-                if (t < len_s[s_]) {                   // (len_s > 0 only for b0 + s_ < Bi: the read of `pre` is in bounds)
-                    const float* p = pre + ((size_t)(b0 + s_) * L + t) * NG * H + j;
-                    float rs[NG];
-#pragma unroll
-                    for (int g = 0; g < NG; ++g)
-                        rs[g] = (acc[g][s_] + ps[((0 * NG + g) * SB + s_) * H + j]) + (ps[((1 * NG + g) * SB + s_) * H + j] + ps[((2 * NG + g) * SB + s_) * H + j]);
-                    if (GRU) {
-                        const float r = sigmoidf_(p[0] + rs[0]), z = sigmoidf_(p[H] + rs[1]);
-                        const float n = tanhf(p[2 * H] + r * (rs[2] + bn));
-                        hv = (1.0f - z) * n + z * hv;
-                    } else {
-                        const float gi = sigmoidf_(p[0] + rs[0]), gf = sigmoidf_(p[H] + rs[1]), gg = tanhf(p[2 * H] + rs[2]), go = sigmoidf_(p[(NG - 1) * H] + rs[NG - 1]);
-                        c[s_] = gf * c[s_] + gi * gg;
-                        hv = go * tanhf(c[s_]);
-                    }
-                }
-                hn[s_ * H + j] = hv;
-            }
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    const float* hf = hs + cur * SB * H;               // (tmax == 0: the zero state)
-    if (Bi == 1 && rows > 1) {
-        if (blockIdx.x == 0)
-            for (int r = kq; r < rows; r += 4) out[(size_t)r * ld_out + j] = hf[j];
-    } else if (kq == 0) {
-#pragma unroll
-        for (int s_ = 0; s_ < SB; ++s_)
-            if (b0 + s_ < Bi) out[(size_t)(b0 + s_) * ld_out + j] = hf[s_ * H + j];
-    }
-}
-template <int SB>
-static const void* instr_final_scan_fn(int gru) {
-    return gru ? reinterpret_cast<const void*>(instr_final_scan_kernel<SB, true>) : reinterpret_cast<const void*>(instr_final_scan_kernel<SB, false>);
-}
-hipError_t launch_instr_final_scan(const float* pre, const float* wt, const float* bhn, const int* lengths, float* out, int Bi, int rows, int L, int H,
-                                   int gru, int ld_out, hipStream_t s) {
-    if (H != 256 || Bi < 1 || rows < Bi || L < 1 || ld_out < H || (gru && !bhn)) return hipErrorInvalidValue;     // 256 hidden units x 4 k-quarters = 1024 threads
-    // samples per workgroup as for instr_lstm_scan_kernel: the fewest (from 2 up) that keep the launch within 128 workgroups, so that the scan does not
-    // take the CUs from the trunks running beside it (B = 64: 32 workgroups).  SB = 1 is not instantiated (see launch_instr_lstm_scan).
-    int SB = 2;
-    while (SB < 8 && (Bi + SB - 1) / SB > 128) SB *= 2;
-    const int NG = gru ? 3 : 4;
-    const size_t lds = (size_t)(2 * SB * H + 3 * NG * SB * H) * sizeof(float);
-    const void* fn = SB == 2 ? instr_final_scan_fn<2>(gru) : SB == 4 ? instr_final_scan_fn<4>(gru) : instr_final_scan_fn<8>(gru);
-    // (28 KB at SB = 2, 112 KB at SB = 8; the kernel also holds a few static words, so the limit asked for is what the launch needs, not the CU's 160 KB)
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    void* args[] = {&pre, &wt, &bhn, &lengths, &out, &Bi, &rows, &L, &H, &ld_out};
-    return hipLaunchKernel(fn, dim3((Bi + SB - 1) / SB), dim3(1024), args, lds, s);
-}
-
-__global__ void gather_last_kernel(const float* __restrict__ all, const int* __restrict__ lengths, float* __restrict__ out, int Bi, int L, int H, int ld_out) {
-    const int r = blockIdx.x, b = Bi == 1 ? 0 : r;
-    int l = lengths[b];
-    l = l > L ? L : l;
-    for (int j = threadIdx.x; j < H; j += blockDim.x) out[(size_t)r * ld_out + j] = l > 0 ? all[((size_t)b * L + l - 1) * H + j] : 0.f;
-}
-hipError_t launch_gather_last(const float* all, const int* lengths, float* out, int Bi, int rows, int L, int H, int ld_out, hipStream_t s) {
-    if (rows < 1 || (Bi != 1 && Bi < rows)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gather_last_kernel, dim3(rows), dim3(256), 0, s, all, lengths, out, Bi, L, H, ld_out);
-    return hipGetLastError();
-}
 __global__ void copy_rows_kernel(const float* __restrict__ src, int ld_src, int n_src, float* __restrict__ dst, int ld_dst, int cols) {
     const int r = blockIdx.x;
     const float* sp = src + (size_t)(n_src == 1 ? 0 : r) * ld_src;

@@ -1526,7 +1526,10 @@ struct Fwd {
                 }
             } else if (Hi == 256 && !no_scan) {
                 // both directions, all L steps: one launch
-                if (!dry) ck(launch_instr_lstm_scan(pre[0], pre[1], w.hh_t[0], w.hh_t[1], ctx->len_buf, ins, B, L, Hi, w.dirs, C, s), "instr lstm scan");
+                InstrScanArgs a;
+                for (int d = 0; d < w.dirs; ++d) a.pre[d] = pre[d], a.wt[d] = w.hh_t[d];
+                a.lengths = ctx->len_buf; a.out = ins; a.ld_out = C; a.B = B; a.L = L;
+                if (!dry) ck(launch_instr_scan(a, w.dirs, 0, s), "instr lstm scan");
             } else {
                 for (int d = 0; d < w.dirs; ++d) {
                     if (!dry) ck(hipMemsetAsync(hc, 0, (size_t)2 * B * Hi * 4, s), "lstm state reset");
@@ -1693,17 +1696,13 @@ struct Fwd {
             float* pre = alloc_f((size_t)Bi * Lm * G * Hi);
             if (!dry) ck(launch_instr_embed(ids, ids_dt, w.emb, x, ctx->len_buf, Bi, L, E, ldi, m.vocab_size, s), "instr embed");
             linear(w.ih, x, Bi * L, ldi, pre, G * Hi, ACT_NONE, true);
-            // HCM_S2S_SCAN (development build; tools/bench_s2s.py): 0 = the per-token launches (what other instr_hidden sizes take), 2 = LSTM only: the
-            // all-outputs scan of CMANet's encoder over all L steps + a gather at each sample's last token -- what the library could do before this kernel
+            // HCM_S2S_SCAN=0 (development build; tools/bench_s2s.py): the per-token launches (what other instr_hidden sizes take)
             static const int scan_mode = dev_env("HCM_S2S_SCAN") ? atoi(dev_env("HCM_S2S_SCAN")) : 1;
             if (Hi == 256 && scan_mode == 1) {
-                if (!dry) ck(launch_instr_final_scan(pre, w.hh_t, w.bhn, ctx->len_buf, xh, Bi, B, L, Hi, gru ? 1 : 0, ldx, s), "instr final-state scan");
-            } else if (Hi == 256 && scan_mode == 2 && !gru) {
-                float* all = alloc_f((size_t)Bi * Lm * Hi);
-                if (!dry) {
-                    ck(launch_instr_lstm_scan(pre, nullptr, w.hh_t, nullptr, ctx->len_buf, all, Bi, L, Hi, 1, Hi, s), "instr lstm scan (all outputs)");
-                    ck(launch_gather_last(all, ctx->len_buf, xh, Bi, B, L, Hi, ldx, s), "instr final-state gather");
-                }
+                InstrScanArgs a;
+                a.pre[0] = pre; a.wt[0] = w.hh_t; a.bhn[0] = w.bhn; a.lengths = ctx->len_buf;
+                a.fin = xh; a.ld_fin = ldx; a.fin_rows = B; a.B = Bi; a.L = L;
+                if (!dry) ck(launch_instr_scan(a, 1, gru ? 1 : 0, s), "instr final-state scan");
             } else {
                 // other INSTRUCTION_ENCODER.hidden_size values: a launch pair per token (the cells freeze h once t >= length[b]), then the final
                 // states are copied (Bi == 1: broadcast) into the rows

@@ -1,17 +1,30 @@
-// Differentiable instruction encoder: the packed (bi)LSTM / GRU scan of elementwise.hip (instr_lstm_scan_kernel, instr_final_scan_kernel) with what a
-// backward pass needs, and its reverse-time scan.  Hidden size 256, one layer, one or two directions, float32.  Each is ONE launch for the whole scan:
-// a workgroup of 1024 threads owns SB samples of one direction for all of their steps, so the only synchronisation between steps is the workgroup
-// barrier -- no grid barrier, no spinning, no atomics, plain vector stores, fixed summation order (bitwise reproducible).
+// The instruction encoder's packed (bi)LSTM / GRU scan, for the engines and for training, and its reverse-time scan.  Hidden size 256, one layer, one
+// or two directions, float32.  Each is ONE launch for the whole scan: a workgroup of 1024 threads owns SB samples of one direction for all of their
+// steps, so the only synchronisation between steps is the workgroup barrier -- no grid barrier, no spinning, no atomics, plain vector stores, fixed
+// summation order (bitwise reproducible).
 //
 // Packed-sequence semantics (pack_padded_sequence / pad_packed_sequence): row b is active at tokens t < length[b]; its state is the zero state in
 // front of its first active token in scan order (token 0 forward, token length[b] - 1 in the reverse direction) and frozen behind its last one.
-// A workgroup walks max(length) over its own samples steps, not L; tokens no sample of it reaches are filled in front of the loop.
+// A workgroup walks max(length) over its own samples steps, not L (the lengths are read on the device: nothing for the host to wait for, the
+// launch is graph-capturable); tokens no sample of it reaches are filled in front of the loop.
 //
-// Forward (instr_scan_train_kernel<SB, GRU>): the work split and arithmetic of the inference kernels -- 256 units x 4 quarters of the k range, W_hh
-// streamed from L2 in the order [k][unit][4 gates] (GRU: fourth slot zero, not accumulated), h double-buffered in LDS, c in registers, the k-quarter
-// partials added as ((q0 + q1) + (q2 + q3)) -- plus, at every active token, the post-activation gates (LSTM i,f,g,o; GRU r,z,n and
-// hn = W_hn h + b_hn), c_t (LSTM), and h_t into the (B, L, dirs*256) buffer that is zero at inactive tokens: the per-token output and the left
-// operand of dW_hh.  The forward direction's state behind a row's last token goes to `fin`.
+// Forward (instr_scan_kernel<SB, GRU, FORM>): 1024 threads = 256 hidden units x 4 quarters of the k range.  Each thread streams a quarter of its
+// unit's recurrent weights from L2 every step -- W_hh in the order [k][unit][4 gates], so the gate weights of (k, unit) are one 16-byte load,
+// coalesced across the units (GRU: fourth slot zero, not accumulated); 4*H*H*4 bytes per step and workgroup -- for SB samples, several loads in
+// flight.  h lives in LDS (double-buffered, broadcast reads), c in registers; the four partial sums per (gate, sample, unit) meet in LDS and are
+// added as ((q0 + q1) + (q2 + q3)).  pre = x_t W_ih^T + bias for every token: LSTM bias b_ih + b_hh; GRU bias b_ih + (b_hr, b_hz, 0), b_hn stays
+// inside the r * (.) product as in torch.  FORM says what is stored -- extra stores of values the epilogue has anyway: the sums, the cells and so
+// every stored bit are the same in all three --
+//   SEQ    h_t at every active token into out (ld_out floats per token, direction d at column d * 256), zero at inactive tokens: CMANet's
+//          per-token encoder output (LSTM only: nothing runs it with a GRU, which is not instantiated);
+//   FIN    no per-token store, only the forward direction's state behind each row's last token, straight into the caller's row (fin, ld_fin):
+//          Seq2SeqNet's final_state_only encoder (instruction_encoder.py:86-90; both Seq2Seq paper configs).  B == 1 with fin_rows > 1: one
+//          instruction for fin_rows frames (seq2seq.py:163 `.expand`) -- one sample is scanned, its result written to every row;
+//   TRAIN  SEQ's output (also the left operand of dW_hh), FIN's final state where `fin` is given, and at every active token the post-activation
+//          gates (LSTM i,f,g,o; GRU r,z,n and hn = W_hn h + b_hn) and c_t (LSTM): what the reverse scan reads.
+// SB is chosen small (instr_scan_sb: 2 for B = 64 in both directions, 64 workgroups): per step a thread then does SB * 256 FMAs behind 64 16-byte
+// loads, and the step is bounded by that weight stream (1 MB from L2) instead of by 8 samples' worth of FMAs and LDS broadcasts on 16 CUs (CMANet
+// step at B = 64, L = 80: 3.15 -> 2.56 ms; the trunks alone take 2.4).
 //
 // Reverse (instr_scan_bwd_kernel<SB, GRU>): the same ownership, the direction's steps walked backwards.  Per step, with dH = d_out[b, t] + carry_h
 // (+ d_fin[b] at t = length[b] - 1, forward direction), c' / h' the state in front of the step (zero at the direction's first token):
@@ -34,33 +47,24 @@ namespace hcm {
 
 constexpr int kInstrH = 256;
 
-struct InstrTrainArgs {
-    const float* pre;        // (dirs, B*L, NG*H): x_t W_ih^T + bias
-    const float* wt;         // (dirs, H (k), H (unit), 4 (gate))
-    const float* bhn;        // (dirs, H), GRU
-    const int* lengths;      // (B,)
-    float* out;              // (B, L, dirs*H)
-    float* fin;              // (B, H) or null
-    float* gates;            // (dirs, B*L, 4H)
-    float* cseq;             // (dirs, B*L, H), LSTM
-    int B, L;
-};
+enum { INSTR_SEQ = 0, INSTR_FIN = 1, INSTR_TRAIN = 2 };
 
-template <int SB, bool GRU>
-__global__ __launch_bounds__(1024) void instr_scan_train_kernel(InstrTrainArgs a) {
+template <int SB, bool GRU, int FORM>
+__global__ __launch_bounds__(1024) void instr_scan_kernel(InstrScanArgs a) {
     constexpr int H = kInstrH, NG = GRU ? 3 : 4, KQ = H / 4;
+    constexpr bool PER_TOKEN = FORM != INSTR_FIN, SAVE = FORM == INSTR_TRAIN;
     extern __shared__ float smf[];         // h [2][SB][H], partials [3][NG][SB][H]
     __shared__ int len_s[SB];
     float* hs = smf;
     float* ps = smf + 2 * SB * H;
-    const int dir = blockIdx.y, dirs = gridDim.y, b0 = blockIdx.x * SB;
-    const int B = a.B, L = a.L, ldo = dirs * H;
+    const int dir = blockIdx.y, b0 = blockIdx.x * SB;
+    const int B = a.B, L = a.L, ldo = a.ld_out;
     const int j = threadIdx.x & 255, kq = threadIdx.x >> 8;
     const size_t BL = (size_t)B * L;
-    const float* __restrict__ pre = a.pre + (size_t)dir * BL * NG * H;
-    const float* __restrict__ wq = a.wt + (size_t)dir * H * H * 4 + ((size_t)kq * KQ * H + j) * 4;
-    float* __restrict__ gates = a.gates + (size_t)dir * BL * 4 * H;
-    float* __restrict__ cseq = GRU ? nullptr : a.cseq + (size_t)dir * BL * H;
+    const float* __restrict__ pre = dir ? a.pre[1] : a.pre[0];       // (selects: an indexed read is a second scalar load that waits for the first)
+    const float* __restrict__ wq = (dir ? a.wt[1] : a.wt[0]) + ((size_t)kq * KQ * H + j) * 4;
+    float* __restrict__ gates = SAVE ? a.gates + (size_t)dir * BL * 4 * H : nullptr;
+    float* __restrict__ cseq = SAVE && !GRU ? a.cseq + (size_t)dir * BL * H : nullptr;
     float* __restrict__ out = a.out;
     if (threadIdx.x < SB) {
         const int b = b0 + threadIdx.x;
@@ -73,15 +77,17 @@ __global__ __launch_bounds__(1024) void instr_scan_train_kernel(InstrTrainArgs a
 #pragma unroll
     for (int s_ = 0; s_ < SB; ++s_) tmax = len_s[s_] > tmax ? len_s[s_] : tmax;
     // zeros at every inactive token of the samples this workgroup owns
-    for (int s_ = 0; s_ < SB; ++s_) {
-        if (b0 + s_ >= B) break;
-        float* o = out + (size_t)(b0 + s_) * L * ldo + dir * H;
-        for (int t = len_s[s_] + kq; t < L; t += 4) o[(size_t)t * ldo + j] = 0.f;
+    if (PER_TOKEN) {
+        for (int s_ = 0; s_ < SB; ++s_) {
+            if (b0 + s_ >= B) break;
+            float* o = out + (size_t)(b0 + s_) * L * ldo + dir * H;
+            for (int t = len_s[s_] + kq; t < L; t += 4) o[(size_t)t * ldo + j] = 0.f;
+        }
     }
     float c[SB];
 #pragma unroll
     for (int s_ = 0; s_ < SB; ++s_) c[s_] = 0.f;
-    const float bn = GRU ? a.bhn[dir * H + j] : 0.f;
+    const float bn = GRU ? (dir ? a.bhn[1] : a.bhn[0])[j] : 0.f;
     int cur = 0;
     for (int n = 0; n < tmax; ++n) {
         const int t = dir ? tmax - 1 - n : n;
@@ -117,7 +123,7 @@ __global__ __launch_bounds__(1024) void instr_scan_train_kernel(InstrTrainArgs a
                 if (t < len_s[s_]) {                   // (len_s > 0 only for b0 + s_ < B: every access below is in bounds)
                     const size_t row = (size_t)(b0 + s_) * L + t;
                     const float* p = pre + row * NG * H + j;
-                    float* gp = gates + row * 4 * H + j;
+                    float* gp = SAVE ? gates + row * 4 * H + j : nullptr;
                     float rs[NG];
 #pragma unroll
                     for (int g = 0; g < NG; ++g)
@@ -127,15 +133,17 @@ __global__ __launch_bounds__(1024) void instr_scan_train_kernel(InstrTrainArgs a
                         const float ghn = rs[2] + bn;
                         const float nn = tanhf(p[2 * H] + r * ghn);
                         hv = (1.0f - z) * nn + z * hv;
-                        gp[0] = r, gp[H] = z, gp[2 * H] = nn, gp[3 * H] = ghn;
+                        if (SAVE) gp[0] = r, gp[H] = z, gp[2 * H] = nn, gp[3 * H] = ghn;
                     } else {
                         const float gi = sigmoidf_(p[0] + rs[0]), gf = sigmoidf_(p[H] + rs[1]), gg = tanhf(p[2 * H] + rs[2]), go = sigmoidf_(p[(NG - 1) * H] + rs[NG - 1]);
                         c[s_] = gf * c[s_] + gi * gg;
                         hv = go * tanhf(c[s_]);
-                        gp[0] = gi, gp[H] = gf, gp[2 * H] = gg, gp[3 * H] = go;
-                        cseq[row * H + j] = c[s_];
+                        if (SAVE) {
+                            gp[0] = gi, gp[H] = gf, gp[2 * H] = gg, gp[3 * H] = go;
+                            cseq[row * H + j] = c[s_];
+                        }
                     }
-                    out[row * ldo + dir * H + j] = hv;
+                    if (PER_TOKEN) out[row * ldo + dir * H + j] = hv;
                 }
                 hnext[s_ * H + j] = hv;
             }
@@ -143,11 +151,16 @@ __global__ __launch_bounds__(1024) void instr_scan_train_kernel(InstrTrainArgs a
         __syncthreads();
         cur ^= 1;
     }
-    if (dir == 0 && a.fin && kq == 0) {
+    if (FORM != INSTR_SEQ && dir == 0 && a.fin) {
         const float* hf = hs + cur * SB * H;           // (length 0: the zero state)
+        if (B == 1 && a.fin_rows > 1) {
+            if (blockIdx.x == 0)
+                for (int r = kq; r < a.fin_rows; r += 4) a.fin[(size_t)r * a.ld_fin + j] = hf[j];
+        } else if (kq == 0) {
 #pragma unroll
-        for (int s_ = 0; s_ < SB; ++s_)
-            if (b0 + s_ < B) a.fin[(size_t)(b0 + s_) * H + j] = hf[s_ * H + j];
+            for (int s_ = 0; s_ < SB; ++s_)
+                if (b0 + s_ < B) a.fin[(size_t)(b0 + s_) * a.ld_fin + j] = hf[s_ * H + j];
+        }
     }
 }
 
@@ -341,41 +354,56 @@ __global__ __launch_bounds__(256) void instr_scan_pack_bwd_kernel(const float* _
 
 bool instr_scan_train_ok(int B, int L, int H, int dirs) { return H == kInstrH && B >= 1 && L >= 1 && (dirs == 1 || dirs == 2); }
 size_t instr_scan_work_floats(int dirs) { return (size_t)dirs * 4 * kInstrH * kInstrH; }
-// samples per workgroup, the rule of launch_instr_lstm_scan / launch_instr_final_scan: the fewest (from 2 up) that keep the launch within 128 workgroups
-// (without launch_instr_lstm_scan's HCM_LSTM_SB override, a knob of the development build only)
-int instr_scan_train_sb(int B, int dirs) {
+// samples per workgroup of the forward and the reverse launch: the fewest (from 2 up) that keep the launch within 128 workgroups, so that the scan
+// does not take the CUs from the trunks running beside it (B = 64: 32 workgroups a direction).  SB = 1 is not built: slower at B = 64 -- 128
+// workgroups take those CUs -- and its instantiation showed run-to-run differences of ~3e-5 whose cause was not found; SB = 2 / 4 / 8 are bitwise
+// reproducible, tested.
+int instr_scan_sb(int B, int dirs) {
     int SB = 2;
     while (SB < 8 && ((B + SB - 1) / SB) * dirs > 128) SB *= 2;
     return SB;
 }
 
+// the forms a caller reaches: nothing runs the per-token form with a GRU
 template <int SB>
-static const void* instr_train_fn(int gru) {
-    return gru ? reinterpret_cast<const void*>(instr_scan_train_kernel<SB, true>) : reinterpret_cast<const void*>(instr_scan_train_kernel<SB, false>);
+static const void* instr_scan_fn(int gru, int form) {
+    if (form == INSTR_SEQ) return gru ? nullptr : reinterpret_cast<const void*>(instr_scan_kernel<SB, false, INSTR_SEQ>);
+    if (form == INSTR_FIN)
+        return gru ? reinterpret_cast<const void*>(instr_scan_kernel<SB, true, INSTR_FIN>) : reinterpret_cast<const void*>(instr_scan_kernel<SB, false, INSTR_FIN>);
+    return gru ? reinterpret_cast<const void*>(instr_scan_kernel<SB, true, INSTR_TRAIN>) : reinterpret_cast<const void*>(instr_scan_kernel<SB, false, INSTR_TRAIN>);
 }
 template <int SB>
 static const void* instr_bwd_fn(int gru) {
     return gru ? reinterpret_cast<const void*>(instr_scan_bwd_kernel<SB, true>) : reinterpret_cast<const void*>(instr_scan_bwd_kernel<SB, false>);
 }
 
-hipError_t launch_instr_scan_train(const float* pre, const float* w_hh, const float* bhn, const int* lengths, float* out, float* fin, float* gates,
-                                   float* cseq, float* work, int B, int L, int H, int dirs, int gru, hipStream_t s) {
-    if (!instr_scan_train_ok(B, L, H, dirs) || !pre || !w_hh || !lengths || !out || !gates || !work || (gru && !bhn) || (cseq == nullptr) != (gru != 0))
-        return hipErrorInvalidValue;
-    const int NG = gru ? 3 : 4;
-    hipLaunchKernelGGL(instr_scan_pack_fwd_kernel, dim3(H, dirs), dim3(256), 0, s, w_hh, (float4*)work, NG);
-    hipError_t e = hipGetLastError();
+hipError_t launch_instr_scan(const InstrScanArgs& a, int dirs, int gru, hipStream_t s) {
+    constexpr int H = kInstrH;
+    const int form = a.gates ? INSTR_TRAIN : a.out ? INSTR_SEQ : INSTR_FIN;
+    if (!instr_scan_train_ok(a.B, a.L, H, dirs) || !a.lengths) return hipErrorInvalidValue;
+    for (int d = 0; d < dirs; ++d)
+        if (!a.pre[d] || !a.wt[d] || (gru && !a.bhn[d])) return hipErrorInvalidValue;
+    if (form != INSTR_FIN && (!a.out || a.ld_out < dirs * H)) return hipErrorInvalidValue;
+    if (form == INSTR_FIN && (dirs != 1 || !a.fin)) return hipErrorInvalidValue;
+    if (a.fin && (a.fin_rows < a.B || a.ld_fin < H)) return hipErrorInvalidValue;
+    if (form == INSTR_TRAIN && (a.cseq == nullptr) != (gru != 0)) return hipErrorInvalidValue;
+    const int SB = instr_scan_sb(a.B, dirs), NG = gru ? 3 : 4;
+    // h [2][SB][H] and the partials [3][NG][SB][H]: 28 KB at SB = 2, 112 KB at SB = 8 (LSTM), within the 160 KB of a CU.  The kernel also holds SB
+    // static words (its lengths), so the limit asked for is what the launch uses, not the CU's 160 KB, which the runtime refuses on top of them
+    const size_t lds = (size_t)(2 + 3 * NG) * SB * H * sizeof(float);
+    const void* fn = SB == 2 ? instr_scan_fn<2>(gru, form) : SB == 4 ? instr_scan_fn<4>(gru, form) : instr_scan_fn<8>(gru, form);
+    if (!fn) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    const int SB = instr_scan_train_sb(B, dirs);
-    // 28 KB at SB = 2, 112 KB at SB = 8 (LSTM), within the 160 KB of a CU
-    const size_t lds = (size_t)(2 * SB * H + 3 * NG * SB * H) * sizeof(float);
-    const void* fn = SB == 2 ? instr_train_fn<2>(gru) : SB == 4 ? instr_train_fn<4>(gru) : instr_train_fn<8>(gru);
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    InstrTrainArgs a;
-    a.pre = pre; a.wt = work; a.bhn = bhn; a.lengths = lengths; a.out = out; a.fin = fin; a.gates = gates; a.cseq = cseq; a.B = B; a.L = L;
-    void* args[] = {&a};
-    return hipLaunchKernel(fn, dim3((B + SB - 1) / SB, dirs), dim3(1024), args, lds, s);
+    InstrScanArgs k = a;
+    void* args[] = {&k};
+    return hipLaunchKernel(fn, dim3((a.B + SB - 1) / SB, dirs), dim3(1024), args, lds, s);
+}
+
+hipError_t launch_instr_scan_pack_fwd(const float* w_hh, float* wt, int dirs, int gru, hipStream_t s) {
+    if (!w_hh || !wt || (dirs != 1 && dirs != 2)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(instr_scan_pack_fwd_kernel, dim3(kInstrH, dirs), dim3(256), 0, s, w_hh, (float4*)wt, gru ? 3 : 4);
+    return hipGetLastError();
 }
 
 hipError_t launch_instr_scan_bwd(const float* d_out, const float* d_fin, const float* gates, const float* cseq, const float* out, const float* w_hh,
@@ -387,7 +415,7 @@ hipError_t launch_instr_scan_bwd(const float* d_out, const float* d_fin, const f
     hipLaunchKernelGGL(instr_scan_pack_bwd_kernel, dim3(NG * H / 4, dirs), dim3(256), 0, s, w_hh, (float4*)work, NG);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int SB = instr_scan_train_sb(B, dirs);
+    const int SB = instr_scan_sb(B, dirs);
     // carry 2, da NG, partials 3, GRU's dH z 1 times SB * H floats, 9 * SB KB for either cell: 18 KB at SB = 2, 72 KB at SB = 8
     const size_t lds = (size_t)(2 + NG + 3 + (gru ? 1 : 0)) * SB * H * sizeof(float);
     const void* fn = SB == 2 ? instr_bwd_fn<2>(gru) : SB == 4 ? instr_bwd_fn<4>(gru) : instr_bwd_fn<8>(gru);

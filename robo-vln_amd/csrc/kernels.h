@@ -358,25 +358,36 @@ hipError_t launch_instr_lstm_cell(const float* pre, const float* gh, float* h, f
                                   int L, int Hd, int ld_out, int col0, hipStream_t s);
 hipError_t launch_instr_gru_cell(const float* pre, const float* gh, float* h, const int* lengths, float* out, int t, int B, int L, int Hd, int ld_out,
                                  int col0, hipStream_t s);   // nn.GRU step of the packed instruction encoder (gate order r, z, n; gh carries b_hh)
-// all L steps of both directions in one launch (H == 256): wt = W_hh transposed [H][4H]
-hipError_t launch_instr_lstm_scan(const float* pre0, const float* pre1, const float* wt0, const float* wt1, const int* lengths, float* out,
-                                  int B, int L, int H, int dirs, int ld_out, hipStream_t s);
-// Seq2SeqNet's instruction encoder (final_state_only, instruction_encoder.py:86-90): the packed scan that keeps ONLY h at t = length[b] - 1.
-// pre [Bi*L][G*H] = x_t W_ih^T + bias (G = 4 LSTM i,f,g,o / 3 GRU r,z,n), wt = W_hh as [H][H][4] (GRU: 4th slot 0), bhn = GRU's b_hn or null.
-// Row b of the result goes to out[b * ld_out .. + H) for b < Bi; with Bi == 1 and rows > 1 the one result is written to `rows` rows.
-// H == 256.  A workgroup runs max(length) of its own samples steps, not L.
-hipError_t launch_instr_final_scan(const float* pre, const float* wt, const float* bhn, const int* lengths, float* out, int Bi, int rows, int L, int H,
-                                   int gru, int ld_out, hipStream_t s);
-// The differentiable instruction encoder (instr_scan_train.hip): the packed scan above with what a backward pass needs, and its reverse scan; ONE
-// launch each behind a weight pack on the stream, H == 256, dirs 1 or 2, any B, L >= 1.  Tensors with a leading `dirs` are stacked per direction:
-//   pre (dirs, B*L, G*H), w_hh (dirs, G*H, H) as torch stores it, bhn (dirs, H) (GRU), gates (dirs, B*L, 4H), cseq (dirs, B*L, H) (LSTM; null for GRU),
-//   d_pre (dirs, B*L, G*H), d_gh (dirs, B*L, 3H) (GRU; null for LSTM); out / d_out (B, L, dirs*H); fin / d_fin (B, H), forward direction, may be null.
-// work: instr_scan_work_floats(dirs) floats, W_hh in the launch's order.  No allocation, no host copy, no synchronisation.
+// The packed instruction-encoder scan (instr_scan.hip), ONE launch for every step of one or two directions: H == 256, dirs 1 or 2, any B, L >= 1,
+// LSTM (G = 4: i,f,g,o) or GRU (G = 3: r,z,n).  What the launch stores follows from the pointers given:
+//   out alone (LSTM)    h_t of every token, zero at inactive ones (CMANet's encoder output);
+//   fin alone (dirs 1)  only h at t = length[b] - 1 (Seq2SeqNet's final_state_only encoder, instruction_encoder.py:86-90);
+//   gates (and out)     the training forward: out, fin where given, and the gates and c_t the reverse scan reads.
+// A workgroup runs max(length) of its own samples steps, not L.
+struct InstrScanArgs {
+    const float* pre[2] = {nullptr, nullptr};      // per direction [B*L][G*H]: x_t W_ih^T + bias (LSTM b_ih + b_hh; GRU b_ih + (b_hr, b_hz, 0))
+    const float* wt[2] = {nullptr, nullptr};       // per direction W_hh as [H (k)][H (unit)][4 (gate)] (GRU: 4th slot 0)
+    const float* bhn[2] = {nullptr, nullptr};      // per direction [H]: GRU's b_hn
+    const int* lengths = nullptr;                  // [B]; below 0 counts as 0, past L as L
+    float* out = nullptr;                          // token (b, t) of direction d at out[(b * L + t) * ld_out + d * H .. + H)
+    int ld_out = 0;
+    float* fin = nullptr;                          // row b of the forward direction's final state at fin[b * ld_fin .. + H), b < B; with B == 1
+    int ld_fin = 0, fin_rows = 0;                  // and fin_rows > 1 the one result is written to fin_rows rows; otherwise fin_rows = B
+    float* gates = nullptr;                        // (dirs, B*L, 4H)
+    float* cseq = nullptr;                         // (dirs, B*L, H), LSTM; null for GRU
+    int B = 0, L = 0;
+};
 bool instr_scan_train_ok(int B, int L, int H, int dirs);
+int instr_scan_sb(int B, int dirs);                        // samples per workgroup the forward and the reverse launch choose
+hipError_t launch_instr_scan(const InstrScanArgs& a, int dirs, int gru, hipStream_t s);
+// The differentiable instruction encoder: the scan above in its training form and its reverse scan, each behind a weight pack on the stream.
+// Tensors with a leading `dirs` are stacked per direction:
+//   w_hh (dirs, G*H, H) as torch stores it, gates (dirs, B*L, 4H), cseq (dirs, B*L, H) (LSTM; null for GRU), d_pre (dirs, B*L, G*H),
+//   d_gh (dirs, B*L, 3H) (GRU; null for LSTM); out / d_out (B, L, dirs*H); d_fin (B, H), forward direction, may be null.
+// work: instr_scan_work_floats(dirs) floats, W_hh in the launch's order (launch_instr_scan_pack_fwd: the forward scan's wt, direction d at
+// work + d * 4 * H * H).  No allocation, no host copy, no synchronisation.
 size_t instr_scan_work_floats(int dirs);
-int instr_scan_train_sb(int B, int dirs);                  // samples per workgroup the two launches choose
-hipError_t launch_instr_scan_train(const float* pre, const float* w_hh, const float* bhn, const int* lengths, float* out, float* fin, float* gates,
-                                   float* cseq, float* work, int B, int L, int H, int dirs, int gru, hipStream_t s);
+hipError_t launch_instr_scan_pack_fwd(const float* w_hh, float* wt, int dirs, int gru, hipStream_t s);
 hipError_t launch_instr_scan_bwd(const float* d_out, const float* d_fin, const float* gates, const float* cseq, const float* out, const float* w_hh,
                                  const int* lengths, float* work, float* d_pre, float* d_gh, int B, int L, int H, int dirs, int gru, hipStream_t s);
 // CMANet's attention stage in float32 with a backward pass (cma_attn_train.hip), one query per sample with the key projection folded into the
@@ -399,8 +410,6 @@ size_t attn1q_train_work_floats(int B, int C0, int Ce, int I);
 hipError_t launch_attn1q_train_fwd(const Attn1qTrainArgs& t, hipStream_t s);
 hipError_t launch_attn1q_train_bwd(const Attn1qTrainArgs& t, hipStream_t s);
 // dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
-// out[r][0..H) = all[b][max(len_b, 1) - 1][0..H) with b = (Bi == 1 ? 0 : r): the last active step of an all-outputs scan (len_b == 0: zeros)
-hipError_t launch_gather_last(const float* all, const int* lengths, float* out, int Bi, int rows, int L, int H, int ld_out, hipStream_t s);
 hipError_t launch_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s);
 hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int* lengths, float* out,
                          int ldo, int B, int S, int D, int Dv, float scale, hipStream_t s);

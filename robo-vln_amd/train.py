@@ -17,7 +17,7 @@ forward and one backward per half; `embed_ln_ref` is the pure-torch restatement,
 drop-in module around `InterModuleAttnLayer`.
 
 Differentiable instruction encoder: the reference's InstructionEncoder (models/encoders/instruction_encoder.py:70-92), a packed nn.LSTM / nn.GRU
-with hidden size 256 in one or two directions, with the whole scan forward and the whole scan backward one launch each (csrc/instr_scan_train.hip)
+with hidden size 256 in one or two directions, with the whole scan forward and the whole scan backward one launch each (csrc/instr_scan.hip)
 and the lengths read on the device.  `instr_scan` is the autograd function, `instr_encoder_ref` the pure-torch restatement, `InstructionEncoder`
 the drop-in module.
 

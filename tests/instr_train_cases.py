@@ -4,8 +4,13 @@ CPU-autograd reference through train.instr_encoder_ref, computed once per case a
 Inputs: weights and biases uniform in +-0.1, embedded rows and the cotangent uniform in +-1.  A case is (rnn, dirs, final, B, L): the lengths
 come from LENGTHS, the cotangent has the shape of the result -- (B, L, dirs*H), or (B, H) for the final state.  EDGE_CASES hold lengths of 0,
 below 0 and past L (instr_encoder_ref's activity test is t < lengths, so they need no other reference), the 200-token horizon and eight samples
-per workgroup in one direction; SATURATED_CASES are built with weight_ih times SATURATED_IH_SCALE."""
+per workgroup in one direction; SATURATED_CASES are built with weight_ih times SATURATED_IH_SCALE.
+
+scan_inputs / forward_scan_digests: the forward scans alone on inputs drawn without a GEMM, as SHA-256 digests, for the bits recorded in
+tests/golden/instr_scan_parent_bits.json (PARENT_BITS_CASES)."""
+import ctypes
 import functools
+import hashlib
 
 import torch
 
@@ -55,6 +60,15 @@ EDGE_CASES = [(*s, B, L) for (B, L), settings in EDGE_SETTINGS.items() for s in 
 SATURATED_IH_SCALE = 20.0
 SATURATED_CASES = [("LSTM", 2, False, 4, 40), ("GRU", 2, False, 4, 40)]
 PARAM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+# the training forward against the engines' one-launch scans, bit for bit (the inference hook serves the final-state scan of either cell and the
+# per-token scan of the LSTM)
+INFER_EDGES = [s + shape for shape in ((6, 9), (3, 200), (513, 2)) for s in EDGE_SETTINGS[shape] if s[2] or s[0] == "LSTM"]
+INFER_CASES = [("LSTM", 1, True, 5, 33), ("GRU", 1, True, 5, 33), ("LSTM", 1, True, 9, 12), ("GRU", 1, True, 9, 12), ("LSTM", 2, False, 5, 33),
+               ("LSTM", 1, False, 9, 12), ("LSTM", 2, False, 130, 3), ("LSTM", 2, False, 260, 2)] + INFER_EDGES
+# the forward scans against the bits recorded at the commit in front of the one-kernel scan (tests/golden/instr_scan_parent_bits.json, written by
+# tools/record_instr_scan_bits.py): INFER_CASES and two per-token GRU cases, which only the training forward runs.  Two, four and eight samples
+# per workgroup, both cells, one and two directions, partial and empty workgroups, lengths below 0 and past L.
+PARENT_BITS_CASES = INFER_CASES + [("GRU", 2, False, 5, 33), ("GRU", 2, False, 260, 2)]
 
 
 def grad_names(dirs):
@@ -131,3 +145,49 @@ def saved64(emb, lengths, params):
                     gates[d, b, t] = torch.cat([r, z, nn_, h_n])
     active = torch.arange(L)[None, :] < lengths[:, None]
     return gates, cs, active
+
+
+def scan_inputs(rnn, dirs, B, L, H=256):
+    """The scan's own inputs, drawn directly (no GEMM, so no BLAS library has a say in their bits), float32 on the CPU: pre (dirs, B*L, G*H)
+    uniform in +-1, w_hh (dirs, G*H, H) and b_hn (dirs, H; None for LSTM) uniform in +-0.1, and LENGTHS[(B, L)] as int32."""
+    g = torch.Generator().manual_seed(77000000 + 10000 * B + 100 * L + 10 * dirs + (rnn == "GRU"))
+    G = 4 if rnn == "LSTM" else 3
+    pre = torch.rand(dirs, B * L, G * H, generator=g) * 2 - 1
+    w_hh = (torch.rand(dirs, G * H, H, generator=g) * 2 - 1) * 0.1
+    b_hn = None if rnn == "LSTM" else (torch.rand(dirs, H, generator=g) * 2 - 1) * 0.1
+    return dict(pre=pre, w_hh=w_hh, b_hn=b_hn, lengths=torch.tensor(LENGTHS[(B, L)], dtype=torch.int32))
+
+
+def digest(t):
+    """SHA-256 of a tensor's raw bytes (None for no tensor)"""
+    return None if t is None else hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def forward_scan_digests(lib, rnn, dirs, final, B, L, H=256):
+    """One case of PARENT_BITS_CASES on the GPU through the C ABI alone: hcm_op_instr_scan_train on scan_inputs, then hcm_op_instr_scan_infer (where
+    it serves the case) on the `work` buffer the training call packed.  Every output starts as NaN, so an element left unwritten counts.
+    Returns (input digests, output digests)."""
+    from robo_vln_amd import _lib
+    lstm = rnn == "LSTM"
+    kind = _lib.HCM_LSTM if lstm else _lib.HCM_GRU
+    inp = scan_inputs(rnn, dirs, B, L, H)
+    dev = {k: None if v is None else v.cuda() for k, v in inp.items()}
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    pt = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    nan = float("nan")
+    o = dict(out=torch.full((B, L, dirs * H), nan, device="cuda"), fin=torch.full((B, H), nan, device="cuda"),
+             gates=torch.full((dirs, B, L, 4 * H), nan, device="cuda"), c_seq=torch.full((dirs, B, L, H), nan, device="cuda") if lstm else None,
+             infer_out=None)
+    work = torch.empty(lib.hcm_op_instr_scan_work_floats(B, L, dirs, kind), device="cuda")
+    assert lib.hcm_op_instr_scan_train(pt(dev["pre"]), pt(dev["w_hh"]), pt(dev["b_hn"]), pt(dev["lengths"]), pt(o["out"]), pt(o["fin"]), pt(o["gates"]),
+                                       pt(o["c_seq"]), pt(work), B, L, H, dirs, kind, st) == 0, _lib.last_error()
+    if final or lstm:
+        o["infer_out"] = torch.full((B, H) if final else (B, L, dirs * H), nan, device="cuda")
+        assert lib.hcm_op_instr_scan_infer(pt(dev["pre"]), pt(work), pt(dev["b_hn"]), pt(dev["lengths"]), pt(o["infer_out"]), B, L, H, dirs, kind,
+                                           int(final), st) == 0, _lib.last_error()
+    torch.cuda.synchronize()
+    return {k: digest(v) for k, v in inp.items()}, {k: digest(v) for k, v in o.items()}
+
+
+def case_id(rnn, dirs, final, B, L):
+    return f"{rnn}-{dirs}-{final}-{B}-{L}"

@@ -159,3 +159,19 @@ def test_a_row_of_length_zero_contributes_nothing(rnn, dirs, final):
     assert (g2[0][1] == 0).all()
     for name, a, b in zip(cases.grad_names(dirs), (g2[0][[0, 2, 3]], *g2[1:]), g):
         assert (a - b).abs().max().item() <= 1e-12 * b.abs().max().item(), name
+
+
+def test_the_recorded_scan_bits_belong_to_the_inputs_drawn_here():
+    """tests/golden/instr_scan_parent_bits.json holds every case of PARENT_BITS_CASES, each with all five outputs, and the digests of the inputs it
+    was recorded on are those of cases.scan_inputs on this machine (they are drawn on the CPU): a change to the draw shows here, without a GPU,
+    and means recording again with the library of the commit whose bits are to be kept (tools/record_instr_scan_bits.py)."""
+    import json
+    with open(os.path.join(GOLD, "instr_scan_parent_bits.json")) as f:
+        rec = json.load(f)["cases"]
+    assert set(rec) == {cases.case_id(*c) for c in cases.PARENT_BITS_CASES} and len(rec) == len(cases.PARENT_BITS_CASES) == 20
+    for rnn, dirs, final, B, L in cases.PARENT_BITS_CASES:
+        want = rec[cases.case_id(rnn, dirs, final, B, L)]
+        assert {k: cases.digest(v) for k, v in cases.scan_inputs(rnn, dirs, B, L).items()} == want["inputs"], (rnn, dirs, final, B, L)
+        assert set(want["outputs"]) == {"out", "fin", "gates", "c_seq", "infer_out"}
+        assert (want["outputs"]["c_seq"] is None) == (rnn == "GRU") and (want["outputs"]["infer_out"] is None) == (rnn == "GRU" and not final)
+        assert all(want["outputs"][k] for k in ("out", "fin", "gates"))

@@ -9,13 +9,16 @@ on the first five shapes with these input distributions.  No element is excluded
 tests/instr_train_cases.py (lengths of 0, below 0 and past L, a workgroup of empty rows, 200 tokens, eight samples per workgroup in one direction)
 and the saturated ones run under the same bounds; tests/test_train_coverage_cpu.py holds the float32 CPU restatement to half of them there.
 
-Samples per workgroup: the launcher takes the fewest of 2, 4, 8 that keep the launch within 128 workgroups, the rule of launch_instr_lstm_scan;
-with two directions (130, 3) reaches 4 and (260, 2) reaches 8, with one direction (260, 2) reaches 4 and (513, 2) reaches 8, every other case
-runs at 2 (tests/test_train_coverage_cpu.py computes this from the case lists).  The rule is restated in instr_scan_train_sb without
-launch_instr_lstm_scan's HCM_LSTM_SB override, which only the development build reads: on that build, with the variable set, the bitwise
-comparison would put the inference scan at another count than the training forward (the sums per sample are the same at every count, so the
-bits should still agree, but that is not what these cases were written to show).  These tests load the shipped library."""
+Samples per workgroup: the launcher takes the fewest of 2, 4, 8 that keep the launch within 128 workgroups (instr_scan_sb of csrc/instr_scan.hip,
+one rule for the engines' scans, the training forward and the reverse scan); with two directions (130, 3) reaches 4 and (260, 2) reaches 8, with
+one direction (260, 2) reaches 4 and (513, 2) reaches 8, every other case runs at 2 (tests/test_train_coverage_cpu.py computes this from the case
+lists).  The engines' scans and the training forward are one kernel, instr_scan_kernel<SB, GRU, FORM>, whose FORM only selects stores: the bitwise
+comparison of the two guards that, and tests/golden/instr_scan_parent_bits.json holds all of them to the bits of the three separate kernels that
+kernel replaced.  These tests load the shipped library."""
 import ctypes as C
+import functools
+import json
+import os
 
 import pytest
 import torch
@@ -170,17 +173,31 @@ def test_padding_is_exactly_zero_and_saved_tensors_are_written(rnn, dirs, final,
     assert e_g <= 1e-5 and e_c <= 1e-5 and e_f <= 1e-5
 
 
-# (the inference hook serves the final-state scan of either cell and the per-token scan of the LSTM)
-INFER_EDGES = [s + shape for shape in ((6, 9), (3, 200), (513, 2)) for s in cases.EDGE_SETTINGS[shape] if s[2] or s[0] == "LSTM"]
-
-
-@pytest.mark.parametrize("rnn,dirs,final,B,L", [("LSTM", 1, True, 5, 33), ("GRU", 1, True, 5, 33), ("LSTM", 1, True, 9, 12), ("GRU", 1, True, 9, 12),
-                                                ("LSTM", 2, False, 5, 33), ("LSTM", 1, False, 9, 12), ("LSTM", 2, False, 130, 3),
-                                                ("LSTM", 2, False, 260, 2)] + INFER_EDGES)
+@pytest.mark.parametrize("rnn,dirs,final,B,L", cases.INFER_CASES)
 def test_training_forward_is_the_inference_scan_bitwise(rnn, dirs, final, B, L):
     o, ref = _raw(rnn, dirs, final, B, L)
     assert not ref.isnan().any()
     assert torch.equal(o["fin"] if final else o["out"], ref)
+
+
+@functools.lru_cache(maxsize=None)
+def _parent_bits():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "instr_scan_parent_bits.json")) as f:
+        return json.load(f)["cases"]
+
+
+@pytest.mark.parametrize("rnn,dirs,final,B,L", cases.PARENT_BITS_CASES)
+def test_forward_scans_carry_the_parent_commits_bits(rnn, dirs, final, B, L):
+    """out, fin, gates, c_seq of hcm_op_instr_scan_train and the output of hcm_op_instr_scan_infer, each pre-filled with NaN, carry the SHA-256
+    that tools/record_instr_scan_bits.py recorded with the three separate scan kernels in front of csrc/instr_scan.hip's one kernel, on inputs drawn
+    without a GEMM.  No case and no tensor is left out; a tensor the case does not have (c_seq of a GRU, the inference output of a per-token GRU) is
+    recorded as null and must be absent."""
+    want = _parent_bits()[cases.case_id(rnn, dirs, final, B, L)]
+    inputs, outputs = cases.forward_scan_digests(_lib.lib(), rnn, dirs, final, B, L)
+    assert inputs == want["inputs"], "the inputs drawn here are not the recorded ones: re-record the fixture at the parent commit (tools/record_instr_scan_bits.py)"
+    assert set(outputs) == set(want["outputs"]) == {"out", "fin", "gates", "c_seq", "infer_out"}
+    for k, v in want["outputs"].items():
+        assert outputs[k] == v, k
 
 
 @pytest.mark.parametrize("rnn,dirs,final", [("LSTM", 2, False), ("GRU", 2, False), ("LSTM", 1, True), ("GRU", 1, True)])

@@ -1,6 +1,6 @@
 """What the case lists of the four training ops reach, and whether their bound means anything where they reach it -- without a GPU.
 
-Coverage: the launch forms, run-time branches and sequence edges of csrc/vla_train.hip, csrc/embed_train.hip, csrc/instr_scan_train.hip and
+Coverage: the launch forms, run-time branches and sequence edges of csrc/vla_train.hip, csrc/embed_train.hip, csrc/instr_scan.hip and
 csrc/state_scan*.hip are chosen from the shapes alone, so the set a case list reaches can be computed here (the precedent is
 test_cases_straddle_the_row_block_and_the_k_slices of tests/test_embed_train_cpu.py).  Each assertion names a set that must be complete; a case
 taken out of a list leaves one of them short.
@@ -60,8 +60,8 @@ def test_prologue_cases_reach_every_k_slice_form_and_d_x_panel():
 
 
 def _samples_per_workgroup(B, dirs):
-    """instr_scan_train_sb of csrc/instr_scan_train.hip restated: the smallest of 2, 4, 8 that keeps ceil(B / SB) * dirs within 128 workgroups
-    (8 where none does).  A change to that rule must change this function, and the cases with it."""
+    """instr_scan_sb of csrc/instr_scan.hip, the one rule of the forward scan in every form and of the reverse scan, restated: the smallest of
+    2, 4, 8 that keeps ceil(B / SB) * dirs within 128 workgroups (8 where none does).  A change to that rule must change this function, and the cases with it."""
     for sb in (2, 4):
         if math.ceil(B / sb) * dirs <= 128:
             return sb

@@ -3,8 +3,7 @@ hcm_low_forward on the same frames in the same process, and the instruction chai
 an engine with all three ablated: what is left is embed + projection + scan).  One JSON line.
 
     python tools/bench_s2s.py [--instr-rnn GRU] [--reps 5] [--steps 40]
-    HCM_DEV_LIB=1 HCM_S2S_SCAN=2 python tools/bench_s2s.py --chain-only     # development build: the pre-existing all-outputs scan + gather (LSTM)
-    HCM_DEV_LIB=1 HCM_S2S_SCAN=0 python tools/bench_s2s.py --chain-only     # ... the per-token launch pairs
+    HCM_DEV_LIB=1 HCM_S2S_SCAN=0 python tools/bench_s2s.py --chain-only     # development build: the per-token launch pairs
 """
 import json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -64,7 +63,7 @@ for graph in (True, False):
     res[f"chain_plus_cell_{tag}"], _ = s2s(graph, ablate_depth=True, ablate_rgb=True)
     res[f"cell_only_{tag}"], _ = s2s(graph, ablate_depth=True, ablate_rgb=True, ablate_instruction=True)
     res[f"instr_chain_{tag}_ms"] = round(res[f"chain_plus_cell_{tag}"]["median_ms"] - res[f"cell_only_{tag}"]["median_ms"], 4)
-res["instr_chain_launches"] = {"1": 3, "2": 4, "0": 2 * L + 4}[res["scan_mode"]]      # by construction: embed, projection, (scan | scan + gather | reset + L pairs + copy)
+res["instr_chain_launches"] = {"1": 3, "0": 2 * L + 4}[res["scan_mode"]]      # by construction: embed, projection, (scan | reset + L pairs + copy)
 if "--chain-only" not in sys.argv:
     for graph in (True, False):
         tag = "graph" if graph else "eager"
