@@ -808,6 +808,40 @@ int hcm_op_attn1q_train(const float* qt, const float* x, const float* e, int lay
 int hcm_op_attn1q_bwd(const float* d_xbar, const float* qt, const float* x, const float* e, const float* a, int layout, float scale, float* d_qt,
                       float* d_x, float* d_e, float* work, int B, int C0, int Ce, int I, void* stream);
 
+/* The end of the flat trainer's update step, _update_agent (robo_vln_trainer.py:505-542), in float32 with a backward pass
+ * (csrc/flat_heads_train.hip): the heads of CMANet / Seq2SeqNet over the state encoder's rows and the criterion of hcm_flat_val_step.
+ *   out = x W_lin^T + b_lin (rows, num_actions);  stop = x W_stop^T + b_stop (rows, 1);  progress_hat = tanh(x W_pm^T + b_pm) (rows, 1)
+ *   x (rows, hidden); w_lin (num_actions, hidden), b_lin (num_actions), w_stop (1, hidden), b_stop (1), w_pm (1, hidden), b_pm (1) as nn.Linear
+ *   stores them; corrected_actions (rows, num_actions), oracle_stop (rows, 1), progress (rows,); all float32 on the device.
+ *   w_pm, b_pm, progress and progress_hat all NULL = no progress monitor; given together otherwise.
+ * hcm_op_flat_heads_loss_train, TWO launches: the heads (a wave per row, a fixed summation order over hidden, so a row's out / stop /
+ *   progress_hat bits depend on that row and the weights alone -- not on rows, the row's position or the grid), then flat_val_loss_kernel on them:
+ *   result (8,) has the bits of hcm_op_flat_val_loss fed this call's out, stop and progress_hat, and its meaning -- [0] the masked MSE, [1] the BCE
+ *   over the rows with oracle_stop != -1, [2] the aux mean over the rows with corrected_actions[r, 0] != 0 with weight 1.0 (the `alpha` quirk; 0
+ *   without the monitor), [3], [4] the two counts, [5..7] 0; NaN over an empty selection.  out and stop are the raw head outputs, as the model's
+ *   forward returns them: the masked_fill_ of :522 is applied inside the criterion only.
+ * hcm_op_flat_heads_loss_bwd, TWO launches, takes the cotangent d_result (8,) ON THE DEVICE ([0..2] = g0, g1, g2 are read; nothing is read back to
+ *   the host), the counts n_stop = result[3] and n_aux = result[4], and x, the weights, out, stop, progress_hat and the labels as the forward had
+ *   them.  Per row:  d_out[r, j] = g0 2 (out - c) / (rows num_actions), exactly 0 where c == 0;  d_stop[r] = g1 (sigmoid(stop) - y) / n_stop on the
+ *   selected rows, exactly 0 elsewhere;  d_pre[r] = g2 2 (p - y) (1 - p^2) / n_aux on the selected rows, exactly 0 elsewhere -- whatever the count:
+ *   with an empty selection the loss is NaN and that term's gradients are zeros, as torch's masked_select(...).mean() over nothing.  Then
+ *   d_x (rows, hidden) = sum_k d_head[r, k] W_k, or NULL: not computed;  d_W_k = sum_r d_head[r, k] x[r, :];  d_b_k = sum_r d_head[r, k]
+ *   into d_w_lin / d_b_lin / d_w_stop / d_b_stop / d_w_pm / d_b_pm (the last two NULL exactly when w_pm is).  A workgroup owns 32 rows and sums
+ *   its share in row order; a second launch adds the workgroups' shares from `work` in workgroup order.
+ * work: hcm_op_flat_heads_work_floats(rows, hidden, num_actions) floats (0 for unsupported sizes) owned by the caller, required by the backward.
+ *   No output may overlap it.  x, d_x, the weights, their gradients and work must be 16-byte aligned.
+ * hidden must be 512 and 1 <= num_actions <= 4; rows >= 0, and rows == 0 is HCM_OK, writes nothing and reads no pointer.  HCM_ERR_ARG with a message (hcm_last_error(NULL)), never
+ *   a launch: any other size, a NULL required pointer, the monitor's pointers disagreeing, an output overlapping work, a misaligned pointer.
+ * The ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible. */
+int64_t hcm_op_flat_heads_work_floats(int rows, int hidden, int num_actions);
+int hcm_op_flat_heads_loss_train(const float* x, const float* w_lin, const float* b_lin, const float* w_stop, const float* b_stop, const float* w_pm,
+                                 const float* b_pm, const float* corrected_actions, const float* oracle_stop, const float* progress, float* out,
+                                 float* stop, float* progress_hat, float* result, int rows, int hidden, int num_actions, void* stream);
+int hcm_op_flat_heads_loss_bwd(const float* d_result, const float* x, const float* w_lin, const float* w_stop, const float* w_pm, const float* out,
+                               const float* stop, const float* progress_hat, const float* corrected_actions, const float* oracle_stop,
+                               const float* progress, const float* result, float* d_x, float* d_w_lin, float* d_b_lin, float* d_w_stop,
+                               float* d_b_stop, float* d_w_pm, float* d_b_pm, float* work, int rows, int hidden, int num_actions, void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

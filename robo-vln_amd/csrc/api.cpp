@@ -1971,6 +1971,68 @@ int hcm_op_attn1q_bwd(const float* d_xbar, const float* qt, const float* x, cons
     return op_rc(launch_attn1q_train_bwd(t, (hipStream_t)stream));
 }
 
+int64_t hcm_op_flat_heads_work_floats(int rows, int hidden, int num_actions) {
+    return flat_heads_ok(rows, hidden, num_actions) ? (int64_t)flat_heads_work_floats(rows, num_actions) : 0;
+}
+
+static int flat_heads_arg_err(const char* what) {
+    g_create_err = std::string("flat_heads: ") + what;
+    return HCM_ERR_ARG;
+}
+static int flat_heads_dims(int rows, int hidden, int num_actions) {
+    if (hidden != 512) return flat_heads_arg_err("hidden must be 512");
+    if (num_actions < 1 || num_actions > 4) return flat_heads_arg_err("num_actions must be in 1..4");
+    if (rows < 0) return flat_heads_arg_err("rows must be at least 0");
+    return HCM_OK;
+}
+
+int hcm_op_flat_heads_loss_train(const float* x, const float* w_lin, const float* b_lin, const float* w_stop, const float* b_stop, const float* w_pm,
+                                 const float* b_pm, const float* corrected_actions, const float* oracle_stop, const float* progress, float* out,
+                                 float* stop, float* progress_hat, float* result, int rows, int hidden, int num_actions, void* stream) {
+    const int rc = flat_heads_dims(rows, hidden, num_actions);
+    if (rc != HCM_OK) return rc;
+    if (rows == 0) return HCM_OK;
+    if (!x || !w_lin || !b_lin || !w_stop || !b_stop || !corrected_actions || !oracle_stop || !out || !stop || !result)
+        return flat_heads_arg_err("a required pointer is NULL");
+    const bool monitor = w_pm != nullptr;
+    if ((b_pm != nullptr) != monitor || (progress != nullptr) != monitor || (progress_hat != nullptr) != monitor)
+        return flat_heads_arg_err("w_pm, b_pm, progress and progress_hat are given together or not at all");
+    if (!vla_train_aligned({x, w_lin, w_stop, w_pm}, {})) return flat_heads_arg_err("x and the weights must be 16-byte aligned");
+    FlatHeadsArgs t;
+    t.x = x; t.w_lin = w_lin; t.b_lin = b_lin; t.w_stop = w_stop; t.b_stop = b_stop; t.w_pm = w_pm; t.b_pm = b_pm;
+    t.corrected = corrected_actions; t.oracle_stop = oracle_stop; t.progress = progress;
+    t.out = out; t.stop = stop; t.progress_hat = progress_hat; t.result = result; t.rows = rows; t.num_actions = num_actions;
+    return op_rc(launch_flat_heads_fwd(t, (hipStream_t)stream));
+}
+
+int hcm_op_flat_heads_loss_bwd(const float* d_result, const float* x, const float* w_lin, const float* w_stop, const float* w_pm, const float* out,
+                               const float* stop, const float* progress_hat, const float* corrected_actions, const float* oracle_stop,
+                               const float* progress, const float* result, float* d_x, float* d_w_lin, float* d_b_lin, float* d_w_stop,
+                               float* d_b_stop, float* d_w_pm, float* d_b_pm, float* work, int rows, int hidden, int num_actions, void* stream) {
+    const int rc = flat_heads_dims(rows, hidden, num_actions);
+    if (rc != HCM_OK) return rc;
+    if (rows == 0) return HCM_OK;
+    if (!d_result || !x || !w_lin || !w_stop || !out || !stop || !corrected_actions || !oracle_stop || !result || !d_w_lin || !d_b_lin || !d_w_stop ||
+        !d_b_stop || !work)
+        return flat_heads_arg_err("a required pointer is NULL");
+    const bool monitor = w_pm != nullptr;
+    if ((progress_hat != nullptr) != monitor || (progress != nullptr) != monitor || (d_w_pm != nullptr) != monitor || (d_b_pm != nullptr) != monitor)
+        return flat_heads_arg_err("w_pm, progress_hat, progress, d_w_pm and d_b_pm are given together or not at all");
+    if (!vla_train_aligned({x, w_lin, w_stop, w_pm, d_x, d_w_lin, d_w_stop, d_w_pm, work}, {}))
+        return flat_heads_arg_err("x, d_x, the weights, their gradients and work must be 16-byte aligned");
+    const size_t A = (size_t)num_actions;
+    if (vla_train_in_work(work, flat_heads_work_floats(rows, num_actions),
+                          {{d_x, (size_t)rows * 512}, {d_w_lin, A * 512}, {d_b_lin, A}, {d_w_stop, 512}, {d_b_stop, 1}, {d_w_pm, 512}, {d_b_pm, 1}}))
+        return flat_heads_arg_err("an output overlaps work");
+    FlatHeadsArgs t;
+    t.d_result = d_result; t.x = x; t.w_lin = w_lin; t.w_stop = w_stop; t.w_pm = w_pm;
+    t.out = const_cast<float*>(out); t.stop = const_cast<float*>(stop); t.progress_hat = const_cast<float*>(progress_hat);
+    t.result = const_cast<float*>(result); t.corrected = corrected_actions; t.oracle_stop = oracle_stop; t.progress = progress;
+    t.d_x = d_x; t.d_w_lin = d_w_lin; t.d_b_lin = d_b_lin; t.d_w_stop = d_w_stop; t.d_b_stop = d_b_stop; t.d_w_pm = d_w_pm; t.d_b_pm = d_b_pm;
+    t.work = work; t.rows = rows; t.num_actions = num_actions;
+    return op_rc(launch_flat_heads_bwd(t, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

@@ -409,6 +409,24 @@ bool attn1q_train_ok(int B, int C0, int Ce, int I);
 size_t attn1q_train_work_floats(int B, int C0, int Ce, int I);
 hipError_t launch_attn1q_train_fwd(const Attn1qTrainArgs& t, hipStream_t s);
 hipError_t launch_attn1q_train_bwd(const Attn1qTrainArgs& t, hipStream_t s);
+// The heads and the criterion of the flat trainer's update step in float32 with a backward pass (flat_heads_train.hip): out = x W_lin^T + b_lin,
+// stop = x W_stop^T + b_stop, progress_hat = tanh(x W_pm^T + b_pm) over x (rows, 512), then launch_flat_val_loss on them.  One argument block for
+// both directions, as Attn1qTrainArgs; w_pm == null = no progress monitor (b_pm, progress, progress_hat, d_w_pm, d_b_pm unused).
+// work: flat_heads_work_floats() floats, the row blocks' d_W / d_b shares.  No allocation, no host copy, no synchronisation, no atomics.
+struct FlatHeadsArgs {
+    const float *x = nullptr, *w_lin = nullptr, *b_lin = nullptr, *w_stop = nullptr, *b_stop = nullptr, *w_pm = nullptr, *b_pm = nullptr;
+    const float *corrected = nullptr, *oracle_stop = nullptr, *progress = nullptr;     // [rows][num_actions], [rows], [rows]
+    float *out = nullptr, *stop = nullptr, *progress_hat = nullptr, *result = nullptr; // forward out / backward in: [rows][num_actions], [rows], [rows], [8]
+    const float* d_result = nullptr;                                                   // [8] on the device, [0..2] read
+    float *d_x = nullptr;                                                              // [rows][512] or null (not computed)
+    float *d_w_lin = nullptr, *d_b_lin = nullptr, *d_w_stop = nullptr, *d_b_stop = nullptr, *d_w_pm = nullptr, *d_b_pm = nullptr;
+    float* work = nullptr;
+    int rows = 0, num_actions = 0;
+};
+bool flat_heads_ok(int rows, int hidden, int num_actions);
+size_t flat_heads_work_floats(int rows, int num_actions);
+hipError_t launch_flat_heads_fwd(const FlatHeadsArgs& t, hipStream_t s);
+hipError_t launch_flat_heads_bwd(const FlatHeadsArgs& t, hipStream_t s);
 // dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
 hipError_t launch_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s);
 hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int* lengths, float* out,

@@ -24,7 +24,12 @@ the drop-in module.
 Differentiable CMANet: the reference's flat baseline (models/cma.py) from cached trunk features.  Its attention stage (cma.py:271-311) has one query
 per sample and keys that are a 1x1 convolution of the raw tokens, so the key projection folds into the query (qt = q W_k; q.b_k cancels in the
 softmax) and K and V are never formed: `attn1q` is the autograd function over csrc/cma_attn_train.hip, `attn1q_ref` the pure-torch restatement,
-`CMANet` the trainable model around it, `InstructionEncoder` and two `RNNStateEncoder`s."""
+`CMANet` the trainable model around it, `InstructionEncoder` and two `RNNStateEncoder`s.
+
+The flat trainer's update step: the reference's `_update_agent` (robo_vln_trainer.py:505-542).  Its end -- `linear`, `stop_linear`,
+tanh(`progress_monitor`) and the masked criteria -- is `flat_heads_loss`, the autograd function over csrc/flat_heads_train.hip (two launches forward,
+two backward), with `flat_heads_loss_ref` the pure-torch restatement; `Seq2SeqNet` is the second flat baseline (models/seq2seq.py) as a trainable
+model from cached trunk features, both models have `update_loss`, and `flat_update` is `_update_agent` around it."""
 import ctypes as C
 import math
 
@@ -866,6 +871,157 @@ def attn1q(qt, x, e, mask_zero, scale, layout):
     return _Attn1q.apply(qt, x, e, bool(mask_zero), float(scale), int(layout))
 
 
+FLAT_HEADS_HIDDEN, FLAT_HEADS_MAX_ACTIONS = 512, 4
+# the launch rules of csrc/flat_heads_train.hip: rows per workgroup of the heads launch, the backward's row block and its two halves, and the
+# thread count of the criterion launch (flat_val_loss_kernel: thread t adds the rows t, t + 256, ...)
+FLAT_HEADS_FWD_ROWS, FLAT_HEADS_BWD_ROWS, FLAT_HEADS_BWD_HALF, FLAT_LOSS_THREADS = 4, 32, 16, 256
+
+
+def flat_heads_ok(rows, hidden, num_actions):
+    """the sizes the kernels serve (include/hcm.h); rows == 0 is legal at the C ABI and writes nothing, so the wrapper leaves it to the restatement"""
+    return rows >= 1 and hidden == FLAT_HEADS_HIDDEN and 1 <= num_actions <= FLAT_HEADS_MAX_ACTIONS
+
+
+def flat_heads_loss_ref(x, w_lin, b_lin, w_stop, b_stop, w_pm, b_pm, corrected_actions, oracle_stop, progress):
+    """Pure-torch restatement, any dtype and device, of the three heads of the flat baselines (seq2seq.py:176-188, cma.py's last lines) and the
+    criterion of `_update_agent` (robo_vln_trainer.py:521-533), statement by statement, AuxLosses.reduce (common/aux_losses.py:27-33) included.
+    x (rows, hidden); the weights as nn.Linear stores them; w_pm / b_pm / progress None = no progress monitor (nothing is registered and reduce
+    returns 0.0).  The model passes PROGRESS_MONITOR.alpha in the `masks` slot of register_loss, so the weight of the registered loss is the
+    default 1.0; reproduced here.  Returns (result (8,), out, stop, progress_hat or None): result as hcm_flat_val_step writes it -- [action loss,
+    stop loss, aux loss, stop rows, aux rows, 0, 0, 0] -- differentiable in its first three entries; out and stop are the raw head outputs."""
+    F = torch.nn.functional
+    losses, alphas = {}, {}                                                   # AuxLosses.clear()
+    progress_hat = None
+    if w_pm is not None:
+        progress_hat = torch.tanh(F.linear(x, w_pm, b_pm))                     # seq2seq.py:177
+        losses["progress_monitor"] = F.mse_loss(progress_hat.squeeze(1), progress.reshape(-1).to(x.dtype), reduction="none")
+        alphas["progress_monitor"] = 1.0                                       # register_loss(name, loss, alpha): alpha lands in `masks`
+    output = F.linear(x, w_lin, b_lin)                                         # seq2seq.py:187
+    stop_out = F.linear(x, w_stop, b_stop)                                     # seq2seq.py:188
+    corrected_actions = corrected_actions.to(x.dtype).reshape(output.shape)
+    action_mask = corrected_actions == 0                                       # :521
+    masked = output.masked_fill(action_mask, 0)                                # :522, out of place: `output` is returned as the model gave it
+    action_loss = F.mse_loss(masked, corrected_actions)                        # :525
+    oracle_stop = oracle_stop.to(x.dtype).reshape(stop_out.shape)
+    mask = oracle_stop != -1                                                   # :527
+    stop_loss = F.binary_cross_entropy_with_logits(torch.masked_select(stop_out, mask), torch.masked_select(oracle_stop, mask))    # :528-530
+    aux_mask = ~action_mask[:, 0]                                              # :531
+    aux_loss = 0.0                                                             # AuxLosses.reduce
+    for k in losses:
+        aux_loss = aux_loss + alphas[k] * torch.masked_select(losses[k], aux_mask).mean()
+    zero = x.new_zeros(())
+    n_aux = aux_mask.sum().to(x.dtype) if losses else zero
+    aux_loss = aux_loss if losses else zero
+    result = torch.stack([action_loss, stop_loss, aux_loss, mask.sum().to(x.dtype), n_aux, zero, zero, zero])
+    return result, output, stop_out, progress_hat
+
+
+class _FlatHeadsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_lin, b_lin, w_stop, b_stop, w_pm, b_pm, corrected_actions, oracle_stop, progress):
+        if not x.is_cuda:
+            raise ValueError("flat_heads_loss runs on the device; CPU tensors go through flat_heads_loss_ref")
+        named = (("w_lin", w_lin), ("b_lin", b_lin), ("w_stop", w_stop), ("b_stop", b_stop), ("w_pm", w_pm), ("b_pm", b_pm),
+                 ("corrected_actions", corrected_actions), ("oracle_stop", oracle_stop), ("progress", progress))
+        for name, t in named:
+            if t is not None and t.device != x.device:    # the kernels take raw pointers: a host pointer would fault on the device
+                raise ValueError(f"flat_heads_loss: {name} is on {t.device}, x on {x.device}")
+        monitor = w_pm is not None
+        if (b_pm is not None) != monitor or (progress is not None) != monitor:
+            raise ValueError("flat_heads_loss: w_pm, b_pm and progress are given together or not at all")
+        if x.dim() != 2 or w_lin.dim() != 2 or not flat_heads_ok(x.shape[0], x.shape[1], w_lin.shape[0]):
+            raise ValueError(f"flat_heads_loss serves x (rows >= 1, {FLAT_HEADS_HIDDEN}) and 1..{FLAT_HEADS_MAX_ACTIONS} actions, got x {tuple(x.shape)}, "
+                             f"w_lin {tuple(w_lin.shape)}")
+        rows, H, A = x.shape[0], x.shape[1], w_lin.shape[0]
+        shapes = [("w_lin", w_lin, (A, H)), ("b_lin", b_lin, (A,)), ("w_stop", w_stop, (1, H)), ("b_stop", b_stop, (1,))]
+        if monitor:
+            shapes += [("w_pm", w_pm, (1, H)), ("b_pm", b_pm, (1,))]
+        for name, t, shape in shapes:
+            if tuple(t.shape) != shape:
+                raise ValueError(f"flat_heads_loss: {name} has shape {tuple(t.shape)}, expected {shape}")
+        for name, t, n in (("corrected_actions", corrected_actions, rows * A), ("oracle_stop", oracle_stop, rows), ("progress", progress, rows)):
+            if t is not None and t.numel() != n:
+                raise ValueError(f"flat_heads_loss: {name} has {t.numel()} elements, expected {n}")
+        x, w_lin, b_lin, w_stop, b_stop, corrected_actions, oracle_stop = (_f32c(t) for t in (x, w_lin, b_lin, w_stop, b_stop, corrected_actions,
+                                                                                             oracle_stop))
+        w_pm, b_pm, progress = (_f32c(t) if monitor else None for t in (w_pm, b_pm, progress))
+        dev = x.device
+        out, stop = torch.empty(rows, A, device=dev), torch.empty(rows, 1, device=dev)
+        progress_hat = torch.empty(rows, 1, device=dev) if monitor else None
+        result = torch.empty(8, device=dev)
+        _lib.check(_lib.lib().hcm_op_flat_heads_loss_train(_ptr(x), _ptr(w_lin), _ptr(b_lin), _ptr(w_stop), _ptr(b_stop), _ptr(w_pm), _ptr(b_pm),
+                                                           _ptr(corrected_actions), _ptr(oracle_stop), _ptr(progress), _ptr(out), _ptr(stop),
+                                                           _ptr(progress_hat), _ptr(result), rows, H, A, _stream()))
+        ctx.save_for_backward(x, w_lin, w_stop, w_pm, out, stop, progress_hat, corrected_actions, oracle_stop, progress, result)
+        ctx.dims = (rows, H, A)
+        ctx.mark_non_differentiable(out, stop)
+        if monitor:
+            ctx.mark_non_differentiable(progress_hat)
+        return result, out, stop, progress_hat
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_result, _d_out, _d_stop, _d_progress_hat):
+        x, w_lin, w_stop, w_pm, out, stop, progress_hat, corrected_actions, oracle_stop, progress, result = ctx.saved_tensors
+        rows, H, A = ctx.dims
+        need, dev, monitor = ctx.needs_input_grad, x.device, w_pm is not None
+        d_result = _f32c(d_result)
+        d_x = torch.empty(rows, H, device=dev) if need[0] else None
+        d_w_lin, d_b_lin = torch.empty(A, H, device=dev), torch.empty(A, device=dev)
+        d_w_stop, d_b_stop = torch.empty(1, H, device=dev), torch.empty(1, device=dev)
+        d_w_pm, d_b_pm = (torch.empty(1, H, device=dev), torch.empty(1, device=dev)) if monitor else (None, None)
+        work = torch.empty(_lib.lib().hcm_op_flat_heads_work_floats(rows, H, A), device=dev)
+        _lib.check(_lib.lib().hcm_op_flat_heads_loss_bwd(_ptr(d_result), _ptr(x), _ptr(w_lin), _ptr(w_stop), _ptr(w_pm), _ptr(out), _ptr(stop),
+                                                         _ptr(progress_hat), _ptr(corrected_actions), _ptr(oracle_stop), _ptr(progress), _ptr(result),
+                                                         _ptr(d_x), _ptr(d_w_lin), _ptr(d_b_lin), _ptr(d_w_stop), _ptr(d_b_stop), _ptr(d_w_pm),
+                                                         _ptr(d_b_pm), _ptr(work), rows, H, A, _stream()))
+        return (d_x, d_w_lin if need[1] else None, d_b_lin if need[2] else None, d_w_stop if need[3] else None, d_b_stop if need[4] else None,
+                d_w_pm if monitor and need[5] else None, d_b_pm if monitor and need[6] else None, None, None, None)
+
+
+def flat_heads_loss(x, w_lin, b_lin, w_stop, b_stop, w_pm, b_pm, corrected_actions, oracle_stop, progress):
+    """The heads and the criterion of the flat trainer's update step with gradients to x and the six head parameters: arguments and the returned
+    (result, out, stop, progress_hat) as flat_heads_loss_ref; `result` is the differentiable output, out / stop / progress_hat are marked
+    non-differentiable (the trainer forms its loss from the criterion alone).
+
+    Float32 device tensors with hidden 512, 1..4 actions and at least one row go through hcm_op_flat_heads_loss_train -- the heads launch and
+    flat_val_loss_kernel behind it, so `result` has the bits of hcm_op_flat_val_loss on this call's outputs -- and hcm_op_flat_heads_loss_bwd: one
+    launch for d_x (only when x requires a gradient) and the row blocks' shares of the parameter gradients, one ordered reduce.  The cotangent and
+    the counts are read on the device: nothing is read back to the host.  CPU tensors, other dtypes and unsupported sizes go through
+    flat_heads_loss_ref.  Nothing is cached between calls."""
+    args = (x, w_lin, b_lin, w_stop, b_stop, w_pm, b_pm, corrected_actions, oracle_stop, progress)
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or w_lin.dim() != 2 or not flat_heads_ok(x.shape[0], x.shape[1], w_lin.shape[0]):
+        return flat_heads_loss_ref(*args)
+    return _FlatHeadsLoss.apply(*args)
+
+
+def _progress_target(observations, monitor):
+    """observations["progress"] when the model has the monitor (a missing key raises, as S2SEngine.val_step does), None otherwise"""
+    if not monitor:
+        return None
+    if "progress" not in observations:
+        raise ValueError("observations['progress'] is missing: the model was built with the progress monitor")
+    return observations["progress"]
+
+
+def _heads_loss(model, x, corrected_actions, oracle_stop, progress):
+    """model._flat_heads (flat_heads_loss; tools/bench_flat_update.py swaps in the restatement) over a model's heads; the labels are brought to
+    x's device and dtype"""
+    rows = x.shape[0]
+    labels = [t.to(device=x.device, dtype=x.dtype) for t in (corrected_actions, oracle_stop)]
+    if labels[0].numel() != rows * model.linear.out_features or labels[1].numel() != rows:
+        raise ValueError(f"update_loss takes corrected_actions ({rows}, {model.linear.out_features}) and oracle_stop ({rows}, 1), got "
+                         f"{tuple(corrected_actions.shape)}, {tuple(oracle_stop.shape)}")
+    pm_w = pm_b = None
+    if progress is not None:
+        progress = progress.to(device=x.device, dtype=x.dtype)
+        if tuple(progress.shape) not in ((rows,), (rows, 1)):
+            raise ValueError(f"observations['progress'] must be ({rows},) or ({rows}, 1), got {tuple(progress.shape)}")
+        pm_w, pm_b = model.progress_monitor.weight, model.progress_monitor.bias
+    return model._flat_heads(x, model.linear.weight, model.linear.bias, model.stop_linear.weight, model.stop_linear.bias, pm_w, pm_b,
+                             labels[0], labels[1], progress)[0]
+
+
 class _CancelledBias(torch.autograd.Function):
     """y unchanged; `bias` -- a key projection's bias, which cancels in the softmax and takes no part in the forward -- receives a gradient of
     exact zeros, not None, so that an optimizer treats it as the reference's does"""
@@ -914,12 +1070,19 @@ class CMANet(nn.Module):
     train.InstructionEncoder and both state encoders train.RNNStateEncoder; the linear layers around them are torch.  rgb_linear and depth_linear
     take the feature and the embedding as two operands, so no (rows, C + 64, I) tensor exists.  The key biases -- text_k.bias and the first
     hidden/2 entries of rgb_kv.bias and depth_kv.bias -- cancel and receive exact zero gradients.  `_scale` is kept as the reference's buffer; the
-    stages use its constructor value 1 / sqrt(hidden / 2) as a host number, so nothing is read back from the device."""
+    stages use its constructor value 1 / sqrt(hidden / 2) as a host number, so nothing is read back from the device.
 
-    def __init__(self, cfg, embeddings=None):
+    update_loss(batch, corrected_actions, oracle_stop) is the model and the criterion of the trainer's update step; progress_monitor=True adds the
+    auxiliary progress loss to it (CMAConfig.validate keeps refusing its own flag: that is the engine's configuration).  forward is the same
+    either way, and without the keyword progress_monitor.* takes part in nothing."""
+
+    _flat_heads = staticmethod(flat_heads_loss)
+
+    def __init__(self, cfg, embeddings=None, progress_monitor=False):
         super().__init__()
         cfg.validate()
         self.cfg = cfg
+        self.monitor = bool(progress_monitor)
         hh, fs, cc = cfg.hidden // 2, cfg.depth_final_spatial(), cfg.depth_compress_channels()
         self.hh, self.depth_shape = hh, (cc, fs * fs)
         self.instruction_encoder = InstructionEncoder(vocab_size=cfg.vocab_size, embedding_size=cfg.embedding_size, hidden_size=cfg.instr_hidden,
@@ -939,7 +1102,7 @@ class CMANet(nn.Module):
         self.register_buffer("_scale", torch.tensor(self.scale))
         self.second_state_compress = nn.Sequential(nn.Linear(cfg.hidden + cfg.rgb_out + cfg.depth_out + cfg.instr_out, cfg.hidden), nn.ReLU(True))
         self.second_state_encoder = RNNStateEncoder(cfg.hidden, cfg.hidden, 1, cfg.rnn_type)
-        self.progress_monitor = nn.Linear(cfg.hidden, 1)      # parameters only: the progress-monitor loss is not built (CMAConfig refuses the flag)
+        self.progress_monitor = nn.Linear(cfg.hidden, 1)      # read by update_loss with progress_monitor=True; parameters only otherwise
         self.linear = nn.Linear(cfg.hidden, cfg.num_actions)
         self.stop_linear = nn.Linear(cfg.hidden, 1)
 
@@ -978,6 +1141,19 @@ class CMANet(nn.Module):
         return x, e, torch.relu(x_in)
 
     def forward(self, batch, taps=None):
+        x, hidden = self._encode(batch, taps)
+        return self.linear(x), self.stop_linear(x), hidden
+
+    def update_loss(self, batch, corrected_actions, oracle_stop):
+        """The forward and the criterion of `_update_agent` (robo_vln_trainer.py:515-533): the model up to the second state encoder, then
+        flat_heads_loss.  -> (result (8,), rnn_hidden_states); result[0] + result[1] + result[2] is the trainer's loss.  With progress_monitor=True
+        the auxiliary loss Seq2SeqNet registers (seq2seq.py:176-185) is formed on CMANet's progress_monitor against observations["progress"]."""
+        progress = _progress_target(batch[0], self.monitor)
+        x, hidden = self._encode(batch, None)
+        return _heads_loss(self, x, corrected_actions, oracle_stop, progress), hidden
+
+    def _encode(self, batch, taps):
+        """forward up to the second state encoder: (its output (rows, hidden), the new packed state)"""
         observations, rnn_hidden_states, prev_actions, masks = batch
         cfg, hh = self.cfg, self.hh
         masks = masks.reshape(masks.shape[0], -1)[:, 0]
@@ -1007,4 +1183,136 @@ class CMANet(nn.Module):
         x, h2 = self.second_state_encoder(x, rnn_hidden_states[R:], masks)
         if taps is not None:
             taps.update(state=state, text=text, rgb_att=att[0], depth_att=att[1], rnn2_out=x)
-        return self.linear(x), self.stop_linear(x), torch.cat([h1, h2], 0)
+        return x, torch.cat([h1, h2], 0)
+
+
+S2S_TRUNK_PREFIXES = CMA_TRUNK_PREFIXES
+
+
+class _FlatRgbEncoder(nn.Module):
+    """What TorchVisionResNet50 in flat mode keeps outside its frozen trunk (resnet_encoders.py:189-237): `fc`, 2048 -> output_size, ReLU behind it"""
+
+    def __init__(self, out):
+        super().__init__()
+        self.fc = nn.Linear(2048, out)
+
+
+class _FlatDepthEncoder(nn.Module):
+    """What VlnResnetDepthEncoder in flat mode keeps outside its frozen trunk (resnet_encoders.py:56-62): visual_fc = Flatten, Linear, ReLU"""
+
+    def __init__(self, in_features, out):
+        super().__init__()
+        self.visual_fc = nn.Sequential(nn.Flatten(), nn.Linear(in_features, out), nn.ReLU(True))
+
+
+class Seq2SeqNet(nn.Module):
+    """The reference's Seq2SeqNet (models/seq2seq.py:21-189) as a trainable model from cached trunk features: the reference's parameters, state-dict
+    keys and shapes outside the two frozen trunks (robo_vln_amd.synth.seq2seq_spec lists them), and its forward signature.  Takes a
+    robo_vln_amd.config.S2SConfig; `embeddings=` goes to InstructionEncoder.  The progress monitor is on when cfg.progress_monitor is set.
+
+    forward((observations, rnn_hidden_states, prev_actions, masks)) -> (output, stop_out, rnn_hidden_states) as seq2seq.py:140-189, with
+    observations["rgb_features"] (rows, 2048, 1, 1) and ["depth_features"] (rows, C, s, s) -- what S2SEngine.encode_features returns; an ablated
+    modality needs no key -- and ["instruction"] (rows, L) or (1, L): one instruction is encoded once and expanded (seq2seq.py:163).  The
+    instruction encoder is train.InstructionEncoder with final_state_only, the state encoder train.RNNStateEncoder; rgb_encoder.fc and
+    depth_encoder.visual_fc.1 with their ReLUs are torch; the cat is the reference's [instruction | depth | rgb].  sub_goal_linear holds
+    parameters only, as in the reference.  update_loss(batch, corrected_actions, oracle_stop) is the model and the criterion of the trainer's
+    update step, with the auxiliary progress loss against observations["progress"] when the monitor is on.
+
+    The SimpleCNN encoders are trunks that train with the model: there is nothing to cache, and they are refused."""
+
+    _flat_heads = staticmethod(flat_heads_loss)
+
+    def __init__(self, cfg, embeddings=None):
+        super().__init__()
+        cfg.validate()
+        if cfg.rgb_encoder != "TorchVisionResNet50" or cfg.depth_encoder != "VlnResnetDepthEncoder":
+            raise ValueError("train.Seq2SeqNet trains from cached features of the two frozen ResNet trunks; SimpleRGBCNN / SimpleDepthCNN are trainable "
+                             f"trunks with nothing to cache (got rgb_encoder {cfg.rgb_encoder!r}, depth_encoder {cfg.depth_encoder!r})")
+        self.cfg = cfg
+        self.monitor = bool(cfg.progress_monitor)
+        fs, cc = cfg.depth_final_spatial(), cfg.depth_compress_channels()
+        self.depth_shape = (cc, fs)
+        self.instruction_encoder = InstructionEncoder(vocab_size=cfg.vocab_size, embedding_size=cfg.embedding_size, hidden_size=cfg.instr_hidden,
+                                                      rnn_type=cfg.instr_rnn, bidirectional=False, final_state_only=True,
+                                                      fine_tune_embeddings=True, embeddings=embeddings)
+        self.depth_encoder = _FlatDepthEncoder(cc * fs * fs, cfg.depth_out)
+        self.rgb_encoder = _FlatRgbEncoder(cfg.rgb_out)
+        self.state_encoder = RNNStateEncoder(cfg.rnn_input_size, cfg.hidden, 1, cfg.rnn_type)
+        self.progress_monitor = nn.Linear(cfg.hidden, 1)
+        self.linear = nn.Linear(cfg.hidden, cfg.num_actions)
+        self.sub_goal_linear = nn.Linear(cfg.hidden, cfg.num_sub_tasks)      # parameters only (seq2seq.py:108): no forward reads it
+        self.stop_linear = nn.Linear(cfg.hidden, 1)
+        nn.init.kaiming_normal_(self.progress_monitor.weight, nonlinearity="tanh")     # _init_layers, seq2seq.py:136-138
+        nn.init.constant_(self.progress_monitor.bias, 0)
+
+    @property
+    def output_size(self):
+        return self.cfg.hidden
+
+    @property
+    def num_recurrent_layers(self):
+        return self.state_encoder.num_recurrent_layers
+
+    def load_reference_state_dict(self, sd):
+        """Load a reference Seq2SeqNet state dict (tensors or arrays): the keys of the two frozen trunks are dropped, everything else is strict --
+        a missing, unexpected or misshapen key raises"""
+        kept = {k: torch.as_tensor(v) for k, v in sd.items() if not k.startswith(S2S_TRUNK_PREFIXES)}
+        return self.load_state_dict(kept, strict=True)
+
+    def _visual(self, name, feat, fc, ablated, rows, shape, like):
+        """One modality's embedding relu(fc(flatten(feature))) (rows, out) from the trunk feature; ablated: times 0 (seq2seq.py:158-161), and
+        exact zeros without the key"""
+        if feat is None:
+            if ablated:
+                return like.new_zeros(rows, fc.out_features)
+            raise ValueError(f"Seq2SeqNet trains from cached trunk features: observations['{name}_features'] is missing; S2SEngine.encode_features "
+                             "returns it from the frames")
+        if tuple(feat.shape) != (rows, *shape):
+            raise ValueError(f"Seq2SeqNet takes {name}_features {(rows, *shape)} as S2SEngine.encode_features returns them, got {tuple(feat.shape)}")
+        y = torch.relu(fc(feat.flatten(1)))                                   # Flatten in NCHW order
+        return y * 0 if ablated else y
+
+    def _encode(self, batch):
+        """forward up to the state encoder: (its output (rows, hidden), the new packed state)"""
+        observations, rnn_hidden_states, prev_actions, masks = batch
+        cfg = self.cfg
+        masks = masks.reshape(masks.shape[0], -1)[:, 0]                       # :172
+        rows = masks.shape[0]
+        instruction = observations["instruction"].long()
+        if instruction.dim() != 2 or instruction.shape[0] not in (1, rows):
+            raise ValueError(f"Seq2SeqNet takes instruction ({rows} or 1, L), got {tuple(instruction.shape)}")
+        ins = self.instruction_encoder(instruction)                           # :153
+        cc, fs = self.depth_shape
+        depth = self._visual("depth", observations.get("depth_features"), self.depth_encoder.visual_fc[1], cfg.ablate_depth, rows, (cc, fs, fs), ins)
+        rgb = self._visual("rgb", observations.get("rgb_features"), self.rgb_encoder.fc, cfg.ablate_rgb, rows, (2048, 1, 1), ins)
+        if cfg.ablate_instruction:
+            ins = ins * 0                                                     # :156-157
+        ins = ins.expand(rows, ins.shape[1])                                  # :163
+        x = torch.cat([ins, depth, rgb], 1)                                   # :164
+        return self.state_encoder(x, rnn_hidden_states, masks)                # :174
+
+    def forward(self, batch):
+        x, hidden = self._encode(batch)
+        return self.linear(x), self.stop_linear(x), hidden
+
+    def update_loss(self, batch, corrected_actions, oracle_stop):
+        """The forward and the criterion of `_update_agent` (robo_vln_trainer.py:515-533): the model up to the state encoder, then flat_heads_loss.
+        -> (result (8,), rnn_hidden_states); result[0] + result[1] + result[2] is the trainer's loss."""
+        progress = _progress_target(batch[0], self.monitor)
+        x, hidden = self._encode(batch)
+        return _heads_loss(self, x, corrected_actions, oracle_stop, progress), hidden
+
+
+def flat_update(model, optimizer, observations, prev_actions, not_done_masks, corrected_actions, oracle_stop, rnn_hidden_states):
+    """The reference's `_update_agent` (robo_vln_trainer.py:505-542) for train.CMANet / train.Seq2SeqNet: zero_grad, detach the carried state
+    (repackage_hidden), model.update_loss, loss = result[0] + result[1] + result[2], backward, optimizer.step().  Returns (result, rnn_hidden_states)
+    with `result` the detached (8,) tensor on the model's device -- [action loss, stop loss, aux loss, stop rows, aux rows, 0, 0, 0] -- where the
+    reference returns three host numbers: nothing is read back and nothing synchronises, so a caller keeps the results of an epoch and reads once,
+    as FlatValidator does."""
+    optimizer.zero_grad()
+    rnn_hidden_states = rnn_hidden_states.detach()
+    result, rnn_hidden_states = model.update_loss((observations, rnn_hidden_states, prev_actions, not_done_masks), corrected_actions, oracle_stop)
+    loss = result[0] + result[1] + result[2]
+    loss.backward()
+    optimizer.step()
+    return result.detach(), rnn_hidden_states
