@@ -842,6 +842,38 @@ int hcm_op_flat_heads_loss_bwd(const float* d_result, const float* x, const floa
                                const float* progress, const float* result, float* d_x, float* d_w_lin, float* d_b_lin, float* d_w_stop,
                                float* d_b_stop, float* d_w_pm, float* d_b_pm, float* work, int rows, int hidden, int num_actions, void* stream);
 
+/* The end of the hierarchical trainer's high-level update step, _update_agent (hierarchical_trainer.py:506-512), in float32 with a backward pass
+ * (csrc/subtask_ce_train.hip): the head of Seq2Seq_HighLevel_CMA over the state encoder's rows and the cross-entropy of hcm_val_step.
+ *   logits = x W^T + b (rows, A);  x (rows, hidden); w (A, hidden), b (A) as nn.Linear stores them; all float32 on the device.
+ *   oracle_subtask (rows,) int64 on the device, as hcm_val_step takes it: 0 = padded row, 1..num_sub_tasks = the target class plus one; a value
+ *   outside [0, num_sub_tasks] is counted in result[6] and treated as padded.
+ * hcm_op_subtask_ce_train, TWO launches: the head (a wave per row, a fixed summation order over hidden, so a row's logits bits depend on that
+ *   row and the weights alone -- not on rows, the row's position or the grid), then the criterion with val_loss_kernel's arithmetic, launch shape
+ *   and order of summation (one workgroup of 256 threads, thread t adds rows t, t + 256, ..., a xor butterfly, then the waves in wave order).
+ *   result (8,) uses the index positions of hcm_val_step: [0] CrossEntropyLoss(ignore_index = -1, mean) of logits against oracle_subtask - 1
+ *   over the valid rows, [3] the valid rows whose argmax (first maximal index) is the target, [4] the valid rows, [6] the out-of-range rows,
+ *   [1] = [2] = [5] = [7] = 0; words [0], [3], [4], [6] have the bits of hcm_op_val_loss fed this call's logits.  No valid row: NaN in [0] and
+ *   counts of 0, as torch gives; a NaN in a valid row's logits propagates into [0].  logits is the raw head output, as the model's forward
+ *   returns it: the masked_fill_ of :509 touches padded rows only, which the criterion ignores.
+ * hcm_op_subtask_ce_bwd, TWO launches, takes the cotangent d_result (8,) ON THE DEVICE ([0] = g0 is read; nothing is read back to the host), the
+ *   count total = result[4], and x, w, logits and the labels as the forward had them.  Per valid row, with the softmax recomputed around the row
+ *   maximum from the saved logits:  d_logits[r, j] = g0 (softmax(logits[r])[j] - [j == target]) / total;  exactly 0 on padded and out-of-range
+ *   rows, and on every row when total == 0 (the loss is NaN and the gradients are zeros, as torch's).  Then
+ *   d_x (rows, hidden) = d_logits W, or NULL: not computed;  d_w (A, hidden) = d_logits^T x;  d_b (A) = sum_r d_logits[r].  A workgroup owns 32
+ *   rows (two halves of 16) and sums its share in row order; a second launch adds the workgroups' shares from `work` in workgroup order.
+ * work: hcm_op_subtask_ce_work_floats(rows, hidden, A) floats (0 for unsupported sizes) owned by the caller, required by the backward.  No
+ *   output may overlap it.  x, w, d_x, d_w and work must be 16-byte aligned, the other float tensors 4-byte and oracle_subtask 8-byte aligned.
+ * hidden must be 512 and 1 <= num_sub_tasks <= A <= 6; rows >= 0, and rows == 0 is HCM_OK, writes nothing and reads no pointer.  HCM_ERR_ARG
+ *   with a message (hcm_last_error(NULL)), never a launch: any other size, a NULL required pointer, an output overlapping work, a misaligned
+ *   pointer.
+ * The ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible. */
+int64_t hcm_op_subtask_ce_work_floats(int rows, int hidden, int A);
+int hcm_op_subtask_ce_train(const float* x, const float* w, const float* b, const int64_t* oracle_subtask, float* logits, float* result, int rows,
+                            int hidden, int A, int num_sub_tasks, void* stream);
+int hcm_op_subtask_ce_bwd(const float* d_result, const float* x, const float* w, const float* logits, const int64_t* oracle_subtask,
+                          const float* result, float* d_x, float* d_w, float* d_b, float* work, int rows, int hidden, int A, int num_sub_tasks,
+                          void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

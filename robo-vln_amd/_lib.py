@@ -158,6 +158,9 @@ EXPORTS = {
     "hcm_op_flat_heads_work_floats": (C.c_int64, [C.c_int] * 3),
     "hcm_op_flat_heads_loss_train": (C.c_int, [C.c_void_p] * 14 + [C.c_int] * 3 + [C.c_void_p]),
     "hcm_op_flat_heads_loss_bwd": (C.c_int, [C.c_void_p] * 20 + [C.c_int] * 3 + [C.c_void_p]),
+    "hcm_op_subtask_ce_work_floats": (C.c_int64, [C.c_int] * 3),
+    "hcm_op_subtask_ce_train": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_subtask_ce_bwd": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_void_p]),
     "hcm_op_feat_ingest":(C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),

@@ -2033,6 +2033,54 @@ int hcm_op_flat_heads_loss_bwd(const float* d_result, const float* x, const floa
     return op_rc(launch_flat_heads_bwd(t, (hipStream_t)stream));
 }
 
+int64_t hcm_op_subtask_ce_work_floats(int rows, int hidden, int A) {
+    return subtask_ce_ok(rows, hidden, A, 1) ? (int64_t)subtask_ce_work_floats(rows, A) : 0;
+}
+
+static int subtask_ce_arg_err(const char* what) {
+    g_create_err = std::string("subtask_ce: ") + what;
+    return HCM_ERR_ARG;
+}
+static int subtask_ce_dims(int rows, int hidden, int A, int num_sub_tasks) {
+    if (hidden != 512) return subtask_ce_arg_err("hidden must be 512");
+    if (A < 1 || A > 6) return subtask_ce_arg_err("A must be in 1..6");
+    if (num_sub_tasks < 1 || num_sub_tasks > A) return subtask_ce_arg_err("num_sub_tasks must be in 1..A");
+    if (rows < 0) return subtask_ce_arg_err("rows must be at least 0");
+    return HCM_OK;
+}
+
+int hcm_op_subtask_ce_train(const float* x, const float* w, const float* b, const int64_t* oracle_subtask, float* logits, float* result, int rows,
+                            int hidden, int A, int num_sub_tasks, void* stream) {
+    const int rc = subtask_ce_dims(rows, hidden, A, num_sub_tasks);
+    if (rc != HCM_OK) return rc;
+    if (rows == 0) return HCM_OK;
+    if (!x || !w || !b || !oracle_subtask || !logits || !result) return subtask_ce_arg_err("a required pointer is NULL");
+    if (!vla_train_aligned({x, w}, {b, logits, result}) || (uintptr_t)oracle_subtask % 8)
+        return subtask_ce_arg_err("x and w must be 16-byte aligned, b, logits and result 4-byte, oracle_subtask 8-byte");
+    SubtaskCeArgs t;
+    t.x = x; t.w = w; t.b = b; t.oracle = oracle_subtask; t.logits = logits; t.result = result;
+    t.rows = rows; t.A = A; t.num_sub_tasks = num_sub_tasks;
+    return op_rc(launch_subtask_ce_fwd(t, (hipStream_t)stream));
+}
+
+int hcm_op_subtask_ce_bwd(const float* d_result, const float* x, const float* w, const float* logits, const int64_t* oracle_subtask,
+                          const float* result, float* d_x, float* d_w, float* d_b, float* work, int rows, int hidden, int A, int num_sub_tasks,
+                          void* stream) {
+    const int rc = subtask_ce_dims(rows, hidden, A, num_sub_tasks);
+    if (rc != HCM_OK) return rc;
+    if (rows == 0) return HCM_OK;
+    if (!d_result || !x || !w || !logits || !oracle_subtask || !result || !d_w || !d_b || !work) return subtask_ce_arg_err("a required pointer is NULL");
+    if (!vla_train_aligned({x, w, d_x, d_w, work}, {d_result, logits, result, d_b}) || (uintptr_t)oracle_subtask % 8)
+        return subtask_ce_arg_err("x, w, d_x, d_w and work must be 16-byte aligned, the other float tensors 4-byte, oracle_subtask 8-byte");
+    if (vla_train_in_work(work, subtask_ce_work_floats(rows, A), {{d_x, (size_t)rows * 512}, {d_w, (size_t)A * 512}, {d_b, (size_t)A}}))
+        return subtask_ce_arg_err("an output overlaps work");
+    SubtaskCeArgs t;
+    t.d_result = d_result; t.x = x; t.w = w; t.logits = const_cast<float*>(logits); t.oracle = oracle_subtask;
+    t.result = const_cast<float*>(result); t.d_x = d_x; t.d_w = d_w; t.d_b = d_b; t.work = work;
+    t.rows = rows; t.A = A; t.num_sub_tasks = num_sub_tasks;
+    return op_rc(launch_subtask_ce_bwd(t, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

@@ -427,6 +427,24 @@ bool flat_heads_ok(int rows, int hidden, int num_actions);
 size_t flat_heads_work_floats(int rows, int num_actions);
 hipError_t launch_flat_heads_fwd(const FlatHeadsArgs& t, hipStream_t s);
 hipError_t launch_flat_heads_bwd(const FlatHeadsArgs& t, hipStream_t s);
+// The head and the criterion of the hierarchical trainer's high-level update step in float32 with a backward pass (subtask_ce_train.hip):
+// logits = x W^T + b over x (rows, 512), then the cross-entropy words of launch_val_loss over them (result [0], [3], [4], [6]; the rest 0).  One
+// argument block for both directions, as FlatHeadsArgs.  work: subtask_ce_work_floats() floats, the row blocks' d_W / d_b shares.  No allocation,
+// no host copy, no synchronisation, no atomics.
+struct SubtaskCeArgs {
+    const float *x = nullptr, *w = nullptr, *b = nullptr;                              // [rows][512], [A][512], [A]
+    const int64_t* oracle = nullptr;                                                   // [rows]: 0 padded, 1..num_sub_tasks valid, else counted and padded
+    float *logits = nullptr, *result = nullptr;                                        // forward out / backward in: [rows][A], [8]
+    const float* d_result = nullptr;                                                   // [8] on the device, [0] read
+    float *d_x = nullptr;                                                              // [rows][512] or null (not computed)
+    float *d_w = nullptr, *d_b = nullptr;                                              // [A][512], [A]
+    float* work = nullptr;
+    int rows = 0, A = 0, num_sub_tasks = 0;
+};
+bool subtask_ce_ok(int rows, int hidden, int A, int num_sub_tasks);
+size_t subtask_ce_work_floats(int rows, int A);
+hipError_t launch_subtask_ce_fwd(const SubtaskCeArgs& t, hipStream_t s);
+hipError_t launch_subtask_ce_bwd(const SubtaskCeArgs& t, hipStream_t s);
 // dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
 hipError_t launch_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s);
 hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int* lengths, float* out,

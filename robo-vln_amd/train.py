@@ -29,7 +29,13 @@ softmax) and K and V are never formed: `attn1q` is the autograd function over cs
 The flat trainer's update step: the reference's `_update_agent` (robo_vln_trainer.py:505-542).  Its end -- `linear`, `stop_linear`,
 tanh(`progress_monitor`) and the masked criteria -- is `flat_heads_loss`, the autograd function over csrc/flat_heads_train.hip (two launches forward,
 two backward), with `flat_heads_loss_ref` the pure-torch restatement; `Seq2SeqNet` is the second flat baseline (models/seq2seq.py) as a trainable
-model from cached trunk features, both models have `update_loss`, and `flat_update` is `_update_agent` around it."""
+model from cached trunk features, both models have `update_loss`, and `flat_update` is `_update_agent` around it.
+
+The hierarchical trainer's update step: the reference's `_update_agent` (hierarchical_trainer.py:492-560).  The high-level criterion -- `linear`,
+masked_fill_, CrossEntropyLoss(ignore_index=-1) -- is `subtask_ce`, the autograd function over csrc/subtask_ce_train.hip (two launches forward, two
+backward), with `subtask_ce_ref` the pure-torch restatement; `HighLevel` (models/seq2seq_highlevel_cma.py, the frozen BERT's output entering as a
+tensor) and `LowLevel` (models/seq2seq_lowlevel.py, its heads on `flat_heads_loss`) are the pair as trainable models from cached trunk features,
+and `hier_update` is `_update_agent` around them."""
 import ctypes as C
 import math
 
@@ -1316,3 +1322,373 @@ def flat_update(model, optimizer, observations, prev_actions, not_done_masks, co
     loss.backward()
     optimizer.step()
     return result.detach(), rnn_hidden_states
+
+
+SUBTASK_CE_HIDDEN, SUBTASK_CE_MAX_CLASSES = 512, 6
+# the launch rules of csrc/subtask_ce_train.hip: rows per workgroup of the head launch, the backward's row block and its two halves, and the
+# thread count of the criterion launch (thread t adds the rows t, t + 256, ...: val_loss_kernel's shape)
+SUBTASK_CE_FWD_ROWS, SUBTASK_CE_BWD_ROWS, SUBTASK_CE_BWD_HALF, SUBTASK_CE_LOSS_THREADS = 4, 32, 16, 256
+
+
+def subtask_ce_ok(rows, hidden, A, num_sub_tasks):
+    """the sizes the kernels serve (include/hcm.h); rows == 0 is legal at the C ABI and writes nothing, so the wrapper leaves it to the restatement"""
+    return rows >= 1 and hidden == SUBTASK_CE_HIDDEN and 1 <= num_sub_tasks <= A <= SUBTASK_CE_MAX_CLASSES
+
+
+def _subtask_labels(oracle_subtask, rows, device):
+    """the label tensor as the collate function carries it -- (rows, 1) float, or any integer tensor of rows elements -- as (rows,) int64 on
+    `device`: moved first, converted there"""
+    if oracle_subtask.numel() != rows:
+        raise ValueError(f"subtask_ce takes one sub-task label per row: {rows} rows, oracle_subtask {tuple(oracle_subtask.shape)}")
+    return oracle_subtask.detach().to(device).reshape(-1).to(torch.int64).contiguous()
+
+
+def subtask_ce_ref(x, w, b, oracle_subtask, num_sub_tasks=None):
+    """Pure-torch restatement, any dtype and device, of the high-level model's head (seq2seq_highlevel_cma.py:232) and the criterion of
+    `_update_agent` (hierarchical_trainer.py:506-511), statement by statement.  x (rows, hidden); w, b as nn.Linear stores them (A classes);
+    oracle_subtask (rows,) or (rows, 1), float or integer: 0 = padded row, 1..num_sub_tasks = the target class plus one (num_sub_tasks = A
+    when not given); a label outside [0, num_sub_tasks] is counted and treated as padded, as tests/val_ref.criteria does.  Returns
+    (result (8,), logits): result in the index positions of hcm_val_step -- [0] the cross-entropy, [3] correct, [4] total, [6] out-of-range rows,
+    the rest 0 -- differentiable in its first entry; logits is the raw head output."""
+    F = torch.nn.functional
+    A = w.shape[0]
+    num_sub_tasks = A if num_sub_tasks is None else int(num_sub_tasks)
+    if not 1 <= num_sub_tasks <= A:
+        raise ValueError(f"subtask_ce: num_sub_tasks must be in 1..{A} (the head's classes), got {num_sub_tasks}")
+    output = F.linear(x, w, b)                                                 # :506, the model's `self.linear(x)`
+    oracle = _subtask_labels(oracle_subtask, output.shape[0], x.device)
+    bad = (oracle < 0) | (oracle > num_sub_tasks)
+    oracle = oracle.masked_fill(bad, 0)                                        # counted, then treated as padded
+    high_level_action_mask = (oracle == 0).view(-1, 1)                         # :508
+    masked = output.masked_fill(high_level_action_mask, 0)                     # :509, out of place: `output` is returned as the model gave it
+    target = oracle - 1                                                        # :510-511; -1 on the padded rows: ignore_index
+    loss = F.cross_entropy(masked, target, ignore_index=-1, reduction="mean")  # :498, :511
+    valid = ~high_level_action_mask[:, 0]
+    correct = ((torch.argmax(output.detach(), 1) == target) & valid).sum().to(x.dtype)
+    zero = x.new_zeros(())
+    result = torch.stack([loss, zero, zero, correct, valid.sum().to(x.dtype), zero, bad.sum().to(x.dtype), zero])
+    return result, output
+
+
+class _SubtaskCe(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, oracle, num_sub_tasks):
+        if not x.is_cuda:
+            raise ValueError("subtask_ce runs on the device; CPU tensors go through subtask_ce_ref")
+        for name, t in (("w", w), ("b", b), ("oracle_subtask", oracle)):
+            if t.device != x.device:                      # the kernels take raw pointers: a host pointer would fault on the device
+                raise ValueError(f"subtask_ce: {name} is on {t.device}, x on {x.device}")
+        if x.dim() != 2 or w.dim() != 2 or not subtask_ce_ok(x.shape[0], x.shape[1], w.shape[0], num_sub_tasks):
+            raise ValueError(f"subtask_ce serves x (rows >= 1, {SUBTASK_CE_HIDDEN}) and 1 <= num_sub_tasks <= A <= {SUBTASK_CE_MAX_CLASSES} classes, got "
+                             f"x {tuple(x.shape)}, w {tuple(w.shape)}, num_sub_tasks {num_sub_tasks}")
+        rows, H, A = x.shape[0], x.shape[1], w.shape[0]
+        for name, t, shape in (("w", w, (A, H)), ("b", b, (A,)), ("oracle_subtask", oracle, (rows,))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"subtask_ce: {name} has shape {tuple(t.shape)}, expected {shape}")
+        if oracle.dtype != torch.int64:
+            raise ValueError(f"subtask_ce: the labels reach the kernels as int64, got {oracle.dtype}")
+        x, w, b = (_f32c(t) for t in (x, w, b))
+        oracle = oracle.contiguous()
+        logits, result = torch.empty(rows, A, device=x.device), torch.empty(8, device=x.device)
+        _lib.check(_lib.lib().hcm_op_subtask_ce_train(_ptr(x), _ptr(w), _ptr(b), _ptr(oracle), _ptr(logits), _ptr(result), rows, H, A, num_sub_tasks,
+                                                      _stream()))
+        ctx.save_for_backward(x, w, logits, oracle, result)
+        ctx.dims = (rows, H, A, num_sub_tasks)
+        ctx.mark_non_differentiable(logits)
+        return result, logits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_result, _d_logits):
+        x, w, logits, oracle, result = ctx.saved_tensors
+        rows, H, A, num_sub_tasks = ctx.dims
+        need, dev = ctx.needs_input_grad, x.device
+        d_result = _f32c(d_result)
+        d_x = torch.empty(rows, H, device=dev) if need[0] else None
+        d_w, d_b = torch.empty(A, H, device=dev), torch.empty(A, device=dev)
+        work = torch.empty(_lib.lib().hcm_op_subtask_ce_work_floats(rows, H, A), device=dev)
+        _lib.check(_lib.lib().hcm_op_subtask_ce_bwd(_ptr(d_result), _ptr(x), _ptr(w), _ptr(logits), _ptr(oracle), _ptr(result), _ptr(d_x), _ptr(d_w),
+                                                    _ptr(d_b), _ptr(work), rows, H, A, num_sub_tasks, _stream()))
+        return d_x, d_w if need[1] else None, d_b if need[2] else None, None, None
+
+
+def subtask_ce(x, w, b, oracle_subtask, num_sub_tasks=None):
+    """The head and the criterion of the hierarchical trainer's high-level update step with gradients to x, w and b: arguments and the returned
+    (result, logits) as subtask_ce_ref; `result` is the differentiable output, logits is marked non-differentiable (the trainer forms its loss from
+    the criterion alone).
+
+    Float32 device tensors with hidden 512, 1 <= num_sub_tasks <= A <= 6 classes and at least one row go through hcm_op_subtask_ce_train -- the
+    head launch and the criterion launch behind it, so result[0], [3], [4], [6] have the bits of hcm_op_val_loss on this call's logits -- and
+    hcm_op_subtask_ce_bwd: one launch for d_x (only when x requires a gradient) and the row blocks' shares of d_w and d_b, one ordered reduce.  The
+    labels are converted to int64 on the device; the cotangent and the count are read there: nothing is read back to the host.  CPU tensors,
+    other dtypes and unsupported sizes go through subtask_ce_ref.  Nothing is cached between calls."""
+    nst = w.shape[0] if num_sub_tasks is None else int(num_sub_tasks)
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or w.dim() != 2 or not subtask_ce_ok(x.shape[0], x.shape[1], w.shape[0], nst):
+        return subtask_ce_ref(x, w, b, oracle_subtask, num_sub_tasks)
+    return _SubtaskCe.apply(x, w, b, _subtask_labels(oracle_subtask, x.shape[0], x.device), nst)
+
+
+def _model_slot(feat, slot):
+    """one model's entry of a feature HCMEngine.encode_features returned for both: (high, low) pairs -> entry `slot`; a tensor is taken as it is"""
+    return feat[slot] if isinstance(feat, (tuple, list)) else feat
+
+
+HCM_HIGH_FROZEN_PREFIXES = ("rgb_encoder.cnn.", "depth_encoder.visual_encoder.", "embedding_layer.")
+HCM_LOW_FROZEN_PREFIXES = CMA_TRUNK_PREFIXES
+
+
+def _refuse_simple_cnn(cls, cfg):
+    if cfg.rgb_encoder != "TorchVisionResNet50" or cfg.depth_encoder != "VlnResnetDepthEncoder":
+        raise ValueError(f"train.{cls} trains from cached features of the two frozen ResNet trunks; SimpleRGBCNN / SimpleDepthCNN are trainable "
+                         f"trunks with nothing to cache (got rgb_encoder {cfg.rgb_encoder!r}, depth_encoder {cfg.depth_encoder!r})")
+
+
+class HighLevel(nn.Module):
+    """The reference's Seq2Seq_HighLevel_CMA (models/seq2seq_highlevel_cma.py:29-233) as a trainable model from cached trunk features and a cached
+    instruction stream: the reference's parameters, state-dict keys and shapes outside its three frozen parts -- the two trunks and BERT
+    (robo_vln_amd.synth.high_level_spec lists them all) -- and its forward signature.  Takes a robo_vln_amd.config.HCMConfig; `dropout` is
+    VISUAL_LING_ATTN.dropout (config/default.py:164); `embedder`, optional, maps token ids (B, L) to BERT's last hidden state (B, L, ins_in).
+
+    forward((observations, rnn_hidden_states, prev_actions, masks)) -> (logits, rnn_hidden_states) as :170-233, with
+    observations["rgb_features"] (rows, 2048, 4, 4) and ["depth_features"] (rows, C, s, s) -- the high entries of HCMEngine.encode_features' pairs;
+    a pair is accepted and its entry 0 taken; an ablated modality needs no key -- and ["instruction_features"] (rows or 1, L, ins_in): BERT is
+    frozen and runs under no_grad in the reference (:192-195), so its output enters as a tensor.  Without that key the stream is
+    embedder(observations["instruction"]) under no_grad; with neither a ValueError names the key.
+
+    rgb_kv / depth_kv are 1x1 convolutions of [feature | spatial embedding]: the tokens are x^T W[:, :C0]^T plus a row-independent (I, vis_in)
+    tail from the spatial table and the bias, computed once per call -- no (rows, C0 + 64, I) tensor is formed -- and rgb_linear / depth_linear
+    take the two operands as train.CMANet's do.  Then the two Visual_Ling_Attn calls on the one image_cm_encoder, the token mean over all L
+    positions (cross_pooler), the cat [rgb_in | depth_in | ins_rgb | ins_depth], train.RNNStateEncoder and `linear`.  ablate_rgb / ablate_depth zero
+    the whole embedding, the spatial tail included (:185-188); ablate_instruction and use_prev_action are branches the reference cannot run and
+    HCMConfig.validate refuses them.  ins_fc and progress_monitor hold parameters only: no forward of the reference reads the first, the
+    monitor's branch reads an undefined name (:221-224) and the trainer adds no aux loss.
+
+    update_loss(batch, oracle_subtask) -> (result (8,), rnn_hidden_states) is the model and the criterion of the trainer's high-level step through
+    subtask_ce; result[0] is the loss."""
+
+    _subtask_ce = staticmethod(subtask_ce)
+
+    def __init__(self, cfg, embedder=None, dropout=0.25):
+        super().__init__()
+        cfg.validate()
+        _refuse_simple_cnn("HighLevel", cfg)
+        self.cfg = cfg
+        object.__setattr__(self, "embedder", embedder)        # frozen and the caller's: not a submodule, so no key of it enters the state dict
+        fs, cc = cfg.depth_final_spatial(), cfg.depth_compress_channels()
+        self.depth_shape = (cc, fs * fs)
+        self.ins_fc = nn.Linear(768, 256)                     # TRANSFORMER_INSTRUCTION_ENCODER d_in / d_model (:46): parameters only
+        self.depth_encoder = _SpatialEncoder(fs * fs)
+        self.rgb_encoder = _SpatialEncoder(16)
+        self.rgb_linear = nn.Sequential(nn.AdaptiveAvgPool1d(1), nn.Flatten(), nn.Linear(2048 + 64, cfg.rgb_out), nn.ReLU(True))
+        self.depth_linear = nn.Sequential(nn.Flatten(), nn.Linear((cc + 64) * fs * fs, cfg.depth_out), nn.ReLU(True))
+        self.rgb_kv = nn.Conv1d(2048 + 64, cfg.vis_in, 1)
+        self.depth_kv = nn.Conv1d(cc + 64, cfg.vis_in, 1)
+        self.image_cm_encoder = Visual_Ling_Attn(N=cfg.vla_layers, vis_in_features=cfg.vis_in, ins_in_features=cfg.ins_in, d_model=cfg.d_model,
+                                                 h=cfg.vla_heads, d_ff=cfg.d_ff, dropout=dropout)
+        self.state_encoder = RNNStateEncoder(cfg.cm_d_model * 2 + cfg.depth_out + cfg.rgb_out, cfg.hidden, 1, cfg.rnn_type)
+        self.progress_monitor = nn.Linear(cfg.hidden, 1)
+        self.linear = nn.Linear(cfg.hidden, cfg.num_actions)
+        nn.init.kaiming_normal_(self.progress_monitor.weight, nonlinearity="tanh")     # _init_layers, :166-168
+        nn.init.constant_(self.progress_monitor.bias, 0)
+
+    @property
+    def output_size(self):
+        return self.cfg.hidden
+
+    @property
+    def num_recurrent_layers(self):
+        return self.state_encoder.num_recurrent_layers
+
+    def load_reference_state_dict(self, sd):
+        """Load a reference Seq2Seq_HighLevel_CMA state dict (tensors or arrays): the keys of the two frozen trunks and of BERT are dropped,
+        everything else is strict -- a missing, unexpected or misshapen key raises"""
+        kept = {k: torch.as_tensor(v) for k, v in sd.items() if not k.startswith(HCM_HIGH_FROZEN_PREFIXES)}
+        return self.load_state_dict(kept, strict=True)
+
+    def _instruction_stream(self, observations, rows):
+        stream = observations.get("instruction_features")
+        if stream is None:
+            if self.embedder is None or "instruction" not in observations:
+                raise ValueError("HighLevel trains from the frozen BERT's output: observations['instruction_features'] (rows or 1, L, "
+                                 f"{self.cfg.ins_in}) is missing, and there is no embedder with observations['instruction'] to compute it from")
+            with torch.no_grad():                                              # :192-195
+                stream = self.embedder(observations["instruction"].long())
+        if stream.dim() != 3 or stream.shape[0] not in (1, rows) or stream.shape[2] != self.cfg.ins_in:
+            raise ValueError(f"HighLevel takes instruction_features ({rows} or 1, L, {self.cfg.ins_in}), got {tuple(stream.shape)}")
+        return stream.detach().expand(rows, stream.shape[1], stream.shape[2])  # :190
+
+    def _visual(self, name, feat, enc, fc, kv, pooled, ablated, rows, C0, I, like):
+        """One modality: (tokens (rows, I, vis_in) = the 1x1 convolution of [feature | spatial embedding], transposed as the cross-modal encoder
+        takes it; input of the state encoder (rows, out)).  Ablated: zeros for the whole embedding, so the tokens are the bias alone."""
+        if ablated:
+            return kv.bias.expand(rows, I, -1), torch.relu(fc.bias).expand(rows, -1)
+        feat = _model_slot(feat, 0)
+        s = int(round(I ** 0.5))
+        if feat is None:
+            raise ValueError(f"HighLevel trains from cached trunk features: observations['{name}_features'] is missing; HCMEngine.encode_features "
+                             "returns it from the frames")
+        if feat.dim() != 4 or tuple(feat.shape) != (rows, C0, s, s):
+            raise ValueError(f"HighLevel takes {name}_features ({rows}, {C0}, {s}, {s}) as HCMEngine.encode_features returns them, got {tuple(feat.shape)}")
+        x = feat.flatten(2)
+        cm, e = enc.tail()
+        w = kv.weight[:, :, 0]
+        tail = torch.addmm(kv.bias, e, w[:, C0:].t())                          # (I, vis_in): the same for every row
+        tokens = torch.matmul(x.transpose(1, 2), w[:, :C0].t()) + tail
+        if pooled:
+            x_in = torch.addmm(torch.nn.functional.linear(cm.mean(1), fc.weight[:, C0:], fc.bias), x.mean(2), fc.weight[:, :C0].t())
+        else:
+            x_in = torch.addmm(torch.nn.functional.linear(cm.reshape(-1), fc.weight[:, C0 * I:], fc.bias), x.flatten(1), fc.weight[:, :C0 * I].t())
+        return tokens, torch.relu(x_in)
+
+    def _encode(self, batch, taps=None):
+        """forward up to the state encoder: (its output (rows, hidden), the new packed state)"""
+        observations, rnn_hidden_states, prev_actions, masks = batch
+        cfg = self.cfg
+        masks = masks.reshape(masks.shape[0], -1)[:, 0]                        # :208
+        rows = masks.shape[0]
+        embedded = self._instruction_stream(observations, rows)
+        cc, I_d = self.depth_shape
+        rgb_tok, rgb_in = self._visual("rgb", observations.get("rgb_features"), self.rgb_encoder, self.rgb_linear[2], self.rgb_kv, True,
+                                       cfg.ablate_rgb, rows, 2048, 16, embedded)
+        dep_tok, dep_in = self._visual("depth", observations.get("depth_features"), self.depth_encoder, self.depth_linear[1], self.depth_kv, False,
+                                       cfg.ablate_depth, rows, cc, I_d, embedded)
+        ins_rgb = self.image_cm_encoder(embedded, rgb_tok, None, None).mean(1)      # :200, :209
+        ins_dep = self.image_cm_encoder(embedded, dep_tok, None, None).mean(1)      # :201, :210
+        x = torch.cat((rgb_in, dep_in, ins_rgb, ins_dep), 1)                   # :215
+        if taps is not None:
+            taps.update(rgb_kv=rgb_tok, depth_kv=dep_tok, rnn_in=x)
+        return self.state_encoder(x, rnn_hidden_states, masks)                 # :219
+
+    def forward(self, batch, taps=None):
+        x, hidden = self._encode(batch, taps)
+        return self.linear(x), hidden
+
+    def update_loss(self, batch, oracle_subtask):
+        """The forward and the criterion of the high-level half of `_update_agent` (hierarchical_trainer.py:505-511): the model up to the state
+        encoder, then subtask_ce with oracle_subtask as the collate function carries it ((rows, 1) float, converted on the device).
+        -> (result (8,), rnn_hidden_states); result[0] is the trainer's high-level loss."""
+        x, hidden = self._encode(batch)
+        if oracle_subtask.numel() != x.shape[0]:
+            raise ValueError(f"update_loss takes oracle_subtask ({x.shape[0]}, 1), got {tuple(oracle_subtask.shape)}")
+        return self._subtask_ce(x, self.linear.weight, self.linear.bias, oracle_subtask.to(x.device), self.cfg.num_sub_tasks)[0], hidden
+
+
+class LowLevel(nn.Module):
+    """The reference's Seq2Seq_LowLevel (models/seq2seq_lowlevel.py:21-162) as a trainable model from cached trunk features: the reference's
+    parameters, state-dict keys and shapes outside the two frozen trunks (robo_vln_amd.synth.low_level_spec lists them), and its forward signature.
+    Takes a robo_vln_amd.config.HCMConfig.
+
+    forward((observations, rnn_hidden_states, prev_actions, masks, discrete_actions)) -> (output, stop_out, rnn_hidden_states) as :116-162, with
+    observations["rgb_features"] (rows, 2048, 1, 1) and ["depth_features"] (rows, C, s, s) -- the low entries of HCMEngine.encode_features' pairs;
+    a pair is accepted and its entry 1 taken; an ablated modality needs no key -- and discrete_actions (rows,) the sub-task of every row,
+    num_sub_tasks on the padded ones.  rgb_encoder.fc and depth_encoder.visual_fc.1 with their ReLUs are torch, as in train.Seq2SeqNet;
+    sub_task_embedding has padding_idx = num_sub_tasks (the reference writes 4, its num_sub_tasks): that row is zero at construction and gets
+    no gradient; the cat is the reference's [depth | rgb | sub_task]; the state encoder is train.RNNStateEncoder.  progress_monitor holds
+    parameters only (the trainer clears AuxLosses and adds no aux loss).
+
+    update_loss(batch, corrected_actions, oracle_stop) -> (result (8,), rnn_hidden_states) is the model and the criterion of the trainer's
+    low-level step through flat_heads_loss without the monitor; result[0] + result[1] is the loss.
+
+    The SimpleCNN encoders are trunks that train with the model: there is nothing to cache, and they are refused."""
+
+    _flat_heads = staticmethod(flat_heads_loss)
+
+    def __init__(self, cfg):
+        super().__init__()
+        cfg.validate()
+        _refuse_simple_cnn("LowLevel", cfg)
+        self.cfg = cfg
+        fs, cc = cfg.depth_final_spatial(), cfg.depth_compress_channels()
+        self.depth_shape = (cc, fs)
+        self.depth_encoder = _FlatDepthEncoder(cc * fs * fs, cfg.depth_out)
+        self.rgb_encoder = _FlatRgbEncoder(cfg.rgb_out)
+        self.sub_task_embedding = nn.Embedding(cfg.num_sub_tasks + 1, 32, padding_idx=cfg.num_sub_tasks)
+        self.state_encoder = RNNStateEncoder(cfg.depth_out + cfg.rgb_out + 32, cfg.hidden, 1, cfg.rnn_type)
+        self.progress_monitor = nn.Linear(cfg.hidden, 1)
+        nn.init.kaiming_normal_(self.progress_monitor.weight, nonlinearity="tanh")     # _init_layers, :112-114
+        nn.init.constant_(self.progress_monitor.bias, 0)
+        self.linear = nn.Linear(cfg.hidden, cfg.lo_actions)
+        self.stop_linear = nn.Linear(cfg.hidden, 1)
+
+    @property
+    def output_size(self):
+        return self.cfg.hidden
+
+    @property
+    def num_recurrent_layers(self):
+        return self.state_encoder.num_recurrent_layers
+
+    def load_reference_state_dict(self, sd):
+        """Load a reference Seq2Seq_LowLevel state dict (tensors or arrays): the keys of the two frozen trunks are dropped, everything else is
+        strict -- a missing, unexpected or misshapen key raises"""
+        kept = {k: torch.as_tensor(v) for k, v in sd.items() if not k.startswith(HCM_LOW_FROZEN_PREFIXES)}
+        return self.load_state_dict(kept, strict=True)
+
+    def _visual(self, name, feat, fc, ablated, rows, shape, like):
+        """One modality's embedding relu(fc(flatten(feature))) (rows, out) from the trunk feature; ablated: times 0 (:132-135), and exact zeros
+        without the key"""
+        feat = _model_slot(feat, 1)
+        if feat is None:
+            if ablated:
+                return like.new_zeros(rows, fc.out_features)
+            raise ValueError(f"LowLevel trains from cached trunk features: observations['{name}_features'] is missing; HCMEngine.encode_features "
+                             "returns it from the frames")
+        if tuple(feat.shape) != (rows, *shape):
+            raise ValueError(f"LowLevel takes {name}_features {(rows, *shape)} as HCMEngine.encode_features returns them, got {tuple(feat.shape)}")
+        y = torch.relu(fc(feat.flatten(1)))                                    # Flatten in NCHW order
+        return y * 0 if ablated else y
+
+    def _encode(self, batch):
+        """forward up to the state encoder: (its output (rows, hidden), the new packed state)"""
+        observations, rnn_hidden_states, prev_actions, masks, discrete_actions = batch
+        cfg = self.cfg
+        masks = masks.reshape(masks.shape[0], -1)[:, 0]                        # :145
+        rows = masks.shape[0]
+        if discrete_actions.numel() != rows or discrete_actions.dtype.is_floating_point:
+            raise ValueError(f"LowLevel takes discrete_actions ({rows},) as an integer tensor, got {discrete_actions.dtype} {tuple(discrete_actions.shape)}")
+        cc, fs = self.depth_shape
+        depth = self._visual("depth", observations.get("depth_features"), self.depth_encoder.visual_fc[1], cfg.ablate_depth, rows, (cc, fs, fs),
+                             rnn_hidden_states)
+        rgb = self._visual("rgb", observations.get("rgb_features"), self.rgb_encoder.fc, cfg.ablate_rgb, rows, (2048, 1, 1), rnn_hidden_states)
+        sub_task = self.sub_task_embedding(discrete_actions.reshape(-1).long())    # :141
+        x = torch.cat([depth, rgb, sub_task], 1)                               # :143
+        return self.state_encoder(x, rnn_hidden_states, masks)                 # :147
+
+    def forward(self, batch):
+        x, hidden = self._encode(batch)
+        return self.linear(x), self.stop_linear(x), hidden
+
+    def update_loss(self, batch, corrected_actions, oracle_stop):
+        """The forward and the criterion of the low-level half of `_update_agent` (hierarchical_trainer.py:539-553): the model up to the state
+        encoder, then flat_heads_loss without the monitor.  -> (result (8,), rnn_hidden_states); result[0] + result[1] is the trainer's loss."""
+        x, hidden = self._encode(batch)
+        return _heads_loss(self, x, corrected_actions, oracle_stop, None), hidden
+
+
+def hier_update(high, low, opt_high, opt_low, observations, prev_actions, not_done_masks, corrected_actions, oracle_stop, hi_hidden, lo_hidden):
+    """The reference's `_update_agent` (hierarchical_trainer.py:492-560) for train.HighLevel / train.LowLevel, in its order: zero both optimizers,
+    detach both carried states (repackage_hidden), the high-level loss with its backward and step, then the low-level model teacher-forced with
+    oracle - 1 -- num_sub_tasks where the label is 0 or out of range, formed by torch.where on the device -- with loss = result[0] + result[1],
+    backward and step.  observations["vln_oracle_action_sensor"] is the label tensor as the collate function carries it, (rows, 1) float; it is
+    converted on the device and `observations` is left as it was (the reference deletes keys from it).  Both models run on one device (the
+    reference moves the low-level model's inputs to a second one).
+
+    Returns (result_high, result_low, hi_hidden, lo_hidden), all detached and on the device: result_high (8,) as subtask_ce writes it, result_low
+    (8,) as flat_heads_loss does, where the reference returns four host numbers: nothing is read back and nothing synchronises."""
+    opt_high.zero_grad()
+    opt_low.zero_grad()
+    hi_hidden, lo_hidden = hi_hidden.detach(), lo_hidden.detach()
+    if "vln_oracle_action_sensor" not in observations:
+        raise ValueError("observations['vln_oracle_action_sensor'] is missing: the oracle sub-task of every row, (rows, 1)")
+    oracle = observations["vln_oracle_action_sensor"]
+    result_high, hi_hidden = high.update_loss((observations, hi_hidden, prev_actions, not_done_masks), oracle)
+    result_high[0].backward()
+    opt_high.step()
+
+    n = low.cfg.num_sub_tasks
+    o = oracle.to(lo_hidden.device).reshape(-1).to(torch.int64)
+    discrete_actions = torch.where((o >= 1) & (o <= n), o - 1, torch.full_like(o, n))      # :522-524
+    result_low, lo_hidden = low.update_loss((observations, lo_hidden, prev_actions, not_done_masks, discrete_actions), corrected_actions, oracle_stop)
+    (result_low[0] + result_low[1]).backward()
+    opt_low.step()
+    return result_high.detach(), result_low.detach(), hi_hidden.detach(), lo_hidden.detach()
