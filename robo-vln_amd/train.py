@@ -1028,18 +1028,26 @@ def _heads_loss(model, x, corrected_actions, oracle_stop, progress):
                              labels[0], labels[1], progress)[0]
 
 
-class _CancelledBias(torch.autograd.Function):
-    """y unchanged; `bias` -- a key projection's bias, which cancels in the softmax and takes no part in the forward -- receives a gradient of
-    exact zeros, not None, so that an optimizer treats it as the reference's does"""
+class _ZeroGrad(torch.autograd.Function):
+    """y unchanged; `param` -- a parameter that takes no part in the forward here but has an exact zero gradient in the reference: a key
+    projection's bias, which cancels in the softmax, or a weight the reference multiplies by an ablated, all-zero embedding -- receives a
+    gradient of exact zeros, not None, so that an optimizer treats it as the reference's does"""
 
     @staticmethod
-    def forward(ctx, y, bias):
-        ctx.save_for_backward(bias)
+    def forward(ctx, y, param):
+        ctx.save_for_backward(param)
         return y.view_as(y)
 
     @staticmethod
     def backward(ctx, g):
         return g, torch.zeros_like(ctx.saved_tensors[0])
+
+
+def _zero_grads(y, *params):
+    """_ZeroGrad for every tensor of `params`"""
+    for p in params:
+        y = _ZeroGrad.apply(y, p)
+    return y
 
 
 class _SpatialEncoder(nn.Module):
@@ -1131,7 +1139,8 @@ class CMANet(nn.Module):
         visual FC takes the feature and the embedding as two operands: rgb_linear pools over the positions first (AdaptiveAvgPool1d(1)),
         depth_linear flattens in NCHW order.  Ablated: zeros for the whole embedding, the spatial tail included (cma.py:238-241)."""
         if ablated:
-            return like.new_zeros(rows, C0, I), like.new_zeros(I, 64), torch.relu(fc.bias).expand(rows, -1)
+            return (like.new_zeros(rows, C0, I), like.new_zeros(I, 64),
+                    _zero_grads(torch.relu(fc.bias).expand(rows, -1), fc.weight, enc.spatial_embeddings.weight))
         s = int(round(I ** 0.5))
         if feat is None:
             raise ValueError(f"CMANet trains from cached trunk features: observations['{name}_features'] is missing; CMAEngine.encode_features "
@@ -1178,7 +1187,7 @@ class CMANet(nn.Module):
         state, h1 = self.state_encoder(torch.cat([rgb_in, dep_in], 1), rnn_hidden_states[:R], masks)
 
         text = self._attend(self.state_q(state), self.text_k.weight[:, :, 0], ins, None, True, TOKEN_MAJOR)
-        text = _CancelledBias.apply(text, self.text_k.bias)
+        text = _ZeroGrad.apply(text, self.text_k.bias)
         text_q = self.text_q(text)
         att = []
         for x, e, kv, ablated in ((rgb_x, rgb_e, self.rgb_kv, cfg.ablate_rgb), (dep_x, dep_e, self.depth_kv, cfg.ablate_depth)):
@@ -1270,7 +1279,7 @@ class Seq2SeqNet(nn.Module):
         exact zeros without the key"""
         if feat is None:
             if ablated:
-                return like.new_zeros(rows, fc.out_features)
+                return _zero_grads(like.new_zeros(rows, fc.out_features), fc.weight, fc.bias)
             raise ValueError(f"Seq2SeqNet trains from cached trunk features: observations['{name}_features'] is missing; S2SEngine.encode_features "
                              "returns it from the frames")
         if tuple(feat.shape) != (rows, *shape):
@@ -1521,7 +1530,8 @@ class HighLevel(nn.Module):
         """One modality: (tokens (rows, I, vis_in) = the 1x1 convolution of [feature | spatial embedding], transposed as the cross-modal encoder
         takes it; input of the state encoder (rows, out)).  Ablated: zeros for the whole embedding, so the tokens are the bias alone."""
         if ablated:
-            return kv.bias.expand(rows, I, -1), torch.relu(fc.bias).expand(rows, -1)
+            return (_zero_grads(kv.bias.expand(rows, I, -1), kv.weight),
+                    _zero_grads(torch.relu(fc.bias).expand(rows, -1), fc.weight, enc.spatial_embeddings.weight))
         feat = _model_slot(feat, 0)
         s = int(round(I ** 0.5))
         if feat is None:
@@ -1630,7 +1640,7 @@ class LowLevel(nn.Module):
         feat = _model_slot(feat, 1)
         if feat is None:
             if ablated:
-                return like.new_zeros(rows, fc.out_features)
+                return _zero_grads(like.new_zeros(rows, fc.out_features), fc.weight, fc.bias)
             raise ValueError(f"LowLevel trains from cached trunk features: observations['{name}_features'] is missing; HCMEngine.encode_features "
                              "returns it from the frames")
         if tuple(feat.shape) != (rows, *shape):
