@@ -879,6 +879,19 @@ int hcm_op_subtask_ce_bwd(const float* d_result, const float* x, const float* w,
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);
 int hcm_op_feat_export(const void* y, int dtype, float* x, int rows, int C, int S, int ld, float scale, void* stream);
 
+/* The depth trunk's run kernels alone: `nblocks` identity bottlenecks (conv1x1 -> GroupNorm(16) -> ReLU -> conv3x3 pad 1 -> GroupNorm -> ReLU ->
+ * conv1x1 -> GroupNorm -> + block input -> ReLU; habitat's GroupNorm ResNet-50 as used at resnet_encoders.py:27-62) in ONE launch, a workgroup per
+ * (sample, trunk).  side 32: 128 / 32 channels, side 16: 256 / 64 (csrc/depth_blk.hip, 1..4 blocks); side 8: 512 / 128 (csrc/igemm.hip
+ * depth_l3_kernel, 1..6 blocks); any other side is HCM_ERR_ARG.  x, y [B][side*side][ld] in `dtype` (HCM_F16 / HCM_BF16), trunk g at channels
+ * [g*C, +C), ld a multiple of 8 and >= groups*C; columns beyond groups*C are neither read nor written.
+ *   w    host array of 3*nblocks device pointers, w1 w2 w3 per block: [groups][CM][C], [groups][CM][9*CM] (k = tap*CM + ci), [groups][C][CM]
+ *   gn   host array of 6*nblocks device pointers, gamma1 beta1 gamma2 beta2 gamma3 beta3 per block: [groups*channels] floats
+ *   eps  host array of 3*nblocks floats
+ * x == y: sides 32 / 16 with one block only (a run reads block 0's input from x and every later one from y: refused otherwise); side 8 with any
+ * block count (a workgroup reads its whole slice of x before it writes one element of y).  Every refusal is HCM_ERR_ARG without a launch. */
+int hcm_op_depth_run(const void* x, void* y, const void* const* w, const float* const* gn, const float* eps, int dtype, int B, int side,
+                     int groups, int nblocks, int ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

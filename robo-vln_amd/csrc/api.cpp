@@ -2093,4 +2093,32 @@ int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, 
     return op_rc(launch_maxpool3x3s2(x, y, op_dt(dtype), B, H, W, C, Ho, Wo, (hipStream_t)stream));
 }
 
+int hcm_op_depth_run(const void* x, void* y, const void* const* w, const float* const* gn, const float* eps, int dtype, int B, int side,
+                     int groups, int nblocks, int ld, void* stream) {
+    if (!x || !y || !w || !gn || !eps || (dtype != HCM_F16 && dtype != HCM_BF16)) return HCM_ERR_ARG;
+    // the run descriptor of either kernel from the pointer tables (its arrays hold `cap` blocks)
+    auto fill = [&](auto& q, int cap) {
+        if (nblocks < 1 || nblocks > cap) return false;
+        q.x = x; q.y = y; q.ld = ld; q.B = B; q.groups = groups; q.nblocks = nblocks;
+        for (int r = 0; r < nblocks; ++r) {
+            for (int i = 0; i < 3; ++i) if (!w[3 * r + i]) return false;
+            for (int i = 0; i < 6; ++i) if (!gn[6 * r + i]) return false;
+            q.w1[r] = w[3 * r]; q.w2[r] = w[3 * r + 1]; q.w3[r] = w[3 * r + 2];
+            q.g1[r] = gn[6 * r]; q.b1[r] = gn[6 * r + 1]; q.g2[r] = gn[6 * r + 2]; q.b2[r] = gn[6 * r + 3]; q.g3[r] = gn[6 * r + 4]; q.b3[r] = gn[6 * r + 5];
+            q.eps1[r] = eps[3 * r]; q.eps2[r] = eps[3 * r + 1]; q.eps3[r] = eps[3 * r + 2];
+        }
+        return true;
+    };
+    if (side == 8) {
+        DepthL3 q;
+        if (!fill(q, 6)) return HCM_ERR_ARG;
+        return op_rc(launch_depth_l3(q, op_dt(dtype), (hipStream_t)stream));
+    }
+    if (side != 32 && side != 16) return HCM_ERR_ARG;
+    DepthBlk q;
+    q.side = side; q.C = side == 32 ? 128 : 256; q.CM = q.C / 4;
+    if (!fill(q, 4)) return HCM_ERR_ARG;
+    return op_rc(launch_depth_blk(q, op_dt(dtype), (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -4,12 +4,14 @@ against the oracle's frame forward, the round trip frames -> encode_features -> 
 mixed frames / features, the precedence of a feature over a frame, a range-folded RGB trunk, and the refusals.
 
 Engines: bert_layers = 2, vla_layers = 2, L = 12, 128-pixel frames, plus one at depth 192 (3 x 3 map: odd S, 228 channels padded to 256 inside) and
-one at RGB 160 x 224 (a 5 x 7 map: the (4,4) pool in front of the export is not the identity); rows 1 and 3, (T, N) = (4, 2) for the sequence and
+one at RGB 160 x 224 (a 5 x 7 map: the (4,4) pool in front of the export is not the identity), one at depth 256 in the 16-bit modes (the
+benchmark's frames: the identity blocks of the depth trunk's layer1-3 run in depth_blk_kernel / depth_l3_kernel); rows 1 and 3, (T, N) = (4, 2) for the sequence and
 validation calls.  One engine per (kind, variant, precision) for the whole module.
 
 Bars: max-abs error over max |reference|, 1e-3 in fp32 mode and 1e-2 in the 16-bit modes (tests/test_parity_gpu.py's output tolerances).  The
 round trips are torch.equal: the fold is a power of two and f32 holds every fp16 / bf16 value, so ingest restores the stored bits."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -25,7 +27,8 @@ pytestmark = pytest.mark.gpu
 TOL = {"fp32": 1e-3, "fp16": 1e-2, "bf16": 1e-2}
 SEED = 5
 T, N = 4, 2
-VARIANTS = {"base": dict(rgb_hw=128, depth_hw=128), "d192": dict(rgb_hw=128, depth_hw=192), "r160": dict(rgb_hw=160, rgb_w=224, depth_hw=128)}
+VARIANTS = {"base": dict(rgb_hw=128, depth_hw=128), "d192": dict(rgb_hw=128, depth_hw=192), "r160": dict(rgb_hw=160, rgb_w=224, depth_hw=128),
+            "d256": dict(rgb_hw=128, depth_hw=256)}      # the benchmark's depth frames: layer1-3's identity blocks run in the depth run kernels
 
 
 def hcm_cfg(variant="base"):
@@ -167,6 +170,33 @@ def test_encode_features_matches_the_oracle_trunks_hcm(variant, rows, engines):
         er, ed = rel_err(feats["rgb_features"][slot], r), rel_err(feats["depth_features"][slot], d)
         print(f"encode_features [{variant}, rows {rows}, model {slot}]: rgb {er:.2e} depth {ed:.2e} (<= {TOL['fp32']:.0e})")
         assert er <= TOL["fp32"] and ed <= TOL["fp32"]
+
+
+@functools.lru_cache(maxsize=None)
+def _d256_depth_ref(rows, slot):
+    """the oracle's depth trunk of model `slot` on the d256 observations, once for both precisions"""
+    return features_ref.trunk_features(hcm_cfg("d256"), weights("hcm", "d256")[slot], observations("hcm", rows, "d256"), spatial=slot == 0)[1]
+
+
+@pytest.mark.parametrize("rows", [1, 3])
+@pytest.mark.parametrize("precision", ["fp16", "bf16"])
+def test_encode_features_matches_the_oracle_depth_trunk_through_the_run_kernels(precision, rows, engines):
+    """256-pixel depth frames in the 16-bit modes, taps off: layer1 / layer2's identity blocks run in depth_blk_kernel and layer3's five in
+    depth_l3_kernel (forward.cpp: fill_run, the range-folded eps, the slot hand-over) -- the path no tap comparison and no fp32 run takes.
+    Bound: the file's 16-bit contract.  Measured 6.7e-3 .. 7.6e-3 (both modes store the depth trunk in fp16); the launch-per-conv form of the
+    same engine (development build, HCM_NO_DEPTH_BLK=1 HCM_NO_DEPTH_L3=1) 7.8e-3 .. 9.5e-3: profiles/depth_runs_parity.md."""
+    eng = engines("hcm", precision, "d256")
+    cfg = hcm_cfg("d256")
+    obs = observations("hcm", rows, "d256")
+    feats = eng.encode_features(cuda(obs))
+    s = cfg.depth_final_spatial()
+    assert tuple(feats["depth_features"][0].shape) == tuple(feats["depth_features"][1].shape) == (rows, cfg.depth_compress_channels(), s, s)
+    for slot in range(2):
+        d = _d256_depth_ref(rows, slot)
+        ed = rel_err(feats["depth_features"][slot], d)
+        print(f"encode_features [d256, {precision}, rows {rows}, model {slot}]: depth {ed:.2e} (<= {TOL[precision]:.0e})")
+        assert ed <= TOL[precision]
+    assert eng.nonfinite_steps() == 0
 
 
 @pytest.mark.parametrize("kind", ["cma", "s2s"])
