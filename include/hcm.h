@@ -892,6 +892,84 @@ int hcm_op_feat_export(const void* y, int dtype, float* x, int rows, int C, int 
 int hcm_op_depth_run(const void* x, void* y, const void* const* w, const float* const* gn, const float* eps, int dtype, int B, int side,
                      int groups, int nblocks, int ld, void* stream);
 
+/* ---- The step's small kernels alone (csrc/elementwise.hip), one entry per kernel family.  None allocates, copies to the host or synchronises;
+ * all run on `stream`.  Every refusal is HCM_ERR_ARG without a launch.  `ld*` are row strides in ELEMENTS; columns between the logical width and
+ * the stride are neither read nor written unless stated.
+ *
+ * hcm_op_heads: the small linear heads on a hidden state h (hidden,) f32, a wave per output row, lanes strided by 64 over hidden:
+ *   out0[b*ld0 + r] = w0[r] . h + b0[r]  (r < r0),  out1 likewise,  out2[b*ld2 + r] = tanh(w2[r] . h + b2[r]);  w* are [r*][hidden] f32.
+ *   A head with r* == 0 is absent.  pred (optional, hcm_op_rnn_cell only): pred[b] = torch.argmax(out0 row) -- the first maximal index, a NaN
+ *   counts as the maximum and the first NaN wins -- and emb_out[b*emb_ld + j] = emb[min(pred[b], emb_rows - 1)*emb_dim + j], j < emb_dim.
+ *   pred needs 1 <= r0 <= 64 (the kernel keeps the logits in 64 words of LDS), out0, emb, emb_out and emb_rows >= 1. */
+typedef struct hcm_op_heads {
+    const float* w0; const float* b0; float* out0; int32_t r0, ld0;
+    const float* w1; const float* b1; float* out1; int32_t r1, ld1;
+    const float* w2; const float* b2; float* out2; int32_t r2, ld2;
+    int64_t* pred; const float* emb; float* emb_out; int32_t emb_rows, emb_dim, emb_ld;
+} hcm_op_heads;
+
+/* One recurrent step behind the gate products (RNNStateEncoder.single_forward, state_encoder.py:72-81), as the engines' rnn_finish launches it:
+ *   xh (optional): xh[b*ld_xh + col0 + j] = h_in[0][b][j] * mask[b]  (the masked state the recurrent product reads), written first;
+ *   HCM_LSTM: gates [B][4*hidden] (i,f,g,o) = x W_ih^T + b_ih + (h*mask) W_hh^T + b_hh, gh NULL; c = h_in[1]*mask;
+ *             c' = sig(f) c + sig(i) tanh(g), h' = sig(o) tanh(c'); h_out (2,B,hidden) = (h', c').  h_in[0] is not read.
+ *   HCM_GRU:  gates = gi, gh [B][3*hidden] (r,z,n) with their biases; h = h_in[0]*mask; r = sig(gi_r + gh_r), z = sig(gi_z + gh_z),
+ *             n = tanh(gi_n + r gh_n), h' = (1 - z) n + z h; h_out (1,B,hidden).
+ *   mask [B] is multiplied in, whatever its value; h_out may alias h_in.  heads (optional) act on h'.
+ *   bad (optional): *bad += 1 per SAMPLE whose gate pre-activations are not all finite. */
+int hcm_op_rnn_cell(const float* gates, const float* gh, const float* h_in, const float* mask, float* h_out, float* xh, int ld_xh, int col0,
+                    const hcm_op_heads* heads, unsigned* bad, int B, int hidden, int rnn_type, void* stream);
+/* The heads over `rows` hidden states hs [rows][hidden]: bit-identical to hcm_op_rnn_cell's head outputs for the same h'.  A `pred` is refused. */
+int hcm_op_heads_rows(const float* hs, const hcm_op_heads* heads, int rows, int hidden, void* stream);
+/* One time step t of the packed instruction encoder (nn.LSTM / nn.GRU over pack_padded_sequence): sample b is active iff t < lengths[b].
+ *   pre [B*L][G*hidden] = x_t W_ih^T + biases of the input side (LSTM: b_ih + b_hh), gh [B][G*hidden] = h W_hh^T (GRU: + b_hh); h, c [B][hidden]
+ *   are updated in place (c NULL for GRU); out[(b*L + t)*ld_out + col0 + j] = h' where active.  An inactive sample keeps h and c and emits
+ *   exact zeros. */
+int hcm_op_instr_cell(const float* pre, const float* gh, float* h, float* c, const int32_t* lengths, float* out, int t, int B, int L, int hidden,
+                      int ld_out, int col0, int rnn_type, void* stream);
+/* CMANet._attn (cma.py:201-209), the inference kernel: one query per sample over S positions, f32.
+ *   logits[s] = q[b] . k[b][s] (D terms); minus 1e8 where s >= lengths[b] (lengths NULL: nothing masked); p = softmax(logits * scale);
+ *   out[b*ldo + c] = sum_s p[s] v[(b*S + s)*ldv + c], c < Dv.  q [B][ldq], k [B][S][ldk], v [B][S][ldv]; k and v may interleave in one
+ *   buffer (ldk = ldv = D + Dv, v = k + D).  1 <= S <= 8192; lengths[b] >= 1 is the caller's contract (the reference cannot pack an empty row). */
+int hcm_op_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* lengths, float* out, int ldo, int B,
+                  int S, int D, int Dv, float scale, void* stream);
+/* F.adaptive_avg_pool2d over NHWC x [B][H][W][ldx] -> y [B][OH][OW][ldy], channels [0, C): window [floor(i*H/OH), ceil((i+1)*H/OH)), the sum in
+ * row-major window order times 1 / count.  C, ldx, ldy multiples of the 16-byte chunk (4 f32 / 8 16-bit) and x, y aligned to it: a channel
+ * offset base pointer picks one half of a hi|lo pair (ldx = 2C). */
+int hcm_op_adaptive_avgpool(const void* x, void* y, int dtype, int B, int H, int W, int C, int OH, int OW, int ldx, int ldy, void* stream);
+/* AdaptiveAvgPool1d(1) over tokens: y[b*ldy + c] = mean over the first n_b rows of x [B][S][ldx], c < C; n_b = S, or with lens (device, [B])
+ * clamp(lens[b], 1, S): a length below 1 averages one row, one beyond S all S.  y is f32 when out_f32, else `dtype`. */
+int hcm_op_mean_rows(const void* x, void* y, int dtype, int B, int S, int C, int ldx, int ldy, int out_f32, const int32_t* lens, void* stream);
+/* F.avg_pool2d(x, 2) of the f32 depth frame x [B][H][W] -> y [B][H/2][W/2] in `dtype`: ((a + b) + (c + d)) * 0.25.  padded: the 16-bit types
+ * only, y [B][H/2 + 6][W/2 + 8] with a zero border of 3 left / top, 5 right, 3 bottom and the same interior bits.  W even (padded: W % 4 == 0). */
+int hcm_op_avgpool2(const float* x, void* y, int dtype, int B, int H, int W, int padded, void* stream);
+/* BertEmbeddings: y[b][l] = LayerNorm(word[id] + pos[l] + type0) * gamma + beta, tables f32, y [B*L][D] in `dtype`; ids (B, L) as HCM_I64,
+ * HCM_I32 or HCM_F32 (truncated) -- the same bits for the same values.  An id below 0 reads row 0, one >= vocab row vocab - 1.
+ * D a multiple of 64, at most 1024. */
+int hcm_op_bert_embed(const void* ids, int ids_dtype, const float* word, const float* pos, const float* type0, const float* gamma,
+                      const float* beta, void* y, int dtype, int B, int L, int D, int vocab, float eps, void* stream);
+/* InstructionEncoder's front end (instruction_encoder.py:70-92): x[(b*L + t)*ldx + j] = table[id][j] for j < E and exact 0 for E <= j < ldx
+ * (ALL ldx columns are written); lengths[b] = the count of non-zero ids of row b (a zero in the middle is not counted, nothing else is
+ * skipped).  ids as for hcm_op_bert_embed, the same clamp to [0, vocab - 1] for the lookup. */
+int hcm_op_instr_embed(const void* ids, int ids_dtype, const float* table, float* x, int32_t* lengths, int B, int L, int E, int ldx, int vocab,
+                       void* stream);
+/* LayerNorm of f32 rows x [rows][D] (two-pass variance), D = 256 / 512 / 768, `dtype` HCM_F16 / HCM_BF16: y16 [rows][D] and EXACTLY ONE of
+ * y32 [rows][D] (the same value unrounded) and stats [rows][2] = (mean, rstd).  Both or neither is refused. */
+int hcm_op_layernorm_f32in(const float* x, const float* gamma, const float* beta, void* y16, float* y32, float* stats, int dtype, int rows,
+                           int D, float eps, void* stream);
+/* The calibration range check over x [rows][ld] in `dtype`, columns [0, cols): slot[0] = max(slot[0], bits of the largest finite |x|),
+ * slot[1] += the count of NaN / +-inf elements.  The slot only grows. */
+int hcm_op_absmax(const void* x, int dtype, int rows, int cols, int ld, unsigned* slot, void* stream);
+/* pred[b] = torch.argmax(logits[b*ld .. + n)): first maximal index; a NaN counts as the maximum and the first NaN wins. */
+int hcm_op_argmax(const float* logits, int64_t* pred, int B, int n, int ld, void* stream);
+/* y[b*ld + col0 + j] = emb[clamp(idx[b], 0, nrows - 1)*D + j], j < D. */
+int hcm_op_embed_rows(const float* emb, const int64_t* idx, float* y, int B, int D, int ld, int col0, int nrows, void* stream);
+/* subtask[r] = oracle[r] - 1 for 1 <= oracle[r] <= num_sub_tasks, else num_sub_tasks (hierarchical_trainer.py:597-599). */
+int hcm_op_val_subtask(const int64_t* oracle, int64_t* subtask, int rows, int num_sub_tasks, void* stream);
+/* y[(b*S + s)*ldy + c] = tab[s*C + c] rounded to `dtype`, c < C. */
+int hcm_op_fill_cols(const float* tab, void* y, int dtype, int B, int S, int C, int ldy, void* stream);
+/* dst[r*ld_dst + j] = src[(n_src == 1 ? 0 : r)*ld_src + j], r < rows, j < cols; n_src == 1 or n_src >= rows. */
+int hcm_op_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,12 @@ class HcmFeaturesStruct(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("rgb_dtype", C.c_int32), ("depth", C.c_void_p), ("rgb_feat", C.c_void_p * 2), ("depth_feat", C.c_void_p * 2)]
 
 
+class HcmOpHeadsStruct(C.Structure):
+    """hcm_op_heads (include/hcm.h): up to three small heads on a hidden state, the optional fused argmax + embedding row"""
+    _fields_ = [f for i in range(3) for f in ((f"w{i}", C.c_void_p), (f"b{i}", C.c_void_p), (f"out{i}", C.c_void_p), (f"r{i}", C.c_int32), (f"ld{i}", C.c_int32))] \
+        + [("pred", C.c_void_p), ("emb", C.c_void_p), ("emb_out", C.c_void_p), ("emb_rows", C.c_int32), ("emb_dim", C.c_int32), ("emb_ld", C.c_int32)]
+
+
 EXPORTS = {
     "hcm_encode_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(HcmFeaturesStruct), C.c_void_p]),
     "hcm_encode_features_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(HcmFeaturesStruct), C.c_int, C.c_void_p]),
@@ -165,6 +171,22 @@ EXPORTS = {
     "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
     "hcm_op_depth_run": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "hcm_op_rnn_cell": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.POINTER(HcmOpHeadsStruct), C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "hcm_op_heads_rows": (C.c_int, [C.c_void_p, C.POINTER(HcmOpHeadsStruct), C.c_int, C.c_int, C.c_void_p]),
+    "hcm_op_instr_cell": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
+    "hcm_op_attn1q": (C.c_int, [C.c_void_p, C.c_int] * 3 + [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "hcm_op_adaptive_avgpool": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 9 + [C.c_void_p]),
+    "hcm_op_mean_rows": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p] * 2),
+    "hcm_op_avgpool2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "hcm_op_bert_embed": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "hcm_op_instr_embed": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "hcm_op_layernorm_f32in": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+    "hcm_op_absmax": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2),
+    "hcm_op_argmax": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
+    "hcm_op_embed_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "hcm_op_val_subtask": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p]),
+    "hcm_op_fill_cols": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "hcm_op_copy_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
 }
 
 _lib = None

@@ -2121,4 +2121,141 @@ int hcm_op_depth_run(const void* x, void* y, const void* const* w, const float* 
     return op_rc(launch_depth_blk(q, op_dt(dtype), (hipStream_t)stream));
 }
 
+// ------------------------------------------------------------------ the step's small kernels (csrc/elementwise.hip; include/hcm.h has the layouts)
+static bool op_dt_known(int dtype) { return dtype == HCM_F32 || dtype == HCM_F16 || dtype == HCM_BF16; }
+static bool op_ids_dt(int d, int* out) {
+    *out = d == HCM_I64 ? DT_I64 : d == HCM_I32 ? DT_I32 : d == HCM_F32 ? DT_F32 : -1;
+    return *out >= 0;
+}
+static bool op_aligned(const void* p, size_t a) { return (uintptr_t)p % a == 0; }
+// hcm_op_heads -> Heads; false on a head without its pointers, a stride below its rows, or a `pred` heads_eval cannot serve
+static bool op_heads(const hcm_op_heads* in, bool allow_pred, Heads* hd) {
+    if (!in) return true;
+    if (in->r0 < 0 || in->r1 < 0 || in->r2 < 0) return false;
+    if (in->r0 && (!in->w0 || !in->b0 || !in->out0 || in->ld0 < in->r0)) return false;
+    if (in->r1 && (!in->w1 || !in->b1 || !in->out1 || in->ld1 < in->r1)) return false;
+    if (in->r2 && (!in->w2 || !in->b2 || !in->out2 || in->ld2 < in->r2)) return false;
+    if (in->pred) {
+        if (!allow_pred || in->r0 < 1 || in->r0 > 64 || !in->emb || !in->emb_out || in->emb_rows < 1 || in->emb_dim < 0 || in->emb_ld < in->emb_dim)
+            return false;
+    }
+    hd->w0 = in->w0; hd->b0 = in->b0; hd->out0 = in->out0; hd->r0 = in->r0; hd->ld0 = in->ld0;
+    hd->w1 = in->w1; hd->b1 = in->b1; hd->out1 = in->out1; hd->r1 = in->r1; hd->ld1 = in->ld1;
+    hd->w2 = in->w2; hd->b2 = in->b2; hd->out2 = in->out2; hd->r2 = in->r2; hd->ld2 = in->ld2;
+    hd->pred = in->pred; hd->emb = in->emb; hd->emb_out = in->emb_out; hd->emb_rows = in->emb_rows; hd->emb_dim = in->emb_dim; hd->emb_ld = in->emb_ld;
+    return true;
+}
+// the cells and heads_rows keep a hidden state in dynamic LDS
+static bool op_hidden_ok(int hidden) { return hidden >= 1 && hidden <= 8192; }
+
+int hcm_op_rnn_cell(const float* gates, const float* gh, const float* h_in, const float* mask, float* h_out, float* xh, int ld_xh, int col0,
+                    const hcm_op_heads* heads, unsigned* bad, int B, int hidden, int rnn_type, void* stream) {
+    if (!gates || !h_in || !mask || !h_out || B < 1 || !op_hidden_ok(hidden)) return HCM_ERR_ARG;
+    if (rnn_type != HCM_LSTM && rnn_type != HCM_GRU) return HCM_ERR_ARG;
+    if ((gh != nullptr) != (rnn_type == HCM_GRU)) return HCM_ERR_ARG;
+    if (xh && (col0 < 0 || ld_xh < col0 + hidden)) return HCM_ERR_ARG;
+    Heads hd;
+    if (!op_heads(heads, true, &hd)) return HCM_ERR_ARG;
+    hd.bad = bad;
+    if (xh) {
+        const int rc = op_rc(launch_rnn_prep(h_in, mask, xh, B, hidden, ld_xh, col0, (hipStream_t)stream));
+        if (rc != HCM_OK) return rc;
+    }
+    if (rnn_type == HCM_LSTM) return op_rc(launch_lstm_cell(gates, h_in, mask, h_out, B, hidden, hd, (hipStream_t)stream));
+    return op_rc(launch_gru_cell(gates, gh, h_in, mask, h_out, B, hidden, hd, (hipStream_t)stream));
+}
+
+int hcm_op_heads_rows(const float* hs, const hcm_op_heads* heads, int rows, int hidden, void* stream) {
+    Heads hd;
+    if (!hs || !heads || rows < 1 || !op_hidden_ok(hidden) || !op_heads(heads, false, &hd)) return HCM_ERR_ARG;
+    return op_rc(launch_heads_rows(hs, rows, hidden, hd, (hipStream_t)stream));
+}
+
+int hcm_op_instr_cell(const float* pre, const float* gh, float* h, float* c, const int32_t* lengths, float* out, int t, int B, int L, int hidden,
+                      int ld_out, int col0, int rnn_type, void* stream) {
+    if (!pre || !gh || !h || !lengths || !out || B < 1 || L < 1 || t < 0 || t >= L || hidden < 1 || col0 < 0 || ld_out < col0 + hidden)
+        return HCM_ERR_ARG;
+    if (rnn_type != HCM_LSTM && rnn_type != HCM_GRU) return HCM_ERR_ARG;
+    if ((c == nullptr) != (rnn_type == HCM_GRU)) return HCM_ERR_ARG;
+    if (rnn_type == HCM_GRU) return op_rc(launch_instr_gru_cell(pre, gh, h, lengths, out, t, B, L, hidden, ld_out, col0, (hipStream_t)stream));
+    return op_rc(launch_instr_lstm_cell(pre, gh, h, c, lengths, out, t, B, L, hidden, ld_out, col0, (hipStream_t)stream));
+}
+
+int hcm_op_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* lengths, float* out, int ldo, int B,
+                  int S, int D, int Dv, float scale, void* stream) {
+    if (!q || !k || !v || !out || B < 1 || S < 1 || S > 8192 || D < 1 || Dv < 1 || ldq < D || ldk < D || ldv < Dv || ldo < Dv) return HCM_ERR_ARG;
+    return op_rc(launch_attn1q(q, ldq, k, ldk, v, ldv, lengths, out, ldo, B, S, D, Dv, scale, (hipStream_t)stream));
+}
+
+int hcm_op_adaptive_avgpool(const void* x, void* y, int dtype, int B, int H, int W, int C, int OH, int OW, int ldx, int ldy, void* stream) {
+    if (!x || !y || !op_dt_known(dtype) || B < 1 || H < 1 || W < 1 || C < 1 || OH < 1 || OW < 1 || ldx < C || ldy < C) return HCM_ERR_ARG;
+    if (!op_aligned(x, 16) || !op_aligned(y, 16)) return HCM_ERR_ARG;     // 16-byte chunks; C, ldx, ldy % chunk: the launcher's check
+    return op_rc(launch_adaptive_avgpool(x, y, op_dt(dtype), B, H, W, C, OH, OW, ldy, (hipStream_t)stream, ldx));
+}
+
+int hcm_op_mean_rows(const void* x, void* y, int dtype, int B, int S, int C, int ldx, int ldy, int out_f32, const int32_t* lens, void* stream) {
+    if (!x || !y || !op_dt_known(dtype) || B < 1 || S < 1 || C < 1 || ldx < C || ldy < C) return HCM_ERR_ARG;
+    return op_rc(launch_mean_rows(x, y, op_dt(dtype), B, S, C, ldx, ldy, out_f32 ? 1 : 0, (hipStream_t)stream, lens));
+}
+
+int hcm_op_avgpool2(const float* x, void* y, int dtype, int B, int H, int W, int padded, void* stream) {
+    if (!x || !y || !op_dt_known(dtype) || B < 1 || H < 2 || W < 2 || (W & 1) || !op_aligned(x, 8)) return HCM_ERR_ARG;     // float2 loads
+    if (padded) return op_rc(launch_avgpool2_f32_padded(x, y, op_dt(dtype), B, H, W, (hipStream_t)stream));
+    return op_rc(launch_avgpool2_f32(x, y, op_dt(dtype), B, H, W, (hipStream_t)stream));
+}
+
+int hcm_op_bert_embed(const void* ids, int ids_dtype, const float* word, const float* pos, const float* type0, const float* gamma,
+                      const float* beta, void* y, int dtype, int B, int L, int D, int vocab, float eps, void* stream) {
+    int idt;
+    if (!ids || !word || !pos || !type0 || !gamma || !beta || !y || !op_dt_known(dtype) || !op_ids_dt(ids_dtype, &idt) || B < 1 || L < 1 || vocab < 1)
+        return HCM_ERR_ARG;
+    return op_rc(launch_bert_embed(ids, idt, word, pos, type0, gamma, beta, y, op_dt(dtype), B, L, D, vocab, eps, (hipStream_t)stream));
+}
+
+int hcm_op_instr_embed(const void* ids, int ids_dtype, const float* table, float* x, int32_t* lengths, int B, int L, int E, int ldx, int vocab,
+                       void* stream) {
+    int idt;
+    if (!ids || !table || !x || !lengths || !op_ids_dt(ids_dtype, &idt) || B < 1 || L < 1 || E < 1 || ldx < E || vocab < 1) return HCM_ERR_ARG;
+    return op_rc(launch_instr_embed(ids, idt, table, x, lengths, B, L, E, ldx, vocab, (hipStream_t)stream));
+}
+
+int hcm_op_layernorm_f32in(const float* x, const float* gamma, const float* beta, void* y16, float* y32, float* stats, int dtype, int rows,
+                           int D, float eps, void* stream) {
+    if (!x || !gamma || !beta || !y16 || rows < 1 || (y32 != nullptr) == (stats != nullptr)) return HCM_ERR_ARG;
+    if (dtype != HCM_F16 && dtype != HCM_BF16) return HCM_ERR_ARG;
+    if (!op_aligned(x, 16) || !op_aligned(gamma, 16) || !op_aligned(beta, 16) || !op_aligned(y16, 8) || !op_aligned(y32, 16) || !op_aligned(stats, 8))
+        return HCM_ERR_ARG;
+    return op_rc(launch_layernorm_f32in(x, gamma, beta, y16, y32, op_dt(dtype), rows, D, eps, (hipStream_t)stream, stats));
+}
+
+int hcm_op_absmax(const void* x, int dtype, int rows, int cols, int ld, unsigned* slot, void* stream) {
+    if (!x || !slot || !op_dt_known(dtype) || rows < 1 || cols < 1 || ld < cols) return HCM_ERR_ARG;
+    return op_rc(launch_absmax(x, op_dt(dtype), rows, cols, ld, slot, (hipStream_t)stream));
+}
+
+int hcm_op_argmax(const float* logits, int64_t* pred, int B, int n, int ld, void* stream) {
+    if (!logits || !pred || B < 1 || n < 1 || ld < n) return HCM_ERR_ARG;
+    return op_rc(launch_argmax(logits, pred, B, n, ld, (hipStream_t)stream));
+}
+
+int hcm_op_embed_rows(const float* emb, const int64_t* idx, float* y, int B, int D, int ld, int col0, int nrows, void* stream) {
+    if (!emb || !idx || !y || B < 1 || D < 1 || col0 < 0 || ld < col0 + D || nrows < 1) return HCM_ERR_ARG;
+    return op_rc(launch_embed_rows(emb, idx, y, B, D, ld, col0, nrows, (hipStream_t)stream));
+}
+
+int hcm_op_val_subtask(const int64_t* oracle, int64_t* subtask, int rows, int num_sub_tasks, void* stream) {
+    if (!oracle || !subtask || rows < 1 || num_sub_tasks < 0) return HCM_ERR_ARG;
+    return op_rc(launch_val_subtask(oracle, subtask, rows, num_sub_tasks, (hipStream_t)stream));
+}
+
+int hcm_op_fill_cols(const float* tab, void* y, int dtype, int B, int S, int C, int ldy, void* stream) {
+    if (!tab || !y || !op_dt_known(dtype) || B < 1 || S < 1 || C < 1 || ldy < C) return HCM_ERR_ARG;
+    return op_rc(launch_fill_cols(tab, y, op_dt(dtype), B, S, C, ldy, (hipStream_t)stream));
+}
+
+int hcm_op_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, void* stream) {
+    if (!src || !dst || cols < 1 || ld_src < cols || ld_dst < cols) return HCM_ERR_ARG;
+    return op_rc(launch_copy_rows(src, ld_src, n_src, dst, ld_dst, rows, cols, (hipStream_t)stream));
+}
+
 }  // extern "C"

@@ -943,6 +943,34 @@ hipError_t launch_layernorm(const void* x, const void* res, const float* gamma, 
     return hipGetLastError();
 }
 
+// Rows whose mean lies far from zero (|mean| > 4 standard deviations): a mean of that size held in ONE float32 is off by up to half a float32 ulp of it
+// however it is summed, that error enters every x - mean, and an output near zero then misses its 16-bit value by many storage ulps (74 in fp16 at
+// 100 standard deviations).  The corrected two-pass form: corr = mean of the residuals x - mean (the part of the mean the float32 lost), the outputs
+// use (x - mean) - corr and the variance is retaken over them.  For every other row corr = 0 and rstd is the plain one, so (x - mean) - 0 keeps the
+// bits the kernels had without this step (the "bf16" mode's streams have |mean| well below one standard deviation).  The row's 32 lanes take the
+// same side: mean and sq are the reduced values.
+template <int CPL, int D>
+__device__ __forceinline__ void ln_f32in_offset_fix(const float (&v)[CPL][4], float mean, float sq, float eps, float& corr, float& rstd) {
+    float rs = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rs += v[i][j] - mean;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
+    const float c = rs * (1.0f / D);
+    float sq2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const float d = (v[i][j] - mean) - c; sq2 += d * d; }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) sq2 += __shfl_xor(sq2, o, 64);
+    const bool far = mean * mean > 16.0f * (sq * (1.0f / D));
+    corr = far ? c : 0.f;
+    rstd = far ? rsqrtf(sq2 * (1.0f / D) + eps) : rsqrtf(sq * (1.0f / D) + eps);
+}
+
 // LayerNorm of an f32 row with two outputs (the bf16 BERT keeps its residual stream in f32: forward.cpp bert()): y16 = the next GEMM's
 // 16-bit operand, y32 = the stream itself.  32 lanes per row, float4 chunks.
 template <typename T, int D>
@@ -971,13 +999,14 @@ __global__ __launch_bounds__(256) void layernorm_f32in_kernel(const float* __res
         for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; sq += d * d; }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    const float rstd = rsqrtf(sq * (1.0f / D) + eps);
+    float corr, rstd;
+    ln_f32in_offset_fix<CPL, D>(v, mean, sq, eps, corr, rstd);
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
         const int c = (i * 32 + sub) * 4;
         const float4 g4 = *reinterpret_cast<const float4*>(gamma + c), b4 = *reinterpret_cast<const float4*>(beta + c);
-        float o[4] = {(v[i][0] - mean) * rstd * g4.x + b4.x, (v[i][1] - mean) * rstd * g4.y + b4.y,
-                      (v[i][2] - mean) * rstd * g4.z + b4.z, (v[i][3] - mean) * rstd * g4.w + b4.w};
+        float o[4] = {((v[i][0] - mean) - corr) * rstd * g4.x + b4.x, ((v[i][1] - mean) - corr) * rstd * g4.y + b4.y,
+                      ((v[i][2] - mean) - corr) * rstd * g4.z + b4.z, ((v[i][3] - mean) - corr) * rstd * g4.w + b4.w};
         st_chunk(y32 + (size_t)row * D + c, o);
         T o4[4];
 #pragma unroll
@@ -1014,21 +1043,23 @@ __global__ __launch_bounds__(256) void layernorm_f32in_stats_kernel(const float*
         for (int j = 0; j < 4; ++j) { const float d = v[i][j] - mean; sq += d * d; }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    const float rstd = rsqrtf(sq * (1.0f / D) + eps);
-    if (sub == 0) *reinterpret_cast<float2*>(stats + 2 * (size_t)row) = make_float2(mean, rstd);
+    float corr, rstd;
+    ln_f32in_offset_fix<CPL, D>(v, mean, sq, eps, corr, rstd);
+    if (sub == 0) *reinterpret_cast<float2*>(stats + 2 * (size_t)row) = make_float2(corr != 0.f ? mean + corr : mean, rstd);
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
         const int c = (i * 32 + sub) * 4;
         const float4 g4 = *reinterpret_cast<const float4*>(gamma + c), b4 = *reinterpret_cast<const float4*>(beta + c);
         T o4[4];
-        Tr<T>::st(&o4[0], (v[i][0] - mean) * rstd * g4.x + b4.x); Tr<T>::st(&o4[1], (v[i][1] - mean) * rstd * g4.y + b4.y);
-        Tr<T>::st(&o4[2], (v[i][2] - mean) * rstd * g4.z + b4.z); Tr<T>::st(&o4[3], (v[i][3] - mean) * rstd * g4.w + b4.w);
+        Tr<T>::st(&o4[0], ((v[i][0] - mean) - corr) * rstd * g4.x + b4.x); Tr<T>::st(&o4[1], ((v[i][1] - mean) - corr) * rstd * g4.y + b4.y);
+        Tr<T>::st(&o4[2], ((v[i][2] - mean) - corr) * rstd * g4.z + b4.z); Tr<T>::st(&o4[3], ((v[i][3] - mean) - corr) * rstd * g4.w + b4.w);
         *reinterpret_cast<uint2*>(y16 + (size_t)row * D + c) = *reinterpret_cast<const uint2*>(o4);
     }
 }
 hipError_t launch_layernorm_f32in(const float* x, const float* gamma, const float* beta, void* y16, float* y32, int dt, int rows, int D, float eps,
                                   hipStream_t s, float* stats) {
     if (dt != DT_BF16 && dt != DT_F16) return hipErrorInvalidValue;
+    if (!stats && !y32) return hipErrorInvalidValue;      // the plain form stores its f32 output unconditionally
     if (stats) {                                   // the statistics form: no f32 output
         if (y32) return hipErrorInvalidValue;
         constexpr int rpb2 = 8;
@@ -1135,8 +1166,8 @@ __device__ __forceinline__ void heads_eval(const float* hs, int Hd, const Heads&
         if (threadIdx.x == 0) {
             int best = 0;
             float bv = lg[0];
-            for (int j = 1; j < hd.r0; ++j)
-                if (lg[j] > bv) { bv = lg[j]; best = j; }
+            for (int j = 1; j < hd.r0; ++j)                     // torch.argmax: a NaN counts as the maximum, the first one wins (as val_loss_kernel)
+                if (lg[j] > bv || (lg[j] != lg[j] && bv == bv)) { bv = lg[j]; best = j; }
             hd.pred[b] = best;
             best_s = best < hd.emb_rows ? best : hd.emb_rows - 1;
         }
@@ -1144,6 +1175,11 @@ __device__ __forceinline__ void heads_eval(const float* hs, int Hd, const Heads&
         const float* e = hd.emb + (size_t)best_s * hd.emb_dim;
         for (int j = threadIdx.x; j < hd.emb_dim; j += blockDim.x) hd.emb_out[(size_t)b * hd.emb_ld + j] = e[j];
     }
+}
+
+// heads_eval keeps the first head's logits of the fused argmax in lg[64] and reads lg[0 .. r0): a fused `pred` needs 1 <= r0 <= 64 and a table to clamp into
+static bool heads_pred_ok(const Heads& hd) {
+    return !hd.pred || (hd.r0 >= 1 && hd.r0 <= 64 && hd.out0 && hd.emb && hd.emb_out && hd.emb_rows >= 1 && hd.emb_dim >= 0);
 }
 
 __global__ void lstm_cell_kernel(const float* __restrict__ gates, const float* __restrict__ h_in, const float* __restrict__ mask,
@@ -1169,6 +1205,7 @@ __global__ void lstm_cell_kernel(const float* __restrict__ gates, const float* _
 }
 hipError_t launch_lstm_cell(const float* gates, const float* h_in, const float* mask, float* h_out, int B, int Hd,
                             const Heads& heads, hipStream_t s) {
+    if (!heads_pred_ok(heads)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lstm_cell_kernel, dim3(B), dim3(256), Hd * sizeof(float), s, gates, h_in, mask, h_out, B, Hd, heads);
     return hipGetLastError();
 }
@@ -1197,6 +1234,7 @@ __global__ void gru_cell_kernel(const float* __restrict__ gi, const float* __res
 }
 hipError_t launch_gru_cell(const float* gi, const float* gh, const float* h_in, const float* mask, float* h_out, int B,
                            int Hd, const Heads& heads, hipStream_t s) {
+    if (!heads_pred_ok(heads)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gru_cell_kernel, dim3(B), dim3(256), Hd * sizeof(float), s, gi, gh, h_in, mask, h_out, B, Hd, heads);
     return hipGetLastError();
 }
@@ -1224,7 +1262,7 @@ __global__ void absmax_kernel(const T* __restrict__ x, int rows, int cols, int l
     unsigned bad = 0;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const float v = Tr<T>::ld(x + (e / cols) * (size_t)ld + e % cols);
-        if (!(fabsf(v) <= 3.0e38f)) ++bad; else mx = fmaxf(mx, fabsf(v));
+        if (!isfinite(v)) ++bad; else mx = fmaxf(mx, fabsf(v));          // (a 3.0e38 threshold counted float32's and bf16's largest finite values as overflows)
     }
     mx = wave_max(mx);
     bad += __shfl_xor(bad, 32, 64); bad += __shfl_xor(bad, 16, 64); bad += __shfl_xor(bad, 8, 64);
@@ -1413,15 +1451,15 @@ hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const
     return hipGetLastError();
 }
 
-// torch.argmax(output, dim=1) (hierarchical_trainer.py:1098): first maximal index
+// torch.argmax(output, dim=1) (hierarchical_trainer.py:1098): first maximal index, and a NaN is maximal
 __global__ void argmax_kernel(const float* __restrict__ logits, int64_t* __restrict__ pred, int B, int n, int ld) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const float* p = logits + (size_t)b * ld;
     int best = 0;
     float bv = p[0];
-    for (int j = 1; j < n; ++j)
-        if (p[j] > bv) { bv = p[j]; best = j; }
+    for (int j = 1; j < n; ++j)                                 // a NaN counts as the maximum, the first one wins (as val_loss_kernel)
+        if (p[j] > bv || (p[j] != p[j] && bv == bv)) { bv = p[j]; best = j; }
     pred[b] = best;
 }
 hipError_t launch_argmax(const float* logits, int64_t* pred, int B, int n, int ld, hipStream_t s) {
