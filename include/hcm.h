@@ -35,7 +35,8 @@ enum hcm_status {
 };
 
 enum hcm_dtype { HCM_F32 = 0, HCM_BF16 = 1, HCM_I32 = 2, HCM_I64 = 3, HCM_U8 = 4, HCM_F16 = 5,
-                 HCM_FEATURES = 6 /* as `rgb_dtype` only: the `rgb` argument is a host `const hcm_features*` (below) */ };
+                 HCM_FEATURES = 6 /* as `rgb_dtype` only: the `rgb` argument is a host `const hcm_features*` (below) */,
+                 HCM_INSTR_FEATURES = 7 /* as `ids_dtype` only: the `ids` argument is a host `const hcm_instr_features*` (below) */ };
 enum hcm_model { HCM_HIGH = 0, HCM_LOW = 1, HCM_CMA = 2 /* CMANet flat baseline: hcm_cma_create handles only */,
                  HCM_S2S = 3 /* Seq2SeqNet flat baseline: hcm_s2s_create handles only */ };
 enum hcm_encoder { HCM_ENC_RESNET = 0, HCM_ENC_SIMPLECNN = 1 };
@@ -136,6 +137,35 @@ typedef struct hcm_features {
     const float* rgb_feat[2];
     const float* depth_feat[2];
 } hcm_features;
+
+/* Precomputed instruction stream: the output of the high-level model's BERT, the counterpart of hcm_features for the text side.
+ * Seq2Seq_HighLevel_CMA.forward runs BERT under torch.no_grad() (models/seq2seq_highlevel_cma.py:192-195) on ids that are fixed for an episode
+ * (:189-190), so its last hidden state is a function of the episode's instruction alone: a rollout can compute it once per episode, a validation
+ * epoch once per trajectory (the trainer's collate repeats one instruction over the T steps of a chunk), a trainer once per episode
+ * (robo-vln_amd/train.py reads it as observations["instruction_features"]).
+ * Every HCM entry point that takes `ids, ids_dtype` and runs the high-level model -- hcm_high_forward, hcm_high_forward_seq, hcm_act, hcm_act_ex,
+ * hcm_act_gather, hcm_val_step -- accepts ids_dtype == HCM_INSTR_FEATURES: `ids` is then a HOST pointer to this struct, consumed during the call.
+ *   stream    DEVICE pointer, f32 (rows, L, bert_hidden) contiguous: BERT's last hidden state, as hcm_encode_instruction writes it
+ *   rows      divides the call's row count (B; T*N for the sequence / validation calls): row r of the call reads stream row r % rows.  rows = B: one
+ *             stream per row; 1: one instruction for every row (:189-190); N in a time-major T*N call: row t*N + n takes environment n's stream
+ *   reserved  must be 0
+ * L and `lengths` stay arguments of the call.  The call runs one conversion launch in place of BERT, on the stream that would have carried the
+ * BERT chain, into the buffer BERT fills (the `hi.bert` tap shows it); the instruction side of Visual_Ling_Attn and everything behind it run
+ * unchanged.  With `lengths`, the positions behind a row's length are filled with zeros and the stream is not read there: whatever a cache holds
+ * behind a length (NaN included) cannot reach the result.  A length below 1 zero-fills the whole row.
+ * Bits: a call fed hcm_encode_instruction's output returns the bits of the same call fed the ids, in every precision mode -- the stream holds the
+ * values of BERT's storage type (fp16 / bf16 / f32 per mode), which f32 carries exactly.  ONE condition: BERT's GEMM launches are chosen by the
+ * row count (tile form and staging depend on rows * L, csrc/igemm.hip; the folded-LayerNorm form of big engines is the exception, it is fixed per
+ * engine), and two launch forms agree to round-off only.  The promise therefore holds for a stream ENCODED AT THE CALL'S OWN ROW COUNT AND L
+ * (encode B rows for a B-row call, T*N for a sequence call; its first row / first N rows are then the rows = 1 / rows = N forms); a stream
+ * encoded at another row count is BERT's output just as well, and reproduces the call to the precision mode's round-off.
+ * A stream computed elsewhere (the reference's own BERT) is rounded once to BERT's storage type on the way in.
+ * Refused with a message, never a GPU fault.  HCM_ERR_UNSUPPORTED: a CMANet / Seq2SeqNet handle (their instruction encoders are recurrent, not
+ * BERT), a handle without a high-level model, an ablated instruction.  HCM_ERR_ARG: rows < 1 or not a divisor of the call's rows, reserved != 0,
+ * a NULL stream, HCM_ACT_REUSE_INSTRUCTION beside it (the flag's cache and a handed-over stream contradict each other), hcm_refresh_instruction,
+ * hcm_calibrate (calibration measures BERT's ranges and needs it to run).  The handle stays usable after a refusal.
+ * A captured hcm_act graph is keyed by `stream` and `rows` like by every other argument. */
+typedef struct hcm_instr_features { const float* stream; int32_t rows; int32_t reserved; } hcm_instr_features;
 
 /* Replaces model construction, hierarchical_trainer.py:315-328 (Seq2Seq_HighLevel_CMA.__init__
  * models/seq2seq_highlevel_cma.py:33-141, Seq2Seq_LowLevel.__init__ models/seq2seq_lowlevel.py:32-98).
@@ -318,6 +348,16 @@ int hcm_act_gather(hcm_handle h, const void* rgb, int rgb_dtype, const float* de
 enum hcm_encode_flags { HCM_ENCODE_ACT = 1 };
 int hcm_encode_features(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int rows, const hcm_features* out, void* stream);
 int hcm_encode_features_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, int rows, const hcm_features* out, int flags, void* stream);
+
+/* BERT alone: runs the high-level model's BERT (seq2seq_highlevel_cma.py:192-195) on `rows` <= max_batch instructions -- ids (rows, L) of
+ * ids_dtype HCM_I32 / HCM_I64 / HCM_F32 and lengths (rows,) or NULL, as for hcm_high_forward -- and writes its last hidden state as f32
+ * (rows, L, bert_hidden) to `out` (device), zeros behind each row's length: the tensor hcm_instr_features.stream takes.  The launches are those
+ * of hcm_high_forward at the same (rows, L), the values those of BERT's storage type; in the "bf16" mode that is the bf16 operand the
+ * instruction side of Visual_Ling_Attn reads, not the internal f32 residual stream.  See hcm_instr_features on row counts and bits.
+ * On the caller's stream; no synchronisation, no allocation.  Uses the workspace like every other forward entry point: an
+ * HCM_ACT_REUSE_INSTRUCTION cache is invalidated.  HCM_ERR_UNSUPPORTED: a CMANet / Seq2SeqNet handle, no high-level model;
+ * HCM_ERR_ARG: rows outside [1, max_batch], L outside [1, instr_len], NULL ids or out, ids_dtype HCM_INSTR_FEATURES. */
+int hcm_encode_instruction(hcm_handle h, const void* ids, int ids_dtype, const int32_t* lengths, int rows, int L, float* out, void* stream);
 
 /* fp16 range safety (no reference counterpart: the reference is fp32).  Sub-networks that store fp16 (all four in HCM_F16 mode, the depth
  * trunks in HCM_BF16 mode) have a range that ends at 65504.  hcm_finalize runs one forward on a synthetic batch with range hooks on every GEMM
@@ -878,6 +918,13 @@ int hcm_op_subtask_ce_bwd(const float* d_result, const float* x, const float* w,
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);
 int hcm_op_feat_export(const void* y, int dtype, float* x, int rows, int C, int S, int ld, float scale, void* stream);
+/* csrc/features.hip alone, the two kernels of hcm_instr_features: x f32 (src_rows, L, D) -> y (B, L, D) contiguous in the storage type `dtype`
+ * (HCM_F32 / HCM_F16 / HCM_BF16), output row r from source row r % src_rows; and y (rows, L, D) -> x f32 (rows, L, D).  lens: device (B,) /
+ * (rows,) int32 or NULL; positions l >= lens[r] (clamped to [0, L]) are written as exact +0.0 and never read.  One round-to-nearest-even into
+ * `dtype` on the way in, exact on the way out.  16-byte accesses on both sides when D is a multiple of 8 and both pointers are 16-byte aligned,
+ * scalar ones otherwise.  HCM_ERR_ARG: B / rows, src_rows, L or D < 1, B % src_rows != 0, a NULL x or y, an unknown dtype. */
+int hcm_op_instr_feat_ingest(const float* x, void* y, int dtype, const int32_t* lens, int B, int src_rows, int L, int D, void* stream);
+int hcm_op_instr_feat_export(const void* y, int dtype, float* x, const int32_t* lens, int rows, int L, int D, void* stream);
 
 /* The depth trunk's run kernels alone: `nblocks` identity bottlenecks (conv1x1 -> GroupNorm(16) -> ReLU -> conv3x3 pad 1 -> GroupNorm -> ReLU ->
  * conv1x1 -> GroupNorm -> + block input -> ReLU; habitat's GroupNorm ResNet-50 as used at resnet_encoders.py:27-62) in ONE launch, a workgroup per

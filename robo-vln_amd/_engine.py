@@ -9,8 +9,9 @@ import torch
 from . import _lib
 
 _TORCH_DT = {torch.float32: _lib.HCM_F32, torch.uint8: _lib.HCM_U8, torch.int32: _lib.HCM_I32, torch.int64: _lib.HCM_I64,
-             "hcm_features": _lib.HCM_FEATURES}
+             "hcm_features": _lib.HCM_FEATURES, "hcm_instr_features": _lib.HCM_INSTR_FEATURES}
 FEATURE_KEYS = ("rgb_features", "depth_features")       # the reference's key names (resnet_encoders.py:207-208, :83-84)
+INSTR_KEY = "instruction_features"                      # the frozen BERT stream, under the name train.HighLevel reads it by
 
 
 class _FeatureFrames:
@@ -35,6 +36,31 @@ class _FeatureFrames:
         """what a captured graph of the call is keyed by"""
         st = self.struct
         return (st.rgb, st.depth, st.rgb_feat[0], st.rgb_feat[1], st.depth_feat[0], st.depth_feat[1])
+
+
+class _InstrStream:
+    """Stands where the ids tensor stands in a library call when the observations carry `instruction_features`: data_ptr() is the address of an
+    hcm_instr_features struct (include/hcm.h), `dtype` selects HCM_INSTR_FEATURES in _TORCH_DT and shape is (call rows, L), so the call sites read
+    as they do for ids.  Holds the stream tensor the struct points to."""
+    dtype = "hcm_instr_features"
+
+    def __init__(self, stream, call_rows):
+        self.stream = stream
+        self.shape = (call_rows, stream.shape[1])
+        st = self.struct = _lib.HcmInstrFeaturesStruct()
+        st.stream, st.rows, st.reserved = stream.data_ptr(), stream.shape[0], 0
+
+    def data_ptr(self):
+        return C.addressof(self.struct)
+
+    def pointers(self):
+        """what a captured graph of the call is keyed by"""
+        return (self.struct.stream, self.struct.rows)
+
+    def check_envs(self, rows, N):
+        """a sequence / validation call, once it knows N: the stream holds one row per frame, one for all, or one per environment"""
+        if self.stream.shape[0] not in (1, N, rows):
+            raise ValueError(f"{INSTR_KEY} must hold {rows} rows (one per frame), 1, or {N} (one per environment, time-major), got {self.stream.shape[0]}")
 
 
 class _NoDepth:
@@ -234,6 +260,12 @@ class _EngineBase:
         if r2.shape[0] != rows:
             raise ValueError(f"the frames hold {r2.shape[0]} rows, the features {rows}")
         return (r2 if rgb is not None else None), (d2 if depth is not None else None)
+
+    def _no_instr_stream(self, observations):
+        """the flat engines: their instruction encoder is a recurrent InstructionEncoder behind an embedding (cma.py:50-52, seq2seq.py:45-48), not BERT"""
+        if observations.get(INSTR_KEY) is not None:
+            raise ValueError(f"observations[{INSTR_KEY!r}] is the frozen BERT stream of the hierarchical pair's high-level model (HCMEngine); "
+                             f"{type(self).__name__}'s instruction encoder is recurrent and trained, there is no such stream to take")
 
     def encode_features(self, observations, for_act=False):
         """The trunks alone (hcm_encode_features): observations["rgb"] / ["depth"] -> {"rgb_features": ..., "depth_features": ...} in the

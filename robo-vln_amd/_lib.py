@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(_HERE, "libhcm_dev.so" if os.environ.get("HCM_DEV_LIB", 
 
 HCM_F32, HCM_BF16, HCM_I32, HCM_I64, HCM_U8, HCM_F16 = 0, 1, 2, 3, 4, 5
 HCM_FEATURES = 6            # as rgb_dtype: `rgb` is a host hcm_features* (HcmFeaturesStruct)
+HCM_INSTR_FEATURES = 7      # as ids_dtype: `ids` is a host hcm_instr_features* (HcmInstrFeaturesStruct)
 HCM_HIGH, HCM_LOW, HCM_CMA, HCM_S2S = 0, 1, 2, 3
 HCM_ENC_RESNET, HCM_ENC_SIMPLECNN = 0, 1
 HCM_LSTM, HCM_GRU = 0, 1
@@ -60,6 +61,11 @@ class HcmFeaturesStruct(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("rgb_dtype", C.c_int32), ("depth", C.c_void_p), ("rgb_feat", C.c_void_p * 2), ("depth_feat", C.c_void_p * 2)]
 
 
+class HcmInstrFeaturesStruct(C.Structure):
+    """hcm_instr_features (include/hcm.h): the precomputed BERT stream, f32 (rows, L, bert_hidden) on the device"""
+    _fields_ = [("stream", C.c_void_p), ("rows", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HcmOpHeadsStruct(C.Structure):
     """hcm_op_heads (include/hcm.h): up to three small heads on a hidden state, the optional fused argmax + embedding row"""
     _fields_ = [f for i in range(3) for f in ((f"w{i}", C.c_void_p), (f"b{i}", C.c_void_p), (f"out{i}", C.c_void_p), (f"r{i}", C.c_int32), (f"ld{i}", C.c_int32))] \
@@ -69,6 +75,7 @@ class HcmOpHeadsStruct(C.Structure):
 EXPORTS = {
     "hcm_encode_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(HcmFeaturesStruct), C.c_void_p]),
     "hcm_encode_features_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(HcmFeaturesStruct), C.c_int, C.c_void_p]),
+    "hcm_encode_instruction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hcm_s2s_create": (C.c_int, [C.POINTER(HcmS2sConfigStruct), C.POINTER(C.c_void_p)]),
     "hcm_s2s_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -169,6 +176,8 @@ EXPORTS = {
     "hcm_op_subtask_ce_bwd": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_void_p]),
     "hcm_op_feat_ingest":(C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+    "hcm_op_instr_feat_ingest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_instr_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "hcm_op_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
     "hcm_op_depth_run": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
     "hcm_op_rnn_cell": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.POINTER(HcmOpHeadsStruct), C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),

@@ -50,6 +50,7 @@ class CMAEngine(_FlatEngine):
         rgb, depth, B = self._frames(observations, (0,), lambda r, d: self._frame_check(r, d, lead))      # (or rgb_features / depth_features)
         if rows is not None and B != rows:
             raise ValueError(f"expected {rows} frames (T*N), got {B}")
+        self._no_instr_stream(observations)
         ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
         # cfg.instr_len is the longest padded instruction the workspace is sized for; every call brings its own L
         if ids.dim() != 2 or ids.shape[0] not in (1, B) or not 1 <= ids.shape[1] <= c.instr_len:

@@ -114,7 +114,7 @@ static std::vector<uint64_t> call_key(const FwdCall& c, bool segmented) {
             (uint64_t)c.ld_logits, (uint64_t)c.ld_vel, (uint64_t)c.ld_stop, p(c.stream), p(c.rgb), p(c.depth), p(c.ids), p(c.lens),
             p(c.hi_h_in), p(c.lo_h_in), p(c.hi_h_out), p(c.lo_h_out), p(c.mask), p(c.subtask), p(c.logits), p(c.vel), p(c.stop), p(c.progress),
             p(c.oracle), p(c.corrected), p(c.oracle_stop), p(c.progress_label), p(c.result),
-            p(c.rgb_feat[0]), p(c.rgb_feat[1]), p(c.depth_feat[0]), p(c.depth_feat[1])};
+            p(c.rgb_feat[0]), p(c.rgb_feat[1]), p(c.depth_feat[0]), p(c.depth_feat[1]), p(c.instr_feat), (uint64_t)c.instr_rows};
 }
 
 // hipGraph cache shared by the fused entry points, keyed by call_key().  A key is run eagerly the first time it is seen (that also
@@ -445,6 +445,11 @@ static void dry_run(hcm_ctx* h, int B) {
         FwdCall e;
         e.encode = true; e.rows = B;
         for (bool act : {false, true}) { e.enc_act = act; run_forward(h, e); }
+    }
+    if (h->kind == 0 && h->cfg.build_high) {               // hcm_encode_instruction: BERT alone at B rows (a subset of the step's buffers; sized all the same)
+        FwdCall e;
+        e.encode_instr = true; e.rows = B; e.L = h->cfg.instr_len;
+        run_forward(h, e);
     }
     if (h->kind == 1) {
         run(B, 1);
@@ -795,6 +800,8 @@ int hcm_calibrate(hcm_handle h, const void* rgb, int rgb_dtype, const float* dep
     REQUIRE(rgb_dtype != HCM_FEATURES, HCM_ERR_ARG,
             "hcm_calibrate with HCM_FEATURES: the calibration measures the ranges inside the trunks and needs them to run -- pass the frames (the reference "
             "has no counterpart: resnet_encoders.py:83-86, :207-214 skip the trunk when the feature key is there)");
+    REQUIRE(ids_dtype != HCM_INSTR_FEATURES, HCM_ERR_ARG,
+            "hcm_calibrate with HCM_INSTR_FEATURES: the calibration measures the ranges inside BERT and needs it to run -- pass the token ids");
     REQUIRE(rgb && depth && (ids || !needs_ids), HCM_ERR_ARG, "null pointer");
     REQUIRE(rgb_dt_ok(rgb_dtype) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     if (needs_ids && (rc = check_len(h, L))) return rc;
@@ -855,8 +862,35 @@ static FwdCall frames(const void* rgb, int rgb_dt, const float* depth, const voi
         for (int m = 0; m < 2; ++m) { c.rgb_feat[m] = f->rgb_feat[m]; c.depth_feat[m] = f->depth_feat[m]; }
     } else { c.rgb = rgb; c.rgb_dt = rgb_dt; c.depth = depth; }
     c.ids = ids; c.ids_dt = ids_dt;
+    if (ids_dt == HCM_INSTR_FEATURES && ids) {             // `ids` is a host hcm_instr_features (check_instr judges it): no token ids in this call
+        const hcm_instr_features* f = (const hcm_instr_features*)ids;
+        c.ids = nullptr; c.instr_feat = f->stream; c.instr_rows = f->rows; c.instr_reserved = f->reserved;
+    }
     c.rows = c.Bi = rows; c.L = L; c.stream = (hipStream_t)stream;
     return c;
+}
+// HCM_INSTR_FEATURES and hcm_encode_instruction need a handle whose instruction encoder is BERT, and runs
+static int instr_handle(hcm_ctx* h, const char* what) {
+    REQUIRE(h->kind == 0, HCM_ERR_UNSUPPORTED,
+            std::string(what) + ": the instruction encoder of a CMANet / Seq2SeqNet handle is a recurrent InstructionEncoder, not BERT (cma.py:50-52, "
+            "seq2seq.py:45-48 with is_bert refused): there is no frozen BERT stream to take or to export");
+    REQUIRE(h->cfg.build_high, HCM_ERR_UNSUPPORTED, std::string(what) + ": the handle holds no high-level model, and only that one reads the instruction");
+    REQUIRE(!h->cfg.ablate_instruction, HCM_ERR_UNSUPPORTED, std::string(what) + ": the instruction is ablated and nothing would read the stream");
+    return HCM_OK;
+}
+static bool ids_arg_ok(int d) { return ids_dt_ok(d) || d == HCM_INSTR_FEATURES; }
+// The instruction part of a call, after frames() and after the call's flags are in the descriptor: a no-op for token ids
+static int check_instr(hcm_ctx* h, const FwdCall& c, int ids_dtype_arg) {
+    if (ids_dtype_arg != HCM_INSTR_FEATURES) return HCM_OK;
+    if (const int rc = instr_handle(h, "HCM_INSTR_FEATURES")) return rc;
+    REQUIRE(c.instr_feat, HCM_ERR_ARG, "HCM_INSTR_FEATURES: hcm_instr_features.stream is NULL");
+    REQUIRE(c.instr_reserved == 0, HCM_ERR_ARG, "HCM_INSTR_FEATURES: hcm_instr_features.reserved must be 0");
+    REQUIRE(c.instr_rows >= 1 && c.rows % c.instr_rows == 0, HCM_ERR_ARG,
+            "HCM_INSTR_FEATURES: hcm_instr_features.rows = " + std::to_string(c.instr_rows) + " must be >= 1 and divide the call's " +
+            std::to_string(c.rows) + " rows (B, or T*N of a sequence / validation call)");
+    REQUIRE(!c.reuse_instruction, HCM_ERR_ARG,
+            "HCM_INSTR_FEATURES together with HCM_ACT_REUSE_INSTRUCTION: the flag says `skip the instruction`, the dtype hands one over");
+    return HCM_OK;
 }
 // Which (model, modality) pairs of this handle have a ResNet trunk that runs (no SimpleCNN, not ablated): [slot][0 rgb, 1 depth]; slot 0 = the
 // high-level model or a flat handle's model, slot 1 = the low-level model.  `why` gets the reason a pair takes no feature.
@@ -941,11 +975,13 @@ static int high_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float*
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
     drop_instruction_cache(h);
+    if (ids_dtype == HCM_INSTR_FEATURES && (rc = instr_handle(h, "HCM_INSTR_FEATURES"))) return rc;
     REQUIRE(h->cfg.build_high, HCM_ERR_STATE, "handle holds no high-level model");
     REQUIRE(ids && h_in && mask && logits && h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE(ids_arg_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
     c.do_hi = true; c.T = T; c.lens = lengths;
+    if ((rc = check_instr(h, c, ids_dtype))) return rc;
     if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     c.hi_h_in = h_in; c.mask = mask; c.logits = logits; c.ld_logits = h->cfg.num_actions; c.hi_h_out = h_out;
     return run_eager(h, c);
@@ -993,6 +1029,7 @@ int hcm_low_forward_seq(hcm_handle h, const void* rgb, int rgb_dtype, const floa
 static int cma_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype, int rows, int T, int L,
                        const float* h_in, const float* mask, float* out, float* stop, float* h_out, void* stream) {
     REQUIRE(ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    if (ids_dtype == HCM_INSTR_FEATURES) return instr_handle(h, "HCM_INSTR_FEATURES");
     REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
     c.T = T;
@@ -1035,6 +1072,7 @@ static int s2s_forward(hcm_ctx* h, const void* rgb, int rgb_dtype, const float* 
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(ids && h_in && mask && out && stop && h_out, HCM_ERR_ARG, "null pointer");
+    if (ids_dtype == HCM_INSTR_FEATURES) return instr_handle(h, "HCM_INSTR_FEATURES");
     REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, rows, L, stream);
     c.T = T; c.Bi = B_instr;
@@ -1059,11 +1097,12 @@ int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* dept
                  const float* lo_h_in, const float* masks, float* result, float* hi_h_out, float* lo_h_out, float* logits, float* vel, float* stop,
                  void* stream) {
     REQUIRE(h, HCM_ERR_ARG, "null handle");
+    int rc = HCM_OK;
+    if (ids_dtype == HCM_INSTR_FEATURES && (rc = instr_handle(h, "HCM_INSTR_FEATURES"))) return rc;
     REQUIRE(h->kind == 0, HCM_ERR_STATE, "hcm_val_step needs an HCM handle (hcm_create): the flat baselines have no high-level / low-level pair");
-    int rc = check_seq(h, T, N);
-    if (rc) return rc;
+    if ((rc = check_seq(h, T, N))) return rc;
     REQUIRE(result, HCM_ERR_ARG, "null result");
-    REQUIRE((rgb_dt_ok(rgb_dtype) || rgb_dtype == HCM_FEATURES) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE((rgb_dt_ok(rgb_dtype) || rgb_dtype == HCM_FEATURES) && ids_arg_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     if ((rc = check_fwd(h, T * N))) return rc;
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_val_step needs both models in the handle");
@@ -1072,6 +1111,7 @@ int hcm_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float* dept
     drop_instruction_cache(h);
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, T * N, L, stream);
     c.do_hi = c.do_lo = true; c.T = T; c.lens = lengths;
+    if ((rc = check_instr(h, c, ids_dtype))) return rc;
     if ((rc = check_obs(h, c, depth, rgb_dtype))) return rc;
     c.hi_h_in = hi_h_in; c.lo_h_in = lo_h_in; c.mask = masks; c.hi_h_out = hi_h_out; c.lo_h_out = lo_h_out;
     c.logits = logits; c.ld_logits = h->cfg.num_actions; c.vel = vel; c.ld_vel = h->cfg.lo_actions; c.stop = stop; c.ld_stop = 1;
@@ -1088,6 +1128,7 @@ int hcm_flat_val_step(hcm_handle h, const void* rgb, int rgb_dtype, const float*
     int rc = check_seq(h, T, N);
     if (rc) return rc;
     REQUIRE(result, HCM_ERR_ARG, "null result");
+    if (ids_dtype == HCM_INSTR_FEATURES) return instr_handle(h, "HCM_INSTR_FEATURES");
     REQUIRE((rgb_dt_ok(rgb_dtype) || rgb_dtype == HCM_FEATURES) && ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     const bool monitor = h->kind == 2 && h->s2s_cfg.progress_monitor;
     if (h->kind == 1)
@@ -1140,19 +1181,35 @@ int hcm_encode_features(hcm_handle h, const void* rgb, int rgb_dtype, const floa
     return hcm_encode_features_ex(h, rgb, rgb_dtype, depth, rows, out, 0, stream);
 }
 
+int hcm_encode_instruction(hcm_handle h, const void* ids, int ids_dtype, const int32_t* lengths, int rows, int L, float* out, void* stream) {
+    int rc = check_fwd(h, rows);
+    if (rc) return rc;
+    if ((rc = instr_handle(h, "hcm_encode_instruction"))) return rc;
+    if ((rc = check_len(h, L))) return rc;
+    REQUIRE(ids_dtype != HCM_INSTR_FEATURES, HCM_ERR_ARG, "hcm_encode_instruction reads token ids: ids_dtype must be HCM_I32, HCM_I64 or HCM_F32");
+    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported ids dtype");
+    REQUIRE(ids && out, HCM_ERR_ARG, "null pointer");
+    drop_instruction_cache(h);
+    FwdCall c = frames(nullptr, DT_F32, nullptr, ids, ids_dtype, rows, L, stream);
+    c.lens = lengths; c.encode_instr = true; c.enc_instr = out;
+    return run_eager(h, c);
+}
+
 int hcm_act_ex(hcm_handle h, const void* rgb, int rgb_dtype, const float* depth, const void* ids, int ids_dtype,
                const int32_t* lengths, int B, int L, const float* hi_h_in, const float* lo_h_in, const float* mask, float* record, float* hi_h_out, float* lo_h_out,
                int flags, void* stream) {
     int rc = check_fwd(h, B);
     if (rc) return rc;
     if ((rc = check_len(h, L))) return rc;
+    if (ids_dtype == HCM_INSTR_FEATURES && (rc = instr_handle(h, "HCM_INSTR_FEATURES"))) return rc;
     REQUIRE(h->cfg.build_high && h->cfg.build_low, HCM_ERR_STATE, "hcm_act needs both models in the handle");
     REQUIRE(ids && hi_h_in && lo_h_in && mask && record && hi_h_out && lo_h_out, HCM_ERR_ARG, "null pointer");
-    REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
+    REQUIRE(ids_arg_ok(ids_dtype), HCM_ERR_ARG, "unsupported rgb/ids dtype");
     REQUIRE(h->cfg.num_actions + h->cfg.lo_actions + 1 == 7, HCM_ERR_UNSUPPORTED, "record layout assumes 4 + 2 + 1 outputs");
     FwdCall c = frames(rgb, rgb_dtype, depth, ids, ids_dtype, B, L, stream);
     c.do_hi = c.do_lo = true; c.lens = lengths;
     c.reuse_instruction = (flags & HCM_ACT_REUSE_INSTRUCTION) != 0;
+    if ((rc = check_instr(h, c, ids_dtype))) return rc;
     REQUIRE(!c.reuse_instruction || (h->last_hi_batch == B && h->last_hi_L == L), HCM_ERR_STATE,
             "HCM_ACT_REUSE_INSTRUCTION: the previous call on this handle was not an hcm_act step with this batch size and instruction length");
     c.host_frames = (flags & HCM_ACT_HOST_FRAMES) != 0;
@@ -1180,6 +1237,9 @@ int hcm_refresh_instruction(hcm_handle h, const void* ids, int ids_dtype, const 
     if ((rc = check_len(h, L))) return rc;
     REQUIRE(h->cfg.build_high, HCM_ERR_STATE, "handle holds no high-level model");
     REQUIRE(ids && (env_indices || n == 0) && n >= 0 && n <= B, HCM_ERR_ARG, "bad argument");
+    REQUIRE(ids_dtype != HCM_INSTR_FEATURES, HCM_ERR_ARG,
+            "hcm_refresh_instruction takes token ids: a stream for the listed environments is not built (pass it to hcm_act_ex without "
+            "HCM_ACT_REUSE_INSTRUCTION instead)");
     REQUIRE(ids_dt_ok(ids_dtype), HCM_ERR_ARG, "unsupported ids dtype");
     REQUIRE(h->last_hi_batch == B && h->last_hi_L == L, HCM_ERR_STATE,
             "hcm_refresh_instruction: the previous call on this handle was not an hcm_act step with this batch size and instruction length");
@@ -2086,6 +2146,15 @@ int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int 
 }
 int hcm_op_feat_export(const void* y, int dtype, float* x, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_export(y, op_dt(dtype), x, rows, C, S, ld, scale, (hipStream_t)stream));
+}
+static bool op_feat_dt(int dtype) { return dtype == HCM_F32 || dtype == HCM_F16 || dtype == HCM_BF16; }
+int hcm_op_instr_feat_ingest(const float* x, void* y, int dtype, const int32_t* lens, int B, int src_rows, int L, int D, void* stream) {
+    if (!op_feat_dt(dtype)) return HCM_ERR_ARG;
+    return op_rc(hcm::launch_instr_feat_ingest(x, y, op_dt(dtype), lens, B, src_rows, L, D, (hipStream_t)stream));
+}
+int hcm_op_instr_feat_export(const void* y, int dtype, float* x, const int32_t* lens, int rows, int L, int D, void* stream) {
+    if (!op_feat_dt(dtype)) return HCM_ERR_ARG;
+    return op_rc(hcm::launch_instr_feat_export(y, op_dt(dtype), x, lens, rows, L, D, (hipStream_t)stream));
 }
 
 int hcm_op_maxpool3x3s2(const void* x, void* y, int dtype, int B, int H, int W, int C, void* stream) {

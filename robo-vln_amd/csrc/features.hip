@@ -127,6 +127,96 @@ hipError_t export_t(const void* y, int dt, float* x, int rows, int C, int S, int
     return hipGetLastError();
 }
 
+// ---- the frozen BERT stream at the ABI (hcm_instr_features, include/hcm.h): f32 (src_rows, L, D) <-> the buffer bert() fills, (B, L, D) contiguous in
+// BERT's storage type.  No transpose, so no LDS: a pure conversion stream.  One workgroup owns kIThreads chunks of ONE output row r; its length
+// lens[r] is loaded through an address that depends on blockIdx alone -- uniform over the workgroup, one scalar load, not one load per lane.
+// Positions l >= lens[r] are stored as exact +0.0 and their source is never read: what BERT (or a caller) leaves behind a row's own length is
+// not part of any contract and must not travel through a cache.
+constexpr int kIThreads = 256;
+
+// grid: (B, ceil(L * D / (kIThreads * CH))) in the 16-byte form, (B, ceil(L * D / kIThreads)) in the scalar one.  Output row r reads source row
+// r % src_rows: B rows (own stream each), 1 (one instruction for every row), N (time-major chunk: row t * N + n takes environment n's stream).
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kIThreads) void instr_feat_ingest_kernel(const float* __restrict__ x, T* __restrict__ y, const int* __restrict__ lens,
+                                                                      int src_rows, int L, int D) {
+    const int r = blockIdx.x;
+    const int len = lens ? min(max(lens[r], 0), L) : L;
+    const size_t n = (size_t)L * D, live = (size_t)len * D;
+    const float* xr = x + (size_t)(r % src_rows) * n;
+    T* yr = y + (size_t)r * n;
+    if (VEC) {
+        constexpr int CH = Tr<T>::CH;                         // D % CH == 0: a chunk never straddles two positions
+        const size_t i = ((size_t)blockIdx.y * kIThreads + threadIdx.x) * CH;
+        if (i >= n) return;
+        if constexpr (CH == 4) {
+            *reinterpret_cast<float4*>(yr + i) = i < live ? *reinterpret_cast<const float4*>(xr + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            uint4 o = make_uint4(0u, 0u, 0u, 0u);
+            if (i < live) {
+                const float4 a = *reinterpret_cast<const float4*>(xr + i), b = *reinterpret_cast<const float4*>(xr + i + 4);
+                o = make_uint4((uint32_t)bits16<T>(a.x) | (uint32_t)bits16<T>(a.y) << 16, (uint32_t)bits16<T>(a.z) | (uint32_t)bits16<T>(a.w) << 16,
+                               (uint32_t)bits16<T>(b.x) | (uint32_t)bits16<T>(b.y) << 16, (uint32_t)bits16<T>(b.z) | (uint32_t)bits16<T>(b.w) << 16);
+            }
+            *reinterpret_cast<uint4*>(yr + i) = o;
+        }
+    } else {
+        const size_t i = (size_t)blockIdx.y * kIThreads + threadIdx.x;
+        if (i >= n) return;
+        Tr<T>::st(yr + i, i < live ? xr[i] : 0.f);
+    }
+}
+
+// grid as above over `rows`; y (rows, L, D) in T -> x (rows, L, D) f32
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kIThreads) void instr_feat_export_kernel(const T* __restrict__ y, float* __restrict__ x, const int* __restrict__ lens, int L, int D) {
+    const int r = blockIdx.x;
+    const int len = lens ? min(max(lens[r], 0), L) : L;
+    const size_t n = (size_t)L * D, live = (size_t)len * D;
+    const T* yr = y + (size_t)r * n;
+    float* xr = x + (size_t)r * n;
+    if (VEC) {
+        constexpr int CH = Tr<T>::CH;
+        const size_t i = ((size_t)blockIdx.y * kIThreads + threadIdx.x) * CH;
+        if (i >= n) return;
+        float e[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) e[j] = 0.f;
+        if (i < live) ld_chunk(yr + i, e);
+#pragma unroll
+        for (int j = 0; j < CH; j += 4) *reinterpret_cast<float4*>(xr + i + j) = make_float4(e[j], e[j + 1], e[j + 2], e[j + 3]);
+    } else {
+        const size_t i = (size_t)blockIdx.y * kIThreads + threadIdx.x;
+        if (i >= n) return;
+        xr[i] = i < live ? Tr<T>::ld(yr + i) : 0.f;
+    }
+}
+
+// the 16-byte form: whole chunks per position and both pointers 16-byte aligned (every row then is: L * D is a multiple of the chunk too)
+bool instr_vec_ok(const void* x, const void* y, int dt, int D) {
+    return D % 8 == 0 && D % dt_chunk(dt) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
+}
+dim3 instr_grid(int rows, int L, int D, int per_thread) {
+    const size_t per_block = (size_t)kIThreads * per_thread;
+    return dim3(rows, (unsigned)(((size_t)L * D + per_block - 1) / per_block), 1);
+}
+
+template <typename T>
+hipError_t instr_ingest_t(const float* x, void* y, int dt, const int* lens, int B, int src_rows, int L, int D, hipStream_t s) {
+    if (instr_vec_ok(x, y, dt, D))
+        hipLaunchKernelGGL((instr_feat_ingest_kernel<T, true>), instr_grid(B, L, D, Tr<T>::CH), dim3(kIThreads), 0, s, x, (T*)y, lens, src_rows, L, D);
+    else
+        hipLaunchKernelGGL((instr_feat_ingest_kernel<T, false>), instr_grid(B, L, D, 1), dim3(kIThreads), 0, s, x, (T*)y, lens, src_rows, L, D);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t instr_export_t(const void* y, int dt, float* x, const int* lens, int rows, int L, int D, hipStream_t s) {
+    if (instr_vec_ok(x, y, dt, D))
+        hipLaunchKernelGGL((instr_feat_export_kernel<T, true>), instr_grid(rows, L, D, Tr<T>::CH), dim3(kIThreads), 0, s, (const T*)y, x, lens, L, D);
+    else
+        hipLaunchKernelGGL((instr_feat_export_kernel<T, false>), instr_grid(rows, L, D, 1), dim3(kIThreads), 0, s, (const T*)y, x, lens, L, D);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_feat_ingest(const float* x, void* y, int dt, int rows, int C, int S, int ld, float scale, hipStream_t s) {
@@ -140,6 +230,23 @@ hipError_t launch_feat_export(const void* y, int dt, float* x, int rows, int C, 
     if (dt == DT_F16) return export_t<f16>(y, dt, x, rows, C, S, ld, scale, s);
     if (dt == DT_BF16) return export_t<bf16>(y, dt, x, rows, C, S, ld, scale, s);
     return export_t<float>(y, dt, x, rows, C, S, ld, scale, s);
+}
+
+// (grid.y carries the chunks of one row: L * D up to 65535 * 256 elements in the scalar form)
+static bool instr_shape_ok(int rows, int L, int D) {
+    return rows >= 1 && L >= 1 && D >= 1 && ((size_t)L * D + kIThreads - 1) / kIThreads <= 65535;
+}
+hipError_t launch_instr_feat_ingest(const float* x, void* y, int dt, const int* lens, int B, int src_rows, int L, int D, hipStream_t s) {
+    if (!x || !y || src_rows < 1 || !instr_shape_ok(B, L, D) || B % src_rows != 0) return hipErrorInvalidValue;
+    if (dt == DT_F16) return instr_ingest_t<f16>(x, y, dt, lens, B, src_rows, L, D, s);
+    if (dt == DT_BF16) return instr_ingest_t<bf16>(x, y, dt, lens, B, src_rows, L, D, s);
+    return instr_ingest_t<float>(x, y, dt, lens, B, src_rows, L, D, s);
+}
+hipError_t launch_instr_feat_export(const void* y, int dt, float* x, const int* lens, int rows, int L, int D, hipStream_t s) {
+    if (!x || !y || !instr_shape_ok(rows, L, D)) return hipErrorInvalidValue;
+    if (dt == DT_F16) return instr_export_t<f16>(y, dt, x, lens, rows, L, D, s);
+    if (dt == DT_BF16) return instr_export_t<bf16>(y, dt, x, lens, rows, L, D, s);
+    return instr_export_t<float>(y, dt, x, lens, rows, L, D, s);
 }
 
 }  // namespace hcm

@@ -1237,9 +1237,15 @@ struct Fwd {
     // BERT (:189-195) -> emb
     void hi_bert(const void* ids, int ids_dt, int B, HiBufs& hb) {
         use(ctx->dt_bert);
-        calib_slot = 0;
-        bert(ctx->hi.bert, ids, ids_dt, B, hb.emb, call.lens);
-        calib_slot = -1;
+        if (call.instr_feat) {
+            // hcm_instr_features: BERT is frozen (seq2seq_highlevel_cma.py:192-195) and the caller hands its output over; one conversion launch
+            // fills the buffer bert() would have filled, on the same stream, zeros behind each row's length
+            if (!dry) ck(launch_instr_feat_ingest(call.instr_feat, hb.emb, dt, call.lens, B, call.instr_rows, call.L, ctx->cfg.bert_hidden, s), "instruction stream ingest");
+        } else {
+            calib_slot = 0;
+            bert(ctx->hi.bert, ids, ids_dt, B, hb.emb, call.lens);
+            calib_slot = -1;
+        }
         tap("hi.bert", hb.emb, true, {B, call.L, ctx->cfg.bert_hidden});
         mark("bert.end");
         hi_ins_pre(B, hb);
@@ -1829,6 +1835,15 @@ struct Fwd {
         feat_out((char*)o.p + (size_t)c0 * esz, f0, B, C, o.H * o.W, o.C, 1.f);
         feat_out((char*)o.p + (size_t)c1 * esz, f1, B, C, o.H * o.W, o.C, 1.f);
     }
+    // hcm_encode_instruction: the BERT chain alone, with the launches of hi_bert at the same (B, L), exported as f32 with zeros behind each length
+    void encode_instruction(int B, float* out) {
+        ar.reset();
+        use(ctx->dt_bert);
+        void* emb = alloc_t((size_t)B * ctx->cfg.instr_len * ctx->cfg.bert_hidden);
+        bert(ctx->hi.bert, call.ids, call.ids_dt, B, emb, call.lens);
+        tap("hi.bert", emb, true, {B, call.L, ctx->cfg.bert_hidden});
+        if (!dry) ck(launch_instr_feat_export(emb, dt, out, call.lens, B, call.L, ctx->cfg.bert_hidden, s), "instruction stream export");
+    }
     void encode(int B) {
         ar.reset();
         const bool multi = ctx->concurrent && !ctx->taps_on;
@@ -2037,6 +2052,7 @@ struct Fwd {
 void run_forward(hcm_ctx* ctx, const FwdCall& c) {
     Fwd f(ctx, c);
     if (c.encode) f.encode(c.rows);
+    else if (c.encode_instr) f.encode_instruction(c.rows, c.enc_instr);
     else if (ctx->kind == 1) f.cma_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.lo_h_in, c.mask, c.vel, c.stop, c.lo_h_out);
     else if (ctx->kind == 2) f.s2s_step(c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.Bi, c.lo_h_in, c.mask, c.vel, c.stop, c.progress, c.lo_h_out);
     else f.step(c.do_hi, c.do_lo, c.rgb, c.rgb_dt, c.depth, c.ids, c.ids_dt, c.rows, c.hi_h_in, c.lo_h_in, c.mask, c.subtask, c.logits, c.ld_logits,

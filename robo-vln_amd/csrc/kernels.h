@@ -486,5 +486,11 @@ hipError_t launch_convert(const void* x, int dt_in, void* y, int dt_out, size_t 
 // `scale`, a power of two (the RGB trunk's range fold, or its inverse on the way out): exact in every storage type.  Any rows, C, S >= 1.
 hipError_t launch_feat_ingest(const float* x, void* y, int dt, int rows, int C, int S, int ld, float scale, hipStream_t s);
 hipError_t launch_feat_export(const void* y, int dt, float* x, int rows, int C, int S, int ld, float scale, hipStream_t s);
+// The frozen BERT stream at the ABI (hcm_instr_features): x f32 (src_rows, L, D) -> y (B, L, D) contiguous in storage type dt (HiBufs::emb), output
+// row r from source row r % src_rows (src_rows divides B); and back, y (rows, L, D) -> x f32 (rows, L, D).  lens (device, one entry per OUTPUT row,
+// clamped to [0, L]) or null: positions l >= lens[r] are written as exact +0.0 and not read.  One rounding to dt on the way in (none for f32), the
+// way out is exact.  hipErrorInvalidValue: rows, src_rows, L or D < 1, B % src_rows != 0, a null pointer, L * D beyond 65535 * 256.
+hipError_t launch_instr_feat_ingest(const float* x, void* y, int dt, const int* lens, int B, int src_rows, int L, int D, hipStream_t s);
+hipError_t launch_instr_feat_export(const void* y, int dt, float* x, const int* lens, int rows, int L, int D, hipStream_t s);
 
 }  // namespace hcm

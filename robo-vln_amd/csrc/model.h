@@ -195,6 +195,12 @@ struct FwdCall {
     float* enc_rgb[2] = {nullptr, nullptr};
     float* enc_depth[2] = {nullptr, nullptr};
     const void* ids = nullptr; int ids_dt = DT_I64;
+    // hcm_instr_features: the precomputed BERT stream, f32 (instr_rows, L, bert_hidden), row r of the call from row r % instr_rows; non-null replaces
+    // BERT (ids is then null).  instr_reserved: the struct's reserved word, for the entry point's check
+    const float* instr_feat = nullptr; int instr_rows = 0, instr_reserved = 0;
+    // hcm_encode_instruction: BERT alone on ids (rows, L), exported as f32 (rows, L, bert_hidden) to enc_instr (null = a sizing pass)
+    bool encode_instr = false;
+    float* enc_instr = nullptr;
     const int* lens = nullptr;                // optional per-row instruction lengths (device, [rows]); null = all L
     int rows = 0;                             // frames: B of a step, T * N of a sequence call (time-major)
     int T = 1;                                // time steps packed in the rows; 1 = the per-step call

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import _TORCH_DT, _EngineBase, _FeatureFrames, _np32, _ptr, obs_rows       # noqa: F401  (_np32: importable from here as before)
+from ._engine import INSTR_KEY, _TORCH_DT, _EngineBase, _FeatureFrames, _InstrStream, _np32, _ptr, obs_rows       # noqa: F401  (_np32: importable from here as before)
 from .config import HCMConfig
 
 _SUB_SLOTS = {"depth": 0, "bert": 1, "vla": 2, "rgb": 3}
@@ -239,17 +239,46 @@ class HCMEngine(_EngineBase):
     def _enc_frames(self, observations):
         return self._frame_check(observations["rgb"], observations["depth"])
 
-    def _obs(self, observations, need_ids, host_frames=False, slots=(0, 1)):
-        """slots: the models the call runs (0 high-level, 1 low-level) -- whose rgb_features / depth_features it takes (_EngineBase._frames)"""
+    def _instr_stream(self, t, B, seq):
+        """observations["instruction_features"] of a call of B rows, checked: f32 (B or 1, L, bert_hidden) on the engine's device -- or, in a
+        sequence / validation call (seq), any row count that divides B; the call narrows it to (B, 1 or N) once it knows N (_InstrStream.check_envs)"""
+        c = self.cfg
+        if not self.has_high:
+            raise ValueError(f"{INSTR_KEY}: this engine holds no high-level model, and only that one reads the instruction")
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise ValueError(f"{INSTR_KEY} must be a tensor on the engine's device {self.device} (encode_instruction returns one); a host copy of a cache "
+                             "is brought over with .to(device) by its owner, not silently per call")
+        if t.device != self.device and (t.device.index is not None and self.device.index is not None):
+            raise ValueError(f"{INSTR_KEY} lives on {t.device}, the engine on {self.device}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{INSTR_KEY} must be float32, got {t.dtype}")
+        if t.dim() != 3 or t.shape[2] != c.bert_hidden:
+            raise ValueError(f"{INSTR_KEY} must be (rows, L, {c.bert_hidden}), got {tuple(t.shape)}")
+        if not 1 <= t.shape[1] <= self.max_instr_len:
+            raise ValueError(f"{INSTR_KEY}: L = {t.shape[1]} outside [1, {self.max_instr_len}] (max_instr_len)")
+        rows = t.shape[0]
+        if rows < 1 or B % rows or (not seq and rows not in (1, B)):
+            raise ValueError(f"{INSTR_KEY} must hold {B} rows or 1" + (f", or one row per environment (a divisor of {B})" if seq else "") + f", got {rows}")
+        return t.contiguous()
+
+    def _obs(self, observations, need_ids, host_frames=False, slots=(0, 1), seq=False):
+        """slots: the models the call runs (0 high-level, 1 low-level) -- whose rgb_features / depth_features it takes (_EngineBase._frames).
+        ids comes back as the (B, L) token tensor, or as an _InstrStream when the observations carry `instruction_features`.
+        seq: a sequence / validation call, whose stream may hold one row per environment"""
         rgb, depth, B = self._frames(observations, tuple(s for s in slots if self._has_slot(s)) or slots,
                                      lambda r, d: self._frame_check(r, d, host_frames), host_frames)
         ids = lens = None
         if need_ids:
-            ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
-            if ids.dim() != 2 or ids.shape[0] not in (1, B) or not 1 <= ids.shape[1] <= self.max_instr_len:
-                raise ValueError(f"instruction must be (B or 1, L) with 1 <= L <= {self.max_instr_len} (max_instr_len), got {tuple(ids.shape)}")
-            # instruction.expand(B, L) (seq2seq_highlevel_cma.py:189-190)
-            ids = ids.expand(B, ids.shape[1]).contiguous()
+            if observations.get(INSTR_KEY) is not None:
+                # the frozen BERT stream instead of the ids: given together with `instruction` the feature wins and the ids are not read, as with the
+                # trunk features; `instruction` may be absent
+                ids = _InstrStream(self._instr_stream(observations[INSTR_KEY], B, seq), B)
+            else:
+                ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
+                if ids.dim() != 2 or ids.shape[0] not in (1, B) or not 1 <= ids.shape[1] <= self.max_instr_len:
+                    raise ValueError(f"instruction must be (B or 1, L) with 1 <= L <= {self.max_instr_len} (max_instr_len), got {tuple(ids.shape)}")
+                # instruction.expand(B, L) (seq2seq_highlevel_cma.py:189-190)
+                ids = ids.expand(B, ids.shape[1]).contiguous()
             # extension for batched rollouts (not a reference key): per-environment token counts of a padded ragged batch
             if observations.get("instruction_lengths") is not None:
                 lens = self._dev(observations["instruction_lengths"], (torch.int32,)).reshape(-1)
@@ -307,11 +336,12 @@ class HCMEngine(_EngineBase):
                 self._gstream = torch.cuda.Stream(device=self.device)
             st = self._static
             feat = isinstance(rgb, _FeatureFrames)      # features are read in place: the graph is keyed by the pointers in the struct
-            if st is None or st["B"] != B or st["rgb"].dtype != rgb.dtype or st["ids"].dtype != ids.dtype or st["rgb"].device != rgb.device:
+            instr = isinstance(ids, _InstrStream)       # ... and so is the instruction stream (no static copy: the graph is keyed by its address and rows)
+            if st is None or st["B"] != B or st["rgb"].dtype != rgb.dtype or (not instr and st["ids"].dtype != ids.dtype) or st["rgb"].device != rgb.device:
                 # the static ids buffer holds the longest instruction; a call uses its first B*L elements, so the graph of a new L
                 # differs by its key only, not by the buffer address
                 st = {"B": B, "tick": 0, "rgb": rgb if feat else torch.empty_like(rgb), "depth": depth if feat else torch.empty_like(depth),
-                      "ids": torch.empty(B * self.max_instr_len, device=self.device, dtype=ids.dtype),
+                      "ids": torch.empty(B * self.max_instr_len, device=self.device, dtype=torch.int64 if instr else ids.dtype),
                       "lens": torch.empty(B, device=self.device, dtype=torch.int32),
                       "mask": torch.empty_like(m), "rec": [torch.empty(B, 7, device=self.device) for _ in range(2)],
                       "hh": [torch.zeros_like(hh) for _ in range(2)], "lh": [torch.zeros_like(lh) for _ in range(2)]}
@@ -323,7 +353,8 @@ class HCMEngine(_EngineBase):
             # output buffers) are read in place: the captured graph is keyed by their addresses like by any other argument.
             # Tensors seen for the first time go through the engine's static copies, so that fresh allocations every step
             # do not force a new capture every step.
-            ptrs = (rgb.pointers() if feat else (rgb.data_ptr(), depth.data_ptr())) + (ids.data_ptr(), m.data_ptr(), L, lens.data_ptr() if lens is not None else 0)
+            ptrs = (rgb.pointers() if feat else (rgb.data_ptr(), depth.data_ptr())) + (ids.pointers() if instr else (ids.data_ptr(),)) \
+                + (m.data_ptr(), L, lens.data_ptr() if lens is not None else 0)
             # (a caller that rotates a few buffer sets -- double-buffered staging -- is recognised as well: the last four sets)
             seen = st.setdefault("seen_ptrs", [])
             direct = ptrs in seen and not os.environ.get("HCM_NO_DIRECT_OBS")
@@ -332,7 +363,7 @@ class HCMEngine(_EngineBase):
             seen.append(ptrs)
             del seen[:-4]
             st["hold"] = (rgb, depth, ids, m, lens)        # keep the caller's tensors alive while the graph may read them
-            s_ids = st["ids"][:B * L].view(B, L)
+            s_ids = ids if instr else st["ids"][:B * L].view(B, L)
             g_rgb, g_depth, g_ids, g_m = (rgb, depth, ids, m) if direct else (st["rgb"], st["depth"], s_ids, st["mask"])
             if host_frames or feat:                        # pinned host frames are always read in place (the library stages them); so are features
                 g_rgb, g_depth = rgb, depth
@@ -366,11 +397,13 @@ class HCMEngine(_EngineBase):
     # ---- training / validation path: T*N frames per call, RNNStateEncoder.seq_forward (state_encoder.py:83-133)
     def high_forward_seq(self, observations, hidden, masks):
         with torch.cuda.device(self.device):
-            rgb, depth, ids, lens, TN = self._obs(observations, True, slots=(0,))
+            rgb, depth, ids, lens, TN = self._obs(observations, True, slots=(0,), seq=True)
             h_in = self._hidden(hidden)
             N = h_in.shape[1]
             if TN % N:
                 raise ValueError(f"{TN} frames is not a multiple of the hidden batch {N}")
+            if isinstance(ids, _InstrStream):
+                ids.check_envs(TN, N)
             m = self._mask(masks, TN)
             logits = torch.empty(TN, self.cfg.num_actions, device=self.device, dtype=torch.float32)
             h_out = torch.empty_like(h_in)
@@ -405,12 +438,14 @@ class HCMEngine(_EngineBase):
         total, stop rows, out-of-range labels, 0]; it is written into `result` when given, so that a caller can keep a table of them and
         read once (check_val_result).  Does not synchronise."""
         with torch.cuda.device(self.device):
-            rgb, depth, ids, lens, TN = self._obs(observations, True)
+            rgb, depth, ids, lens, TN = self._obs(observations, True, seq=True)
             hh = self._hidden(hi_hidden)
             N = hh.shape[1]
             lh = self._hidden(lo_hidden, N)
             if TN % N:
                 raise ValueError(f"{TN} frames is not a multiple of the hidden batch {N}")
+            if isinstance(ids, _InstrStream):
+                ids.check_envs(TN, N)
             m = self._mask(masks, TN)
             oracle = observations["vln_oracle_action_sensor"]
             if not isinstance(oracle, torch.Tensor):
@@ -457,7 +492,14 @@ class HCMEngine(_EngineBase):
         library copies each to the device at the head of the encoder chain that reads it (HCM_ACT_HOST_FRAMES), overlapping the copies
         with BERT and with each other's compute; bit-identical to copying first.
         gather=True (after comm_init()): the returned record is the all-gathered (world * B, 7) record of every rank's environments, rank-major
-        (hcm_act_gather: one ncclAllGather enqueued by the library behind the step)."""
+        (hcm_act_gather: one ncclAllGather enqueued by the library behind the step).
+        observations["instruction_features"] (encode_instruction's output, f32 (B or 1, L, bert_hidden)) replaces BERT; it wins over `instruction`,
+        which may then be left out; `instruction_lengths` still applies.  In graph mode the stream is read IN PLACE, as the trunk features are:
+        there is no static copy, the captured graph is keyed by the stream's address and row count, so keep the tensor alive and at one address
+        over an episode (a new address costs one eager step and one capture)."""
+        if reuse_instruction and isinstance(observations, dict) and observations.get(INSTR_KEY) is not None:
+            raise ValueError(f"reuse_instruction=True together with observations[{INSTR_KEY!r}]: the flag says `keep the previous step's instruction`, "
+                             "the key hands one over -- drop one of them")
         if gather and not self.comm_world:
             raise RuntimeError("act(gather=True) needs comm_init() first")
         if not gather:
@@ -524,6 +566,28 @@ class HCMEngine(_EngineBase):
             self._guard_poll(self._stream(), defer=gather)
         return rec, hh2, lh2
 
+    def encode_instruction(self, instruction, instruction_lengths=None):
+        """BERT alone (hcm_encode_instruction): instruction (rows, L) ids -> f32 (rows, L, bert_hidden) on the engine's device, the tensor the calls
+        take as observations["instruction_features"] in place of the ids; zeros behind instruction_lengths[r] where lengths are given.  BERT is
+        frozen and runs under no_grad in the reference (seq2seq_highlevel_cma.py:192-195), so once per episode is enough: a call fed the stream
+        returns the bits of the call fed the ids when the stream was encoded at the call's own row count (include/hcm.h, hcm_instr_features), and
+        agrees to the precision mode's round-off otherwise.  The values carry the engine's precision: precision="fp32" gives the stream within
+        the fp32 contract (what train.HighLevel should be fed).  Invalidates a reuse_instruction cache, like every entry point but act()."""
+        with torch.cuda.device(self.device):
+            ids = self._dev(instruction, (torch.int64, torch.int32, torch.float32))
+            if ids.dim() != 2 or not 1 <= ids.shape[0] <= self.max_batch or not 1 <= ids.shape[1] <= self.max_instr_len:
+                raise ValueError(f"instruction must be (rows <= {self.max_batch}, L <= {self.max_instr_len}), got {tuple(ids.shape)}")
+            rows, L = ids.shape
+            lens = None
+            if instruction_lengths is not None:
+                lens = self._dev(instruction_lengths, (torch.int32,)).reshape(-1)
+                if lens.numel() != rows:
+                    raise ValueError(f"instruction_lengths must hold {rows} entries, got {lens.numel()}")
+            out = torch.empty(rows, L, self.cfg.bert_hidden, device=self.device, dtype=torch.float32)
+            _lib.check(self._lib.hcm_encode_instruction(self._h, ids.data_ptr(), _TORCH_DT[ids.dtype], _ptr(lens), rows, L, out.data_ptr(),
+                                                        self._stream()), self._h)
+        return out
+
     def refresh_instruction(self, instruction, env_indices, instruction_lengths=None):
         """Recompute the cached instruction stream of the listed environments (those that started a new episode) from
         `instruction` (B, L) -- same L as the cached step; afterwards act(..., reuse_instruction=True) is valid again
@@ -583,6 +647,7 @@ class Seq2Seq_HighLevel_CMA(_ModelBase):
     def forward(self, batch):
         observations, rnn_hidden_states, prev_actions, masks = batch   # prev_actions unused (use_prev_action=False)
         # RNNStateEncoder.forward dispatch (state_encoder.py:135-137): frames == hidden batch -> single step, else sequence
+        # (observations["instruction_features"], the frozen BERT stream, is taken in place of the ids by both calls: HCMEngine.encode_instruction)
         if obs_rows(observations) == rnn_hidden_states.shape[1]:
             logits, hidden = self.engine.high_forward(observations, rnn_hidden_states, masks)
         else:

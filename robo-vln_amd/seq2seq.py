@@ -54,6 +54,7 @@ class S2SEngine(_FlatEngine):
         rgb, depth, B = self._frames(observations, (0,), self._frame_check)      # (or rgb_features / depth_features)
         if rows is not None and B != rows:
             raise ValueError(f"expected {rows} frames, got {B}")
+        self._no_instr_stream(observations)
         ids = self._dev(observations["instruction"], (torch.int64, torch.int32, torch.float32))
         # cfg.instr_len is the longest padded instruction the workspace is sized for; every call brings its own L.  A (1, L) instruction is NOT
         # expanded here: the library encodes it once and writes the vector to all B rows (seq2seq.py:163)

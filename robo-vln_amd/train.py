@@ -1460,7 +1460,7 @@ class HighLevel(nn.Module):
 
     forward((observations, rnn_hidden_states, prev_actions, masks)) -> (logits, rnn_hidden_states) as :170-233, with
     observations["rgb_features"] (rows, 2048, 4, 4) and ["depth_features"] (rows, C, s, s) -- the high entries of HCMEngine.encode_features' pairs;
-    a pair is accepted and its entry 0 taken; an ablated modality needs no key -- and ["instruction_features"] (rows or 1, L, ins_in): BERT is
+    a pair is accepted and its entry 0 taken; an ablated modality needs no key -- and ["instruction_features"] (rows or 1 or N | rows, L, ins_in): BERT is
     frozen and runs under no_grad in the reference (:192-195), so its output enters as a tensor.  Without that key the stream is
     embedder(observations["instruction"]) under no_grad; with neither a ValueError names the key.
 
@@ -1522,8 +1522,12 @@ class HighLevel(nn.Module):
                                  f"{self.cfg.ins_in}) is missing, and there is no embedder with observations['instruction'] to compute it from")
             with torch.no_grad():                                              # :192-195
                 stream = self.embedder(observations["instruction"].long())
-        if stream.dim() != 3 or stream.shape[0] not in (1, rows) or stream.shape[2] != self.cfg.ins_in:
-            raise ValueError(f"HighLevel takes instruction_features ({rows} or 1, L, {self.cfg.ins_in}), got {tuple(stream.shape)}")
+        if stream.dim() != 3 or stream.shape[0] < 1 or rows % stream.shape[0] or stream.shape[2] != self.cfg.ins_in:
+            raise ValueError(f"HighLevel takes instruction_features ({rows} or 1, L, {self.cfg.ins_in}) -- or (N, L, {self.cfg.ins_in}) with N dividing "
+                             f"the {rows} time-major rows, one stream per trajectory -- got {tuple(stream.shape)}")
+        if stream.shape[0] not in (1, rows):
+            # one stream per trajectory (HCMEngine.encode_instruction of the N instructions): row t*N + n takes trajectory n's, as the collate repeats the ids
+            return stream.detach().repeat(rows // stream.shape[0], 1, 1)
         return stream.detach().expand(rows, stream.shape[1], stream.shape[2])  # :190
 
     def _visual(self, name, feat, enc, fc, kv, pooled, ablated, rows, C0, I, like):

@@ -87,21 +87,67 @@ class HCMValidator(_FeatureCache):
 
     `engine` needs `val_step`, `num_recurrent_layers`, `cfg.hidden`, `device` and `check_val_result` -- HCMEngine, or a stand-in in tests.
     cache_features / cache_device: see _FeatureCache (off by default; the engine then needs `encode_features` too).
+    cache_instruction (off by default; the engine then needs `encode_instruction`; independent of cache_features): BERT is frozen and runs
+    under no_grad in the reference (seq2seq_highlevel_cma.py:192-195), and the collate repeats an episode's instruction at every step, so only
+    N of a chunk's T*N instruction rows are distinct.  The first run() encodes each chunk's first N rows (time step 0) once and keeps the
+    (N, L, bert_hidden) stream per (batch, chunk) -- on cache_device, under _FeatureCache's rules: a later run() must bring the same chunks,
+    clear_cache() forgets the streams too.  That run and every later one hand the chunk to val_step as `instruction_features` with no
+    `instruction`: BERT runs on N rows once instead of on T*N rows every epoch.  `instruction_lengths` passes through (the first N entries go
+    to the encoder).  check_instruction=True verifies the precondition on the encoding run, `instruction.view(T, N, L) == instruction[:N]`, one
+    device-to-host read per chunk, and raises ValueError when an instruction changes along T.
     """
 
-    def __init__(self, engine, tbptt_steps, batch_size, cache_features=False, cache_device="cuda"):
+    def __init__(self, engine, tbptt_steps, batch_size, cache_features=False, cache_device="cuda", cache_instruction=False, check_instruction=True):
         if tbptt_steps < 1 or batch_size < 1:
             raise ValueError("tbptt_steps and batch_size must be >= 1")
         self.engine = engine
         self.tbptt_steps = int(tbptt_steps)
         self.batch_size = int(batch_size)
+        self.cache_instruction = bool(cache_instruction)
+        self.check_instruction = bool(check_instruction)
         self._init_cache(cache_features, cache_device)
+
+    def clear_cache(self):
+        super().clear_cache()
+        self._streams = {}
+        self._streams_full = False      # as _cache_full, for the instruction streams
 
     def _instruction(self, ids, rows):
         N = self.batch_size
         if ids.shape[0] in (1, rows) or ids.shape[0] != N:
             return ids                                     # (anything else is refused by the engine with its own message)
         return ids.repeat(rows // N, 1)                    # row t*N + n -> the instruction of trajectory n
+
+    def _chunk_stream(self, batch_idx, chunk_idx, obs, rows):
+        """cache_instruction: the chunk's observations with the cached BERT stream under `instruction_features` in place of `instruction`"""
+        if not self.cache_instruction:
+            return obs
+        key = (batch_idx, chunk_idx)
+        hit = self._streams.get(key)
+        if hit is None:
+            if self._streams_full:
+                raise ValueError(f"cache_instruction: batch {batch_idx} chunk {chunk_idx} was not part of the cached run (clear_cache() first)")
+            ids = torch.as_tensor(obs["instruction"])
+            N, lens = self.batch_size, obs.get("instruction_lengths")
+            if ids.shape[0] != 1:                          # (1, L): one instruction for every row, nothing to compare
+                if ids.dim() != 2 or ids.shape[0] != rows:
+                    raise ValueError(f"cache_instruction: instruction must be (1, L), ({N}, L) or ({rows}, L), got {tuple(ids.shape)}")
+                if self.check_instruction and not bool((ids.view(rows // N, N, ids.shape[1]) == ids[:N]).all()):
+                    raise ValueError(f"cache_instruction: batch {batch_idx} chunk {chunk_idx}: an instruction changes along the chunk's time steps -- "
+                                     "the collate repeats an episode's instruction at every step (hierarchical_trainer.py:66-154), and one stream "
+                                     "per trajectory stands for all of them")
+                ids = ids[:N]
+                if lens is not None:
+                    lens = torch.as_tensor(lens).reshape(-1)[:N]
+            elif lens is not None:
+                raise ValueError("cache_instruction: a (1, L) instruction with per-row instruction_lengths has no single stream")
+            hit = self._streams[key] = (rows, self._keep(self.engine.encode_instruction(ids, lens)))
+        elif hit[0] != rows:
+            raise ValueError(f"cache_instruction: batch {batch_idx} chunk {chunk_idx} has {rows} rows, the cached stream was made for {hit[0]} "
+                             "(clear_cache() before validating other batches)")
+        out = {k: v for k, v in obs.items() if k != "instruction"}
+        out["instruction_features"] = hit[1].to(self.engine.device, non_blocking=True)
+        return out
 
     def run(self, batches):
         """Returns a dict:
@@ -140,12 +186,17 @@ class HCMValidator(_FeatureCache):
                 obs = {k: v[i] for k, v in per_key.items() if v is not None}
                 obs["instruction"] = self._instruction(ids, rows)
                 obs = self._chunk_obs(bi, i, obs, rows)
+                obs = self._chunk_stream(bi, i, obs, rows)
                 n_keys += 1
                 _, hh, lh = eng.val_step(obs, c_split[i], s_split[i], hh, lh, m_split[i], result=table[i])
             tables.append(table)
         if not tables:
             raise ValueError("no batches")
         self._close_cache(n_keys)
+        if self.cache_instruction:
+            if self._streams_full and n_keys != len(self._streams):
+                raise ValueError(f"cache_instruction: this run had {n_keys} chunks, the cached one {len(self._streams)} (clear_cache() first)")
+            self._streams_full = True
         table = eng.check_val_result(torch.cat(tables, 0))  # the one device-to-host read; raises on out-of-range labels
         total = float(table[:, 4].sum())
         return {
