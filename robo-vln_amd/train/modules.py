@@ -1,0 +1,276 @@
+"""The drop-in modules: the reference's parameters, state-dict keys, initialisation and forward signatures around the training ops of
+train/ops.py.  Each sends device tensors through its op, at the sizes the kernels are built for (anything else on the device raises), and CPU
+tensors through the op's pure-torch restatement.
+
+`RNNStateEncoder`: the reference's RNNStateEncoder (models/decoder/state_encoder.py) around `state_scan` / `cell_loop`: same parameters, same
+state-dict keys, same argument shapes.
+
+`InterModuleAttnLayer`: the reference's InterModuleAttnLayer (models/transformer/transformer.py:209-221); the three projections are torch,
+everything behind them is `vla_layer` / `vla_layer_ref`.
+
+`Visual_Ling_Attn`: the reference's whole cross-modal encoder (transformer.py:250-282): both prologue halves on `embed_ln` / `embed_ln_ref`, then
+its `InterModuleAttnLayer`s.
+
+`InstructionEncoder`: the reference's InstructionEncoder (models/encoders/instruction_encoder.py:70-92) around `instr_scan` / `instr_encoder_ref`."""
+import torch
+from torch import nn
+
+from .ops import (EMBED_K_STEP, EMBED_MAX_K, INSTR_HIDDEN, SCAN_HIDDEN, VLA_D_MODEL, VLA_HEADS, VLA_MAX_D_FF, cell_loop, embed_k_ok, embed_ln,
+                  embed_ln_ref, instr_encoder_ref, instr_scan, sinusoid_table, state_scan, vla_layer, vla_layer_ref)
+
+
+class RNNStateEncoder(nn.Module):
+    """Drop-in for the reference's RNNStateEncoder: parameters under rnn.weight_ih_l0 / rnn.weight_hh_l0 / rnn.bias_ih_l0 / rnn.bias_hh_l0 in
+    a real nn.GRU / nn.LSTM (storage and initialisation only: orthogonal weights, zero biases), so load_state_dict takes a reference
+    checkpoint's keys unchanged.  Unlike the reference's, seq_forward also serves LSTM."""
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, rnn_type: str = "GRU"):
+        super().__init__()
+        if rnn_type not in ("GRU", "LSTM"):
+            raise ValueError(f"rnn_type must be GRU or LSTM, got {rnn_type!r}")
+        self._num_recurrent_layers = num_layers
+        self._rnn_type = rnn_type
+        self._hidden_size = hidden_size
+        self.rnn = getattr(nn, rnn_type)(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
+        self.layer_init()
+
+    def layer_init(self):
+        for name, param in self.rnn.named_parameters():
+            if "weight" in name:
+                nn.init.orthogonal_(param)
+            elif "bias" in name:
+                nn.init.constant_(param, 0)
+
+    @property
+    def num_recurrent_layers(self):
+        return self._num_recurrent_layers * (2 if "LSTM" in self._rnn_type else 1)
+
+    def _params(self):
+        return [tuple(getattr(self.rnn, f"{n}_l{l}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                for l in range(self._num_recurrent_layers)]
+
+    def _run(self, x, hidden_states, masks):
+        masks = masks.reshape(-1)
+        if not x.is_cuda:
+            return cell_loop(x, self._params(), hidden_states, masks, self._rnn_type)
+        if self._hidden_size != SCAN_HIDDEN or self._num_recurrent_layers != 1:
+            raise ValueError(f"on the device RNNStateEncoder serves hidden_size {SCAN_HIDDEN} with one layer "
+                             f"(got hidden_size {self._hidden_size}, num_layers {self._num_recurrent_layers})")
+        return state_scan(x, *self._params()[0], hidden_states, masks)
+
+    def single_forward(self, x, hidden_states, masks):
+        """x (N, in), hidden_states (R, N, H), masks (N,) or (N, 1): one step (T = 1)"""
+        if x.size(0) != hidden_states.size(1):
+            raise ValueError(f"single_forward takes one row per state, got {x.size(0)} rows for {hidden_states.size(1)} states")
+        return self._run(x, hidden_states, masks)
+
+    def seq_forward(self, x, hidden_states, masks):
+        """x (T*N, in) flattened from (T, N, in), hidden_states (R, N, H), masks (T*N,) or (T*N, 1)"""
+        if x.size(0) % hidden_states.size(1):
+            raise ValueError(f"{x.size(0)} rows are not a whole number of steps of {hidden_states.size(1)} states")
+        return self._run(x, hidden_states, masks)
+
+    def forward(self, x, hidden_states, masks):
+        if x.size(0) == hidden_states.size(1):
+            return self.single_forward(x, hidden_states, masks)
+        return self.seq_forward(x, hidden_states, masks)
+
+
+class _ScaledDotProductAttention(nn.Module):
+    """Parameters and initialisation of the reference's ScaledDotProductAttention (transformer.py:46-79): xavier_normal_ weights, zero biases"""
+
+    def __init__(self, d_model, d_k, d_v, h):
+        super().__init__()
+        self.fc_q = nn.Linear(d_model, h * d_k)
+        self.fc_k = nn.Linear(d_model, h * d_k)
+        self.fc_v = nn.Linear(d_model, h * d_v)
+        self.fc_o = nn.Linear(h * d_v, d_model)
+        for fc in (self.fc_q, self.fc_k, self.fc_v, self.fc_o):
+            nn.init.xavier_normal_(fc.weight, gain=1.0)
+        for fc in (self.fc_q, self.fc_k, self.fc_v, self.fc_o):
+            nn.init.constant_(fc.bias, 0)
+
+
+class _MultiHeadAttention(nn.Module):
+    def __init__(self, d_model, d_k, d_v, h):
+        super().__init__()
+        self.attention = _ScaledDotProductAttention(d_model, d_k, d_v, h)
+        self.layer_norm = nn.LayerNorm(d_model)
+
+
+class _PositionWiseFeedForward(nn.Module):
+    def __init__(self, d_model, d_ff):
+        super().__init__()
+        self.fc1 = nn.Linear(d_model, d_ff)
+        self.fc2 = nn.Linear(d_ff, d_model)
+        self.layer_norm = nn.LayerNorm(d_model)
+
+
+class InterModuleAttnLayer(nn.Module):
+    """Drop-in for the reference's InterModuleAttnLayer (transformer.py:209-221): the same sixteen state-dict keys (enc_att.attention.fc_{q,k,v,o},
+    enc_att.layer_norm, pwff.fc1, pwff.fc2, pwff.layer_norm), the same initialisation and forward signature.  fc_q / fc_k / fc_v are ordinary
+    nn.Linear through torch autograd; everything behind them is vla_layer on the device and vla_layer_ref on the CPU.  In train mode with
+    dropout > 0 the three keep masks are drawn with torch's generator on the input's device (draw_keep), so torch.manual_seed governs them."""
+
+    def __init__(self, d_model=256, d_k=64, d_v=64, h=4, d_ff=1024, dropout=.1):
+        super().__init__()
+        self.enc_att = _MultiHeadAttention(d_model, d_k, d_v, h)
+        self.pwff = _PositionWiseFeedForward(d_model, d_ff)
+        self.d_model, self.d_k, self.d_v, self.h, self.d_ff, self.dropout = d_model, d_k, d_v, h, d_ff, float(dropout)
+
+    def draw_keep(self, rows, device):
+        """The three uint8 keep masks of one call: (rows, d_model), (rows, d_ff), (rows, d_model), each element kept with probability 1 - dropout"""
+        return tuple((torch.rand(rows, n, device=device) >= self.dropout).to(torch.uint8) for n in (self.d_model, self.d_ff, self.d_model))
+
+    def forward(self, input_1, input_2, mask_self_att, mask_enc_att, pos_embed=None, _keep=None):
+        if mask_enc_att is not None:
+            raise ValueError("InterModuleAttnLayer serves mask_enc_att = None, as the high-level model calls it (seq2seq_highlevel_cma.py:200-201)")
+        att, ln1, ff = self.enc_att.attention, self.enc_att.layer_norm, self.pwff
+        p = self.dropout if self.training else 0.0
+        keep = _keep
+        if keep is None and p > 0:
+            keep = self.draw_keep(input_1.shape[0] * input_1.shape[1], input_1.device)
+        q = att.fc_q(input_1)
+        kv = torch.cat([att.fc_k(input_2), att.fc_v(input_2)], -1)
+        args = (q, input_1, kv, att.fc_o.weight, att.fc_o.bias, ff.fc1.weight, ff.fc1.bias, ff.fc2.weight, ff.fc2.bias,
+                ln1.weight, ln1.bias, ff.layer_norm.weight, ff.layer_norm.bias)
+        if not input_1.is_cuda:
+            return vla_layer_ref(*args, keep=keep, p=p, heads=self.h)
+        if (self.d_model, self.d_k, self.d_v, self.h) != (VLA_D_MODEL, 64, 64, VLA_HEADS) or self.d_ff % 256 or not 256 <= self.d_ff <= VLA_MAX_D_FF:
+            raise ValueError(f"on the device InterModuleAttnLayer serves d_model {VLA_D_MODEL}, {VLA_HEADS} heads of 64 and d_ff a multiple of 256 up to "
+                             f"{VLA_MAX_D_FF} (got d_model {self.d_model}, d_k {self.d_k}, d_v {self.d_v}, h {self.h}, d_ff {self.d_ff})")
+        return vla_layer(*args, keep=keep, p=p)
+
+
+class Visual_Ling_Attn(nn.Module):
+    """Drop-in for the reference's Visual_Ling_Attn (transformer.py:250-282), `image_cm_encoder` of the high-level model: the reference's state-dict
+    keys (layers.{i}.<the sixteen keys of InterModuleAttnLayer>, vis_fc.*, ins_fc.*, layer_norm.*), initialisation and forward signature.  Takes the
+    reference's config object (N, vis_in_features, ins_in_features, d_model, h, d_ff, dropout) or the same names as keyword arguments, which win.
+
+    Both prologue halves are embed_ln on the device and embed_ln_ref on the CPU; one layer_norm serves both, and its gradient accumulates
+    through autograd.  The sinusoid table is kept per (L, device) in the plain dict `_tables` -- no buffer, not in the state dict -- so the device
+    path copies nothing per call.  In train mode with dropout > 0 the keep masks are drawn by draw_keep with torch's generator on the input's
+    device, in the order vis half, ins half, then each layer's three, so torch.manual_seed governs them; `_keep` takes them explicitly."""
+
+    def __init__(self, config=None, **kw):
+        super().__init__()
+        names = ("N", "vis_in_features", "ins_in_features", "d_model", "h", "d_ff", "dropout")
+        unknown = set(kw) - set(names)
+        if unknown:
+            raise TypeError(f"Visual_Ling_Attn: unknown arguments {sorted(unknown)}")
+        missing = [n for n in names if n not in kw and not hasattr(config, n)]
+        if missing:
+            raise TypeError(f"Visual_Ling_Attn: missing {missing}")
+        N, vis_in, ins_in, d_model, h, d_ff, dropout = (kw[n] if n in kw else getattr(config, n) for n in names)
+        self.d_model, self.d_att, self.p = d_model, int(d_model / h), float(dropout)
+        self.layers = nn.ModuleList([InterModuleAttnLayer(d_model, self.d_att, self.d_att, h, d_ff, dropout) for _ in range(N)])
+        self.vis_fc = nn.Linear(vis_in, d_model)
+        self.ins_fc = nn.Linear(ins_in, d_model)
+        self.layer_norm = nn.LayerNorm(d_model)
+        self._tables = {}
+
+    def table(self, L, device):
+        key = (L, torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = sinusoid_table(L, self.d_model).to(device)
+        return self._tables[key]
+
+    def draw_keep(self, B, L, Lk, device):
+        """The uint8 keep masks of one call in their fixed order: (vis half (B*Lk, d_model), ins half (B*L, d_model), layer 0's three, layer 1's three, ...)"""
+        def draw(rows):
+            return (torch.rand(rows, self.d_model, device=device) >= self.p).to(torch.uint8)
+        vis, ins = draw(B * Lk), draw(B * L)
+        return (vis, ins, *(layer.draw_keep(B * L, device) for layer in self.layers))
+
+    def _embed(self, x, fc, keep, p, post):
+        args = (x, fc.weight, fc.bias, self.layer_norm.weight, self.layer_norm.bias)
+        if not x.is_cuda:
+            return embed_ln_ref(*args, keep=keep, p=p, post=post)
+        if self.d_model != VLA_D_MODEL or not embed_k_ok(fc.in_features):
+            raise ValueError(f"on the device Visual_Ling_Attn serves d_model {VLA_D_MODEL} and input widths that are multiples of {EMBED_K_STEP} from "
+                             f"{EMBED_K_STEP} to {EMBED_MAX_K} (got d_model {self.d_model}, in_features {fc.in_features})")
+        return embed_ln(*args, keep=keep, p=p, post=post)
+
+    def forward(self, input, input_2, self_att_mask, enc_att_mask, _keep=None):
+        if self_att_mask is not None or enc_att_mask is not None:
+            raise ValueError("Visual_Ling_Attn serves self_att_mask = enc_att_mask = None, as the high-level model calls it (seq2seq_highlevel_cma.py:200-201)")
+        if input.dim() != 3 or input_2.dim() != 3 or input.shape[0] != input_2.shape[0]:
+            raise ValueError(f"Visual_Ling_Attn takes input (B, L, ins_in) and input_2 (B, Lk, vis_in), got {tuple(input.shape)}, {tuple(input_2.shape)}")
+        B, L, Lk = input.shape[0], input.shape[1], input_2.shape[1]
+        p = self.p if self.training else 0.0
+        keep = _keep
+        if keep is None:
+            keep = self.draw_keep(B, L, Lk, input.device) if p > 0 else (None, None) + (None,) * len(self.layers)
+        out = self._embed(input_2, self.vis_fc, keep[0], p, None)
+        inp = self._embed(input, self.ins_fc, keep[1], p, self.table(L, input.device))
+        for layer, k in zip(self.layers, keep[2:]):
+            out = layer(inp, out, None, None, _keep=k)
+        return out
+
+
+class InstructionEncoder(nn.Module):
+    """Drop-in for the reference's InstructionEncoder (models/encoders/instruction_encoder.py): the reference's state-dict keys --
+    embedding_layer.weight and encoder_rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0, with the _reverse suffix for the second direction -- in a
+    real nn.Embedding and a real nn.LSTM / nn.GRU (storage and initialisation only), so load_state_dict takes a reference checkpoint's keys
+    unchanged.  Takes the reference's config object (vocab_size, embedding_size, hidden_size, rnn_type, bidirectional, final_state_only,
+    fine_tune_embeddings) or the same names as keyword arguments, which win.  `embeddings=` (vocab, E) stands in for the reference's file load:
+    the table is nn.Embedding.from_pretrained(embeddings, freeze=not fine_tune_embeddings), as with use_pretrained_embeddings; without it the
+    table is a trainable nn.Embedding(vocab_size, embedding_size, padding_idx=0), as in the reference.
+
+    forward(instruction) takes (B, L) token ids, 0 = padding, and derives lengths = (instruction != 0).sum(1) on the device: nothing is read
+    back to the host.  With final_state_only it returns (B, hidden); otherwise (B, D, L), D = hidden * directions: the reference's
+    (B, D, max(lengths)) zero-padded to L -- trimming to max(lengths) would need the host read this module exists to remove.  CMANet masks
+    all-zero columns (cma.py:273), so the model's outputs are unchanged.
+
+    Device tensors go through instr_scan (hidden size 256; anything else raises), CPU tensors through instr_encoder_ref.  final_state_only
+    together with bidirectional is refused: the reference returns a (2, B, H) tensor there that no model can consume."""
+
+    NAMES = ("vocab_size", "embedding_size", "hidden_size", "rnn_type", "bidirectional", "final_state_only", "fine_tune_embeddings")
+
+    def __init__(self, config=None, embeddings=None, **kw):
+        super().__init__()
+        unknown = set(kw) - set(self.NAMES)
+        if unknown:
+            raise TypeError(f"InstructionEncoder: unknown arguments {sorted(unknown)}")
+        given = dict(fine_tune_embeddings=False)
+        if embeddings is not None:
+            given.update(vocab_size=embeddings.shape[0], embedding_size=embeddings.shape[1])
+        given.update({n: getattr(config, n) for n in self.NAMES if hasattr(config, n)})
+        given.update(kw)
+        missing = [n for n in self.NAMES if n not in given]
+        if missing:
+            raise TypeError(f"InstructionEncoder: missing {missing}")
+        vocab, E, H, rnn_type, bidir, final, fine_tune = (given[n] for n in self.NAMES)
+        if rnn_type not in ("GRU", "LSTM"):
+            raise ValueError(f"rnn_type must be GRU or LSTM, got {rnn_type!r}")
+        if final and bidir:
+            raise ValueError("InstructionEncoder: final_state_only with bidirectional is refused (the reference returns a (2, B, H) tensor no model consumes)")
+        if embeddings is not None:
+            if tuple(embeddings.shape) != (vocab, E):
+                raise ValueError(f"InstructionEncoder: embeddings has shape {tuple(embeddings.shape)}, expected {(vocab, E)}")
+            self.embedding_layer = nn.Embedding.from_pretrained(embeddings.detach().clone().float(), freeze=not fine_tune)
+        else:
+            self.embedding_layer = nn.Embedding(num_embeddings=vocab, embedding_dim=E, padding_idx=0)
+        self.encoder_rnn = getattr(nn, rnn_type)(input_size=E, hidden_size=H, bidirectional=bool(bidir))
+        self.rnn_type, self.hidden_size, self.bidir, self.final_state_only = rnn_type, H, bool(bidir), bool(final)
+
+    @property
+    def output_size(self):
+        return self.hidden_size * (2 if self.bidir else 1)
+
+    def _params(self):
+        return [tuple(getattr(self.encoder_rnn, f"{n}_l0{sfx}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                for sfx in (("", "_reverse") if self.bidir else ("",))]
+
+    def forward(self, instruction):
+        if instruction.dim() != 2:
+            raise ValueError(f"InstructionEncoder takes instruction (B, L), got {tuple(instruction.shape)}")
+        lengths = (instruction != 0).sum(1)
+        embedded = self.embedding_layer(instruction.long())
+        if not instruction.is_cuda:
+            y = instr_encoder_ref(embedded, lengths, self._params(), self.final_state_only)
+        else:
+            if self.hidden_size != INSTR_HIDDEN:
+                raise ValueError(f"on the device InstructionEncoder serves hidden_size {INSTR_HIDDEN} (got {self.hidden_size})")
+            y = instr_scan(embedded, lengths, self._params(), self.final_state_only)
+        return y if self.final_state_only else y.permute(0, 2, 1)

@@ -7,7 +7,7 @@ loss.backward(), and two Adam steps) against train.HighLevel / train.LowLevel, t
              state and final parameters -- within 1e-9 of the tensor's largest element (a projection: 1e-9 sqrt(n) max|g|; sum|g|: 1e-9 n max|g|).  Float64 round-off
              over these reductions is ~1e-14 and the float32 bound 5e-6: 1e-9 separates "the same function" from "the same to float32".
   zeros      a key bias cancels in the softmax: the fixture's own values are below 1e-12 of the partner weight's gradient, ours are compared on
-             that scale, and where train.py promises exact zeros (_ZeroGrad, the unused key halves, an ablated modality) they are exact
+             that scale, and where train/models.py promises exact zeros (_ZeroGrad, the unused key halves, an ablated modality) they are exact
   float32    a condition on the cases, not a tolerance on the code (tests/test_train_coverage_cpu.py): the same modules in float32 on the CPU
              stay within half the GPU bound, 5e-6, of the fixture in every figure, so that the GPU tests' 1e-5 has room for the kernels.
 

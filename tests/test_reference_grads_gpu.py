@@ -7,7 +7,7 @@ to the device; nothing outside the repository is read.
 
 The bound is the project's rule for the training ops, BOUND = 1e-5: per tensor max|g - g_ref| / max|g_ref| on the stored values, forward values
 on their tensor's largest element, a projection on sqrt(n) max|g_ref|, sum|g| on n max|g_ref| (tests/update_ref.errors).  The counts, the
-partition of the parameters into gradient / None, and the zeros train.py promises are exact; a cancelling key bias is held to the bound on its
+partition of the parameters into gradient / None, and the zeros train/models.py promises are exact; a cancelling key bias is held to the bound on its
 weight's scale.  The float32 CPU run of the same modules stays within half of it (tests/test_reference_grads_cpu.py), which leaves the kernels
 the other half.
 

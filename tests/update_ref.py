@@ -277,7 +277,7 @@ def trajectory(name, nets, conv):
 
 @contextlib.contextmanager
 def relu_inputs(record):
-    """record(x) for every ReLU input of the CPU path: train.py calls torch.relu, an nn.ReLU module F.relu"""
+    """record(x) for every ReLU input of the CPU path: train/models.py and train/ops.py call torch.relu, an nn.ReLU module F.relu"""
     relu, f_relu = torch.relu, F.relu
 
     def patched(x):
