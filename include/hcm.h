@@ -914,6 +914,36 @@ int hcm_op_subtask_ce_bwd(const float* d_result, const float* x, const float* w,
                           const float* result, float* d_x, float* d_w, float* d_b, float* work, int rows, int hidden, int A, int num_sub_tasks,
                           void* stream);
 
+/* The convolutional part of the reference's SimpleAllCNN.cnn (models/encoders/simple_cnns.py:76-95) in float32 with a backward pass
+ * (csrc/simplecnn_train.hip), the trainable form of what hcm_op_simplecnn3 runs for the engines:
+ *   Conv2d(Cin, 32, 8, stride 4) + ReLU -> Conv2d(32, 64, 4, stride 2) + ReLU -> Conv2d(64, 32, 3, stride 1), no padding.
+ *   x (B, H, W, Cin), the frames as the observations carry them: HCM_F32, or HCM_U8 with Cin = 3; every element is multiplied by `scale` (1/255
+ *   for RGB bytes, 1 for depth) as it is read.  Cin is 1 or 3; H, W >= 36, any other size, non-square allowed.
+ *   w1 (32, Cin, 8, 8), b1 (32), w2 (64, 32, 4, 4), b2 (64), w3 (32, 64, 3, 3), b3 (32): torch's OIHW parameters, float32 on the device.
+ *   With h1 = (H - 8) / 4 + 1, h2 = (h1 - 4) / 2 + 1, h3 = h2 - 2 (and w likewise):  y (B, 32, h3, w3), contiguous and channel-major, so
+ *   y viewed as (B, 32 h3 w3) is the reference's Flatten order in front of cnn.7.
+ * hcm_op_simplecnn_train packs the three weights into `work` (one small launch each) and runs one launch per convolution on
+ *   v_mfma_f32_32x32x2f32.  It writes y and leaves the two post-ReLU maps in `work` for the backward; their layout is the kernels' business.
+ *   Every output element sums its window in the order (ci, ky, kx) ascending, so a row's bits depend on that row and the weights alone, not on
+ *   B or the row's position.
+ * hcm_op_simplecnn_bwd takes d_y (B, 32, h3, w3), the frames, scale, w2 and w3 as the forward had them and THE SAME `work` the forward filled,
+ *   and writes d_w1, d_b1, d_w2, d_b2, d_w3, d_b3 in the parameters' shapes: per layer from the last, the weight gradient (a chunk of output
+ *   pixels per workgroup, the chunks' shares added in chunk order by a second launch), the bias sum (a fixed tree), and for conv3 and conv2 the
+ *   gradient of the layer's input gated by `stored value > 0`, torch's in-place ReLU.  A pixel of map 1 or map 2 that no window of the next
+ *   convolution covers receives an exact zero.  There is no frame gradient.  The backward leaves the maps intact, so it may run twice.
+ * work: hcm_op_simplecnn_work_floats(B, H, W, Cin) floats (0 for unsupported arguments) owned by the caller: packed weights, the two maps,
+ *   the two gated gradients, the chunk shares.  No output may overlap it.  The float tensors must be 4-byte aligned.
+ * HCM_ERR_ARG with a message (hcm_last_error(NULL)), never a launch: Cin outside {1, 3}, a frame under 36 pixels, HCM_U8 with Cin = 1 or any
+ *   other dtype, B < 0, a call so large that an element offset leaves 31 bits, a NULL required pointer, an output overlapping work, a
+ *   misaligned pointer.  No pointer may be NULL, except that with B = 0 the forward is HCM_OK and touches nothing, and the backward writes
+ *   zeros to the six gradients and reads no other pointer.
+ * The ops allocate nothing, copy nothing to the host, do not synchronise, run on `stream`, use no atomics and are bitwise reproducible. */
+int64_t hcm_op_simplecnn_work_floats(int B, int H, int W, int Cin);
+int hcm_op_simplecnn_train(const void* x, int x_dtype, float scale, const float* w1, const float* b1, const float* w2, const float* b2,
+                           const float* w3, const float* b3, float* y, float* work, int B, int H, int W, int Cin, void* stream);
+int hcm_op_simplecnn_bwd(const float* d_y, const void* x, int x_dtype, float scale, const float* w2, const float* w3, float* work, float* d_w1,
+                         float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3, int B, int H, int W, int Cin, void* stream);
+
 /* csrc/features.hip alone: x (rows, C, S) f32 contiguous (the reference's NCHW feature) <-> columns [0, C) of y [rows][S][ld] in the storage
  * type `dtype`, times `scale` (a power of two at every call site).  Any rows in [1, 65535], C, S >= 1, ld >= C. */
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream);

@@ -174,6 +174,9 @@ EXPORTS = {
     "hcm_op_subtask_ce_work_floats": (C.c_int64, [C.c_int] * 3),
     "hcm_op_subtask_ce_train": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
     "hcm_op_subtask_ce_bwd": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_simplecnn_work_floats": (C.c_int64, [C.c_int] * 4),
+    "hcm_op_simplecnn_train": (C.c_int, [C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p]),
+    "hcm_op_simplecnn_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_void_p]),
     "hcm_op_feat_ingest":(C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "hcm_op_feat_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "hcm_op_instr_feat_ingest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),

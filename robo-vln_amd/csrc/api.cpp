@@ -2141,6 +2141,66 @@ int hcm_op_subtask_ce_bwd(const float* d_result, const float* x, const float* w,
     return op_rc(launch_subtask_ce_bwd(t, (hipStream_t)stream));
 }
 
+int64_t hcm_op_simplecnn_work_floats(int B, int H, int W, int Cin) {
+    return simplecnn_train_ok(B, H, W, Cin) ? (int64_t)simplecnn_train_work_floats(B, H, W, Cin) : 0;
+}
+
+static int simplecnn_arg_err(const char* what) {
+    g_create_err = std::string("simplecnn_train: ") + what;
+    return HCM_ERR_ARG;
+}
+// the kernels move single floats: every float tensor on a 4-byte boundary
+static bool simplecnn_aligned(std::initializer_list<const void*> f32) {
+    for (const void* p : f32) if ((uintptr_t)p % 4) return false;
+    return true;
+}
+static int simplecnn_dims(int x_dtype, int B, int H, int W, int Cin) {
+    if (Cin != 1 && Cin != 3) return simplecnn_arg_err("Cin must be 1 or 3");
+    if (x_dtype != HCM_F32 && !(x_dtype == HCM_U8 && Cin == 3)) return simplecnn_arg_err("frames are HCM_F32, or HCM_U8 with Cin = 3");
+    if (B < 0) return simplecnn_arg_err("B must be at least 0");
+    if (H < 36 || W < 36) return simplecnn_arg_err("frames must be at least 36 x 36");
+    if (!simplecnn_train_ok(B, H, W, Cin)) return simplecnn_arg_err("the call is too large: an element offset would not fit 31 bits");
+    return HCM_OK;
+}
+// the element counts of y (B, 32, h3, w3) and of the three weight tensors
+static size_t simplecnn_y_floats(int B, int H, int W) {
+    const int h1 = (H - 8) / 4 + 1, w1 = (W - 8) / 4 + 1, h2 = (h1 - 4) / 2 + 1, w2 = (w1 - 4) / 2 + 1;
+    return (size_t)B * 32 * (h2 - 2) * (w2 - 2);
+}
+
+int hcm_op_simplecnn_train(const void* x, int x_dtype, float scale, const float* w1, const float* b1, const float* w2, const float* b2,
+                           const float* w3, const float* b3, float* y, float* work, int B, int H, int W, int Cin, void* stream) {
+    const int rc = simplecnn_dims(x_dtype, B, H, W, Cin);
+    if (rc != HCM_OK) return rc;
+    if (B == 0) return HCM_OK;
+    if (!x || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !y || !work) return simplecnn_arg_err("a required pointer is NULL");
+    if (!simplecnn_aligned({w1, b1, w2, b2, w3, b3, y, work, x_dtype == HCM_F32 ? x : nullptr}))
+        return simplecnn_arg_err("the float tensors must be 4-byte aligned");
+    if (vla_train_in_work(work, simplecnn_train_work_floats(B, H, W, Cin), {{y, simplecnn_y_floats(B, H, W)}}))
+        return simplecnn_arg_err("an output overlaps work");
+    SimpleCnnTrainArgs t;
+    t.x = x; t.x_u8 = x_dtype == HCM_U8; t.scale = scale; t.w1 = w1; t.b1 = b1; t.w2 = w2; t.b2 = b2; t.w3 = w3; t.b3 = b3; t.y = y; t.work = work;
+    t.B = B; t.H = H; t.W = W; t.Cin = Cin;
+    return op_rc(launch_simplecnn_train_fwd(t, (hipStream_t)stream));
+}
+
+int hcm_op_simplecnn_bwd(const float* d_y, const void* x, int x_dtype, float scale, const float* w2, const float* w3, float* work, float* d_w1,
+                         float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3, int B, int H, int W, int Cin, void* stream) {
+    const int rc = simplecnn_dims(x_dtype, B, H, W, Cin);
+    if (rc != HCM_OK) return rc;
+    if (!d_w1 || !d_b1 || !d_w2 || !d_b2 || !d_w3 || !d_b3) return simplecnn_arg_err("a required pointer is NULL");
+    if (B > 0 && (!d_y || !x || !w2 || !w3 || !work)) return simplecnn_arg_err("a required pointer is NULL");
+    if (!simplecnn_aligned({d_y, w2, w3, work, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, x_dtype == HCM_F32 ? x : nullptr}))
+        return simplecnn_arg_err("the float tensors must be 4-byte aligned");
+    if (B > 0 && vla_train_in_work(work, simplecnn_train_work_floats(B, H, W, Cin),
+                                   {{d_w1, (size_t)32 * Cin * 64}, {d_b1, 32}, {d_w2, (size_t)64 * 512}, {d_b2, 64}, {d_w3, (size_t)32 * 576}, {d_b3, 32}}))
+        return simplecnn_arg_err("an output overlaps work");
+    SimpleCnnTrainArgs t;
+    t.d_y = d_y; t.x = x; t.x_u8 = x_dtype == HCM_U8; t.scale = scale; t.w2 = w2; t.w3 = w3; t.work = work;
+    t.d_w1 = d_w1; t.d_b1 = d_b1; t.d_w2 = d_w2; t.d_b2 = d_b2; t.d_w3 = d_w3; t.d_b3 = d_b3; t.B = B; t.H = H; t.W = W; t.Cin = Cin;
+    return op_rc(launch_simplecnn_train_bwd(t, (hipStream_t)stream));
+}
+
 int hcm_op_feat_ingest(const float* x, void* y, int dtype, int rows, int C, int S, int ld, float scale, void* stream) {
     return op_rc(hcm::launch_feat_ingest(x, y, op_dt(dtype), rows, C, S, ld, scale, (hipStream_t)stream));
 }

@@ -445,6 +445,25 @@ bool subtask_ce_ok(int rows, int hidden, int A, int num_sub_tasks);
 size_t subtask_ce_work_floats(int rows, int A);
 hipError_t launch_subtask_ce_fwd(const SubtaskCeArgs& t, hipStream_t s);
 hipError_t launch_subtask_ce_bwd(const SubtaskCeArgs& t, hipStream_t s);
+// The convolutional part of SimpleAllCNN.cnn in float32 with a backward pass (simplecnn_train.hip): Conv2d(Cin, 32, 8, 4) + ReLU ->
+// Conv2d(32, 64, 4, 2) + ReLU -> Conv2d(64, 32, 3, 1) over frames (B, H, W, Cin), f32 or (x_u8) bytes, times `scale`; weights OIHW.  One argument
+// block for both directions, as FlatHeadsArgs.  work: simplecnn_train_work_floats() floats -- the packed weights, the two post-ReLU maps the
+// forward leaves for the backward, the gated gradients and the weight gradients' chunk shares.  No allocation, no host copy, no synchronisation,
+// no atomics.
+struct SimpleCnnTrainArgs {
+    const void* x = nullptr;                                                           // [B][H][W][Cin]
+    const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
+    float* y = nullptr;                                                                // forward out: [B][32][h3][w3]
+    const float* d_y = nullptr;                                                        // backward in
+    float *d_w1 = nullptr, *d_b1 = nullptr, *d_w2 = nullptr, *d_b2 = nullptr, *d_w3 = nullptr, *d_b3 = nullptr;
+    float* work = nullptr;
+    float scale = 1.f;
+    int x_u8 = 0, B = 0, H = 0, W = 0, Cin = 0;
+};
+bool simplecnn_train_ok(int B, int H, int W, int Cin);
+size_t simplecnn_train_work_floats(int B, int H, int W, int Cin);
+hipError_t launch_simplecnn_train_fwd(const SimpleCnnTrainArgs& t, hipStream_t s);
+hipError_t launch_simplecnn_train_bwd(const SimpleCnnTrainArgs& t, hipStream_t s);
 // dst[r][0..cols) = src[(n_src == 1 ? 0 : r)][0..cols), r < rows (f32; the per-token fall-back's gather / broadcast of the final states)
 hipError_t launch_copy_rows(const float* src, int ld_src, int n_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s);
 hipError_t launch_attn1q(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int* lengths, float* out,

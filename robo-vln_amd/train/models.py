@@ -15,7 +15,7 @@ different models and stay apart."""
 import torch
 from torch import nn
 
-from .modules import InstructionEncoder, RNNStateEncoder, Visual_Ling_Attn
+from .modules import InstructionEncoder, RNNStateEncoder, SimpleDepthCNN, SimpleRGBCNN, Visual_Ling_Attn
 from .ops import CHANNEL_MAJOR, TOKEN_MAJOR, _zero_grads, _ZeroGrad, attn1q, attn1q_ref, flat_heads_loss, subtask_ce
 
 CMA_TRUNK_PREFIXES = ("rgb_encoder.cnn.", "depth_encoder.visual_encoder.")
@@ -41,6 +41,32 @@ def _refuse_simple_cnn(cls, cfg):
     if cfg.rgb_encoder != "TorchVisionResNet50" or cfg.depth_encoder != "VlnResnetDepthEncoder":
         raise ValueError(f"train.{cls} trains from cached features of the two frozen ResNet trunks; SimpleRGBCNN / SimpleDepthCNN are trainable "
                          f"trunks with nothing to cache (got rgb_encoder {cfg.rgb_encoder!r}, depth_encoder {cfg.depth_encoder!r})")
+
+
+def _simple_trunks(cls, cfg, trainable_trunks):
+    """(rgb is a SimpleRGBCNN, depth is a SimpleDepthCNN) for a model built with trainable_trunks=True; without the keyword the SimpleCNN
+    encoders are refused, as they always were"""
+    if not trainable_trunks:
+        _refuse_simple_cnn(cls, cfg)
+        return False, False
+    return cfg.rgb_encoder == "SimpleRGBCNN", cfg.depth_encoder == "SimpleDepthCNN"
+
+
+def _frozen_prefixes(simple_rgb, simple_depth):
+    """the trunk prefixes load_reference_state_dict drops: those of the ResNet modalities; a SimpleCNN's keys are the model's own"""
+    return tuple(p for p, simple in zip(CMA_TRUNK_PREFIXES, (simple_rgb, simple_depth)) if not simple)
+
+
+def _simple_visual(model, enc, observations, ablated, rows, like):
+    """One modality's embedding from a trainable SimpleCNN encoder (rows, out): the encoder on its frames; ablated: the encoder runs and its
+    output is multiplied by 0 (seq2seq.py:158-161, seq2seq_lowlevel.py:132-135), so its parameters get zero gradients; ablated without the
+    frames key: exact zeros, and zero gradients through _zero_grads"""
+    if ablated and enc.KEY not in observations:
+        return _zero_grads(like.new_zeros(rows, enc.output_size), *enc.parameters())
+    y = enc(observations)
+    if y.shape[0] != rows:
+        raise ValueError(f"{model} takes one {enc.KEY} frame per row: {rows} rows, observations['{enc.KEY}'] {tuple(observations[enc.KEY].shape)}")
+    return y * 0 if ablated else y
 
 
 def _init_monitor(progress_monitor):
@@ -275,24 +301,28 @@ class Seq2SeqNet(_FromReference):
     parameters only, as in the reference.  update_loss(batch, corrected_actions, oracle_stop) is the model and the criterion of the trainer's
     update step, with the auxiliary progress loss against observations["progress"] when the monitor is on.
 
-    The SimpleCNN encoders are trunks that train with the model: there is nothing to cache, and they are refused."""
+    The SimpleCNN encoders are trunks that train with the model: there is nothing to cache, and without a keyword they are refused.  With
+    trainable_trunks=True a modality whose encoder is a SimpleCNN gets train.SimpleRGBCNN / train.SimpleDepthCNN under the reference's keys
+    (rgb_encoder.cnn.*, depth_encoder.cnn.*), reads observations["rgb"] / ["depth"] -- the frames -- in place of the cached feature, and is
+    loaded by load_reference_state_dict with everything else; a ResNet modality of the same model still trains from its cached feature."""
 
     FROZEN_PREFIXES = S2S_TRUNK_PREFIXES
     _flat_heads = staticmethod(flat_heads_loss)
 
-    def __init__(self, cfg, embeddings=None):
+    def __init__(self, cfg, embeddings=None, trainable_trunks=False):
         super().__init__()
         cfg.validate()
-        _refuse_simple_cnn("Seq2SeqNet", cfg)
+        self.simple_rgb, self.simple_depth = _simple_trunks("Seq2SeqNet", cfg, trainable_trunks)
+        self.FROZEN_PREFIXES = _frozen_prefixes(self.simple_rgb, self.simple_depth)
         self.cfg = cfg
         self.monitor = bool(cfg.progress_monitor)
-        fs, cc = cfg.depth_final_spatial(), cfg.depth_compress_channels()
+        fs, cc = (0, 0) if self.simple_depth else (cfg.depth_final_spatial(), cfg.depth_compress_channels())
         self.depth_shape = (cc, fs)
         self.instruction_encoder = InstructionEncoder(vocab_size=cfg.vocab_size, embedding_size=cfg.embedding_size, hidden_size=cfg.instr_hidden,
                                                       rnn_type=cfg.instr_rnn, bidirectional=False, final_state_only=True,
                                                       fine_tune_embeddings=True, embeddings=embeddings)
-        self.depth_encoder = _FlatDepthEncoder(cc * fs * fs, cfg.depth_out)
-        self.rgb_encoder = _FlatRgbEncoder(cfg.rgb_out)
+        self.depth_encoder = SimpleDepthCNN(cfg.depth_shape, cfg.depth_out) if self.simple_depth else _FlatDepthEncoder(cc * fs * fs, cfg.depth_out)
+        self.rgb_encoder = SimpleRGBCNN(cfg.rgb_shape, cfg.rgb_out) if self.simple_rgb else _FlatRgbEncoder(cfg.rgb_out)
         self.state_encoder = RNNStateEncoder(cfg.rnn_input_size, cfg.hidden, 1, cfg.rnn_type)
         self.progress_monitor = nn.Linear(cfg.hidden, 1)
         self.linear = nn.Linear(cfg.hidden, cfg.num_actions)
@@ -319,10 +349,16 @@ class Seq2SeqNet(_FromReference):
             raise ValueError(f"Seq2SeqNet takes instruction ({rows} or 1, L), got {tuple(instruction.shape)}")
         ins = self.instruction_encoder(instruction)                           # :153
         cc, fs = self.depth_shape
-        depth = _flat_visual("Seq2SeqNet", "S2SEngine", "depth", observations.get("depth_features"), self.depth_encoder.visual_fc[1],
-                             cfg.ablate_depth, rows, (cc, fs, fs), ins)
-        rgb = _flat_visual("Seq2SeqNet", "S2SEngine", "rgb", observations.get("rgb_features"), self.rgb_encoder.fc, cfg.ablate_rgb, rows,
-                           (2048, 1, 1), ins)
+        if self.simple_depth:
+            depth = _simple_visual("Seq2SeqNet", self.depth_encoder, observations, cfg.ablate_depth, rows, ins)
+        else:
+            depth = _flat_visual("Seq2SeqNet", "S2SEngine", "depth", observations.get("depth_features"), self.depth_encoder.visual_fc[1],
+                                 cfg.ablate_depth, rows, (cc, fs, fs), ins)
+        if self.simple_rgb:
+            rgb = _simple_visual("Seq2SeqNet", self.rgb_encoder, observations, cfg.ablate_rgb, rows, ins)
+        else:
+            rgb = _flat_visual("Seq2SeqNet", "S2SEngine", "rgb", observations.get("rgb_features"), self.rgb_encoder.fc, cfg.ablate_rgb, rows,
+                               (2048, 1, 1), ins)
         if cfg.ablate_instruction:
             ins = ins * 0                                                     # :156-157
         ins = ins.expand(rows, ins.shape[1])                                  # :163
@@ -493,20 +529,25 @@ class LowLevel(_FromReference):
     update_loss(batch, corrected_actions, oracle_stop) -> (result (8,), rnn_hidden_states) is the model and the criterion of the trainer's
     low-level step through flat_heads_loss without the monitor; result[0] + result[1] is the loss.
 
-    The SimpleCNN encoders are trunks that train with the model: there is nothing to cache, and they are refused."""
+    The SimpleCNN encoders are trunks that train with the model: there is nothing to cache, and without a keyword they are refused.  With
+    trainable_trunks=True a modality whose encoder is a SimpleCNN gets train.SimpleRGBCNN / train.SimpleDepthCNN under the reference's keys
+    (rgb_encoder.cnn.*, depth_encoder.cnn.*), reads observations["rgb"] / ["depth"] -- the frames -- in place of the cached feature, and is
+    loaded by load_reference_state_dict with everything else; a ResNet modality of the same model still trains from its cached feature.  The
+    state dict of such a model is what HCMEngine loads as its low-level weights."""
 
     FROZEN_PREFIXES = HCM_LOW_FROZEN_PREFIXES
     _flat_heads = staticmethod(flat_heads_loss)
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, trainable_trunks=False):
         super().__init__()
         cfg.validate()
-        _refuse_simple_cnn("LowLevel", cfg)
+        self.simple_rgb, self.simple_depth = _simple_trunks("LowLevel", cfg, trainable_trunks)
+        self.FROZEN_PREFIXES = _frozen_prefixes(self.simple_rgb, self.simple_depth)
         self.cfg = cfg
-        fs, cc = cfg.depth_final_spatial(), cfg.depth_compress_channels()
+        fs, cc = (0, 0) if self.simple_depth else (cfg.depth_final_spatial(), cfg.depth_compress_channels())
         self.depth_shape = (cc, fs)
-        self.depth_encoder = _FlatDepthEncoder(cc * fs * fs, cfg.depth_out)
-        self.rgb_encoder = _FlatRgbEncoder(cfg.rgb_out)
+        self.depth_encoder = SimpleDepthCNN(cfg.depth_shape, cfg.depth_out) if self.simple_depth else _FlatDepthEncoder(cc * fs * fs, cfg.depth_out)
+        self.rgb_encoder = SimpleRGBCNN(cfg.rgb_shape, cfg.rgb_out) if self.simple_rgb else _FlatRgbEncoder(cfg.rgb_out)
         self.sub_task_embedding = nn.Embedding(cfg.num_sub_tasks + 1, 32, padding_idx=cfg.num_sub_tasks)
         self.state_encoder = RNNStateEncoder(cfg.depth_out + cfg.rgb_out + 32, cfg.hidden, 1, cfg.rnn_type)
         self.progress_monitor = nn.Linear(cfg.hidden, 1)
@@ -531,10 +572,16 @@ class LowLevel(_FromReference):
         if discrete_actions.numel() != rows or discrete_actions.dtype.is_floating_point:
             raise ValueError(f"LowLevel takes discrete_actions ({rows},) as an integer tensor, got {discrete_actions.dtype} {tuple(discrete_actions.shape)}")
         cc, fs = self.depth_shape
-        depth = _flat_visual("LowLevel", "HCMEngine", "depth", _model_slot(observations.get("depth_features"), 1), self.depth_encoder.visual_fc[1],
-                             cfg.ablate_depth, rows, (cc, fs, fs), rnn_hidden_states)
-        rgb = _flat_visual("LowLevel", "HCMEngine", "rgb", _model_slot(observations.get("rgb_features"), 1), self.rgb_encoder.fc, cfg.ablate_rgb,
-                           rows, (2048, 1, 1), rnn_hidden_states)
+        if self.simple_depth:
+            depth = _simple_visual("LowLevel", self.depth_encoder, observations, cfg.ablate_depth, rows, rnn_hidden_states)
+        else:
+            depth = _flat_visual("LowLevel", "HCMEngine", "depth", _model_slot(observations.get("depth_features"), 1),
+                                 self.depth_encoder.visual_fc[1], cfg.ablate_depth, rows, (cc, fs, fs), rnn_hidden_states)
+        if self.simple_rgb:
+            rgb = _simple_visual("LowLevel", self.rgb_encoder, observations, cfg.ablate_rgb, rows, rnn_hidden_states)
+        else:
+            rgb = _flat_visual("LowLevel", "HCMEngine", "rgb", _model_slot(observations.get("rgb_features"), 1), self.rgb_encoder.fc, cfg.ablate_rgb,
+                               rows, (2048, 1, 1), rnn_hidden_states)
         sub_task = self.sub_task_embedding(discrete_actions.reshape(-1).long())    # :141
         x = torch.cat([depth, rgb, sub_task], 1)                               # :143
         return self.state_encoder(x, rnn_hidden_states, masks)                 # :147

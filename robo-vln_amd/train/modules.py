@@ -11,12 +11,16 @@ everything behind them is `vla_layer` / `vla_layer_ref`.
 `Visual_Ling_Attn`: the reference's whole cross-modal encoder (transformer.py:250-282): both prologue halves on `embed_ln` / `embed_ln_ref`, then
 its `InterModuleAttnLayer`s.
 
-`InstructionEncoder`: the reference's InstructionEncoder (models/encoders/instruction_encoder.py:70-92) around `instr_scan` / `instr_encoder_ref`."""
+`InstructionEncoder`: the reference's InstructionEncoder (models/encoders/instruction_encoder.py:70-92) around `instr_scan` / `instr_encoder_ref`.
+
+`SimpleDepthCNN`, `SimpleRGBCNN`: the reference's trainable SimpleCNN encoders (models/encoders/simple_cnns.py:104-147); the three convolutions are
+`simple_cnn` / `simple_cnn_ref`, cnn.7 and its ReLU are torch."""
 import torch
 from torch import nn
 
 from .ops import (EMBED_K_STEP, EMBED_MAX_K, INSTR_HIDDEN, SCAN_HIDDEN, VLA_D_MODEL, VLA_HEADS, VLA_MAX_D_FF, cell_loop, embed_k_ok, embed_ln,
-                  embed_ln_ref, instr_encoder_ref, instr_scan, sinusoid_table, state_scan, vla_layer, vla_layer_ref)
+                  embed_ln_ref, instr_encoder_ref, instr_scan, simple_cnn, simple_cnn_out_hw, simple_cnn_ref, sinusoid_table, state_scan, vla_layer,
+                  vla_layer_ref)
 
 
 class RNNStateEncoder(nn.Module):
@@ -274,3 +278,69 @@ class InstructionEncoder(nn.Module):
                 raise ValueError(f"on the device InstructionEncoder serves hidden_size {INSTR_HIDDEN} (got {self.hidden_size})")
             y = instr_scan(embedded, lengths, self._params(), self.final_state_only)
         return y if self.final_state_only else y.permute(0, 2, 1)
+
+
+class _SimpleCNN(nn.Module):
+    """Drop-in for the reference's SimpleAllCNN with one modality (simple_cnns.py:51-101): the reference's state-dict keys cnn.0.*, cnn.2.*,
+    cnn.4.*, cnn.7.* with the shapes robo_vln_amd.synth.simple_cnn_spec lists, in a real nn.Sequential (storage and initialisation only:
+    habitat's layer_init as habitat writes it, kaiming_normal_(weight, calculate_gain("relu")) -- the gain lands in
+    the slope argument `a` -- and zero biases), so load_state_dict takes a reference checkpoint's keys unchanged.
+    frame_hw is the frame's (H, W), or one number for a square frame.
+
+    forward(observations) reads observations[KEY] (rows, H, W, CHANNELS) and returns (rows, output_size).  The three convolutions are
+    simple_cnn on the device and simple_cnn_ref on the CPU; cnn.7 and its ReLU are torch, one dense product."""
+
+    KEY, CHANNELS, SCALE = None, 0, 1.0
+    ROUTES = {"hip": simple_cnn, "torch": simple_cnn_ref}
+    HIP_MAX_FRAME_PIXELS = 0        # rows x H x W up to which the op was not slower than torch (profiles/simplecnn_train.md)
+    route = "auto"
+
+    def __init__(self, frame_hw, output_size):
+        super().__init__()
+        H, W = (frame_hw, frame_hw) if isinstance(frame_hw, int) else frame_hw
+        self.frame_hw = (int(H), int(W))
+        h3, w3 = simple_cnn_out_hw(*self.frame_hw)
+        if h3 < 1 or w3 < 1:
+            raise ValueError(f"{type(self).__name__}: a {H} x {W} frame leaves no pixel behind the three convolutions")
+        self.cnn = nn.Sequential(nn.Conv2d(self.CHANNELS, 32, 8, 4), nn.ReLU(True), nn.Conv2d(32, 64, 4, 2), nn.ReLU(True), nn.Conv2d(64, 32, 3, 1),
+                                 nn.Identity(), nn.Flatten(), nn.Linear(32 * h3 * w3, output_size), nn.ReLU(True))
+        self.layer_init()
+
+    def layer_init(self):
+        for layer in self.cnn:
+            if isinstance(layer, (nn.Conv2d, nn.Linear)):
+                nn.init.kaiming_normal_(layer.weight, nn.init.calculate_gain("relu"))
+                if layer.bias is not None:
+                    nn.init.constant_(layer.bias, val=0)
+
+    @property
+    def output_size(self):
+        return self.cnn[7].out_features
+
+    def device_route(self, rows):
+        """"hip" or "torch" for a device call of `rows` frames: `route` when it names one, otherwise the measured rule"""
+        if self.route != "auto":
+            return self.route
+        return "hip" if rows * self.frame_hw[0] * self.frame_hw[1] <= self.HIP_MAX_FRAME_PIXELS else "torch"
+
+    def forward(self, observations):
+        if self.KEY not in observations:
+            raise ValueError(f"{type(self).__name__} trains from the frames: observations['{self.KEY}'] is missing")
+        x = observations[self.KEY]
+        if x.dim() != 4 or tuple(x.shape[1:]) != (*self.frame_hw, self.CHANNELS):
+            raise ValueError(f"{type(self).__name__} takes observations['{self.KEY}'] (rows, {self.frame_hw[0]}, {self.frame_hw[1]}, {self.CHANNELS}), "
+                             f"got {tuple(x.shape)}")
+        c1, c2, c3 = self.cnn[0], self.cnn[2], self.cnn[4]
+        fn = self.ROUTES[self.device_route(x.shape[0])] if x.is_cuda else simple_cnn_ref
+        y = fn(x, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias, self.SCALE)
+        return torch.relu(self.cnn[7](y.flatten(1)))
+
+
+class SimpleDepthCNN(_SimpleCNN):
+    """The reference's SimpleDepthCNN (simple_cnns.py:104-125): observations["depth"] (rows, H, W, 1), float32"""
+    KEY, CHANNELS, SCALE = "depth", 1, 1.0
+
+
+class SimpleRGBCNN(_SimpleCNN):
+    """The reference's SimpleRGBCNN (simple_cnns.py:128-147): observations["rgb"] (rows, H, W, 3), float32 or uint8, divided by 255"""
+    KEY, CHANNELS, SCALE = "rgb", 3, 1.0 / 255.0

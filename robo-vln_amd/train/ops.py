@@ -1,4 +1,4 @@
-"""The training ops: seven autograd functions over the HIP training kernels, each with its public wrapper and its pure-torch restatement.  Device
+"""The training ops: eight autograd functions over the HIP training kernels, each with its public wrapper and its pure-torch restatement.  Device
 tensors go through the kernels, at the sizes the kernels are built for, and anything else on the device raises; the restatement is the CPU
 path of the drop-in modules (train/modules.py) and what the GPU tests compare against, not a fallback for a missing kernel.
 
@@ -26,7 +26,12 @@ are csrc/cma_attn_train.hip, `attn1q_ref` is the restatement.
 and the masked criteria -- over csrc/flat_heads_train.hip (two launches forward, two backward); `flat_heads_loss_ref` is the restatement.
 
 `subtask_ce`: the high-level criterion of the hierarchical trainer's `_update_agent` (hierarchical_trainer.py:492-560) -- `linear`, masked_fill_,
-CrossEntropyLoss(ignore_index=-1) -- over csrc/subtask_ce_train.hip (two launches forward, two backward); `subtask_ce_ref` is the restatement."""
+CrossEntropyLoss(ignore_index=-1) -- over csrc/subtask_ce_train.hip (two launches forward, two backward); `subtask_ce_ref` is the restatement.
+
+`simple_cnn`: the convolutional part of the reference's SimpleAllCNN.cnn (models/encoders/simple_cnns.py:76-95) -- Conv2d(Cin, 32, 8, 4), ReLU,
+Conv2d(32, 64, 4, 2), ReLU, Conv2d(64, 32, 3, 1) over depth or RGB frames -- on the float32 kernels of csrc/simplecnn_train.hip, one launch per
+convolution forward, and backward a weight-gradient launch with its ordered reduce, a bias sum and a data-gradient launch per layer;
+`simple_cnn_ref` is the restatement."""
 import ctypes as C
 import math
 
@@ -39,6 +44,7 @@ SCAN_HIDDEN = 512
 INSTR_HIDDEN = 256
 VLA_D_MODEL, VLA_HEADS, VLA_MAX_KEYS, VLA_MAX_D_FF = 256, 4, 64, 1024
 EMBED_K_STEP, EMBED_MAX_K = 64, 1024
+SIMPLE_CNN_MIN_HW, SIMPLE_CNN_CHANNELS = 36, (1, 3)
 
 
 def _ptr(t):
@@ -839,3 +845,89 @@ def subtask_ce(x, w, b, oracle_subtask, num_sub_tasks=None):
     if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or w.dim() != 2 or not subtask_ce_ok(x.shape[0], x.shape[1], w.shape[0], nst):
         return subtask_ce_ref(x, w, b, oracle_subtask, num_sub_tasks)
     return _SubtaskCe.apply(x, w, b, _subtask_labels(oracle_subtask, x.shape[0], x.device), nst)
+
+
+def simple_cnn_out_hw(H, W):
+    """(h3, w3) of the last map for an H x W frame: three unpadded convolutions, 8/4, 4/2, 3/1 (simple_cnns.py:63-73)"""
+    for k, st in ((8, 4), (4, 2), (3, 1)):
+        H, W = (H - k) // st + 1, (W - k) // st + 1
+    return H, W
+
+
+def simple_cnn_ref(x, w1, b1, w2, b2, w3, b3, scale=1.0, _taps=None):
+    """Pure-torch restatement of the convolutional part of SimpleAllCNN.cnn, any dtype and device: x (B, H, W, Cin) as the observations carry the
+    frames, permuted to NCHW and multiplied by `scale` (simple_cnns.py:122-125, :144-147: 1/255 for RGB); the weights as nn.Conv2d stores them.
+    Returns (B, 32, h3, w3); .flatten(1) is the reference's Flatten order in front of cnn.7."""
+    F = torch.nn.functional
+    x = x.to(w1.dtype).permute(0, 3, 1, 2) * scale
+    p1 = F.conv2d(x, w1, b1, stride=4)
+    p2 = F.conv2d(torch.relu(p1), w2, b2, stride=2)
+    if _taps is not None:
+        _taps.update(pre1=p1, pre2=p2)
+    return F.conv2d(torch.relu(p2), w3, b3, stride=1)
+
+
+def _simple_cnn_check(x, w1, b1, w2, b2, w3, b3):
+    """the refusals of simple_cnn that need no device"""
+    if x.requires_grad:
+        raise ValueError("simple_cnn: the frames must not require a gradient (there is no frame gradient)")
+    if x.dim() != 4 or x.shape[3] not in SIMPLE_CNN_CHANNELS:
+        raise ValueError(f"simple_cnn takes frames (B, H, W, Cin) with Cin in {SIMPLE_CNN_CHANNELS}, got {tuple(x.shape)}")
+    B, H, W, Cin = x.shape
+    if H < SIMPLE_CNN_MIN_HW or W < SIMPLE_CNN_MIN_HW:
+        raise ValueError(f"simple_cnn: frames must be at least {SIMPLE_CNN_MIN_HW} x {SIMPLE_CNN_MIN_HW}, got {H} x {W}")
+    if x.dtype != torch.float32 and not (x.dtype == torch.uint8 and Cin == 3):
+        raise ValueError(f"simple_cnn takes float32 frames, or uint8 RGB frames, got {x.dtype} with {Cin} channel(s)")
+    _check_shapes("simple_cnn", (("w1", w1, (32, Cin, 8, 8)), ("b1", b1, (32,)), ("w2", w2, (64, 32, 4, 4)), ("b2", b2, (64,)),
+                                 ("w3", w3, (32, 64, 3, 3)), ("b3", b3, (32,))))
+    return B, H, W, Cin
+
+
+class _SimpleCnn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, scale):
+        _on_device("simple_cnn", "simple_cnn_ref", "x", x, (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("w3", w3), ("b3", b3)))
+        B, H, W, Cin = _simple_cnn_check(x, w1, b1, w2, b2, w3, b3)
+        n = _lib.lib().hcm_op_simplecnn_work_floats(B, H, W, Cin)
+        if B < 1 or not n:
+            raise ValueError(f"simple_cnn serves B >= 1 and calls whose element offsets fit 31 bits, got frames {tuple(x.shape)}")
+        x = x.detach().contiguous()
+        w1, b1, w2, b2, w3, b3 = (_f32c(t) for t in (w1, b1, w2, b2, w3, b3))
+        dt = _lib.HCM_U8 if x.dtype == torch.uint8 else _lib.HCM_F32
+        h3, w3_ = simple_cnn_out_hw(H, W)
+        y = torch.empty(B, 32, h3, w3_, device=x.device)
+        work = torch.empty(n, device=x.device)
+        _lib.check(_lib.lib().hcm_op_simplecnn_train(_ptr(x), dt, scale, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(y), _ptr(work),
+                                                     B, H, W, Cin, _stream()))
+        ctx.save_for_backward(x, w2, w3, work)
+        ctx.dims = (B, H, W, Cin, dt, scale)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        x, w2, w3, work = ctx.saved_tensors
+        B, H, W, Cin, dt, scale = ctx.dims
+        dev = x.device
+        d_y = _f32c(d_y)
+        d_w1, d_b1 = torch.empty(32, Cin, 8, 8, device=dev), torch.empty(32, device=dev)
+        d_w2, d_b2 = torch.empty(64, 32, 4, 4, device=dev), torch.empty(64, device=dev)
+        d_w3, d_b3 = torch.empty(32, 64, 3, 3, device=dev), torch.empty(32, device=dev)
+        _lib.check(_lib.lib().hcm_op_simplecnn_bwd(_ptr(d_y), _ptr(x), dt, scale, _ptr(w2), _ptr(w3), _ptr(work), _ptr(d_w1), _ptr(d_b1), _ptr(d_w2),
+                                                   _ptr(d_b2), _ptr(d_w3), _ptr(d_b3), B, H, W, Cin, _stream()))
+        need = ctx.needs_input_grad
+        return (None, *(g if need[1 + i] else None for i, g in enumerate((d_w1, d_b1, d_w2, d_b2, d_w3, d_b3))), None)
+
+
+def simple_cnn(x, w1, b1, w2, b2, w3, b3, scale=1.0):
+    """The convolutional part of SimpleAllCNN.cnn (float32, on the device) with gradients to the six parameters: arguments and result as
+    simple_cnn_ref; frames (B >= 1, H, W, Cin) with Cin 1 or 3 and H, W >= 36 (non-square and any remainder allowed), float32 or, for RGB, uint8;
+    a frame that requires a gradient, another Cin, a smaller frame or another dtype raises ValueError.
+
+    Forward: hcm_op_simplecnn_train packs the weights and runs one launch per convolution; the two post-ReLU maps stay in the call's work
+    buffer, which the autograd node keeps.  Backward: hcm_op_simplecnn_bwd on that buffer -- per layer a weight-gradient launch over chunks of
+    pixels with an ordered reduce, a bias sum, and for conv3 and conv2 a data-gradient launch gated by `stored value > 0`.  There is no frame
+    gradient.  A row's forward bits depend on that row and the weights alone, and two runs give the same bits.  cnn.7 behind it is a dense
+    product and stays in torch.  Nothing is cached between calls: the weights are packed on the device in every call."""
+    _simple_cnn_check(x, w1, b1, w2, b2, w3, b3)
+    return _SimpleCnn.apply(x, w1, b1, w2, b2, w3, b3, float(scale))
